@@ -1,13 +1,17 @@
 #!/usr/bin/env python
 """Headline benchmark: VQ-VAE train step (BASELINE.json configs[1]: standard K=1024, 256x256, bs=32/GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = preprocess -> encoder -> quantizer -> decoder -> MSE -> backward -> one flat-gradient all-reduce
 -> AdamW, on a synthetic U(0,1) batch that is resident in HBM before the timed region.  Rank 0 prints ONE
-JSON line.  `roofline` is for the dominant kernel (the implicit-GEMM conv): algorithmic FLOPs of its launches
+JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figures (`value`, `ms_per_step`);
+`--dump-outputs DIR` also writes what the timed path's step computes (`dump_outputs`).  Everything below is measured only
+with `--full`: the sustained loop, the kernel event pass, the box calibration, the collective probe, the VQ kernel, the
+CPU baseline with the parity cost, the other BASELINE.json configs and the HBM traffic passes.
+`roofline` is for the dominant kernel (the implicit-GEMM conv): algorithmic FLOPs of its launches
 (2*M*Cout*Cin*k*k each) over their HIP-event durations, recorded on the launch stream -- inside the timed region when the step
 is issued eagerly (--no-graph), in eager steps of the same shapes right after it when the timed region replays hipGraphs (events
 cannot be read back from inside a replayed graph; `roofline.event_pass` says which).
@@ -194,7 +198,7 @@ def other_configs(steps: int = 20, warmup: int = 5) -> dict:
     res = {}
     for label, argv in OTHER_CONFIGS.items():
         try:
-            j, r = _child(argv + ['--steps', str(steps), '--warmup', str(warmup), '--no-cpu-baseline'])
+            j, r = _child(argv + ['--steps', str(steps), '--warmup', str(warmup), '--no-cpu-baseline', '--full'])
             if j is None:
                 res[label] = dict(error=(r.stderr or r.stdout)[-300:])
             else:
@@ -220,6 +224,21 @@ GN_FAMILIES = {      # bench event name -> kernel symbols behind it (csrc/norm.h
 }
 
 
+def traffic_argv(argv) -> list:
+    """the workload options of this command line for the traffic passes: run length, measurement and output options dropped"""
+    keep = []
+    skip = {'--steps', '--warmup', '--sustain-s', '--traffic', '--cpu-batch', '--cpu-steps', '--dump-outputs'}
+    it = iter(argv)
+    for a in it:
+        if a in skip:
+            next(it, None)
+        elif a.split('=', 1)[0] in skip:
+            continue
+        elif a not in ('--no-graph', '--no-cpu-baseline', '--no-kernel-events', '--no-other-configs', '--quick', '--full'):
+            keep.append(a)
+    return keep
+
+
 def measure_traffic(kernel_sub: str, events_per_step: int, argv):
     """HBM bytes per bench event of the dominant kernel -- and per STEP of the GroupNorm kernel families -- measured now: two
     rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE -- separate passes, counters only, as MI355X_MICROARCH.md prescribes) over a
@@ -231,14 +250,7 @@ def measure_traffic(kernel_sub: str, events_per_step: int, argv):
     prof = shutil.which('rocprofv3') or ('/opt/rocm/bin/rocprofv3' if os.path.exists('/opt/rocm/bin/rocprofv3') else None)
     if prof is None:
         return None, None, {}
-    keep = []
-    skip = {'--steps', '--warmup', '--sustain-s', '--traffic', '--cpu-batch', '--cpu-steps'}
-    it = iter(argv)
-    for a in it:
-        if a in skip:
-            next(it, None)
-        elif a not in ('--no-graph', '--no-cpu-baseline', '--no-kernel-events', '--no-other-configs', '--quick'):
-            keep.append(a)
+    keep = traffic_argv(argv)
     steps = 2
     total, fam = {}, {k: {} for k in GN_FAMILIES}
     try:
@@ -365,6 +377,39 @@ def box_calibration(device, ms_per_step, seconds: float = 0.3) -> dict:
     return out
 
 
+DUMP_SAMPLE = 1 << 14        # elements kept of a larger tensor by dump_outputs (64 KiB each in float32)
+DUMP_LIMIT = 64 << 20        # bytes a dump may hold in all
+
+
+def dump_outputs(out_dir: str, model, loss) -> dict:
+    """What a step of the timed path hands its caller, as ``out_dir/<name>.npy``: ``loss`` (float64), ``state.<name>`` for every
+    tensor of the model's state after that step's optimizer update (parameters and buffers) and ``grad.<name>`` for every
+    parameter gradient of the step.  Floating-point tensors are written as float32 (float64 stays float64), integer ones as
+    float64.  A tensor of more than DUMP_SAMPLE elements is written as a fixed sample of its logical (NCHW-order) elements:
+    DUMP_SAMPLE indices drawn with a generator seeded by the element count, the same in every run and every build."""
+    import numpy as np
+    tensors = {'loss': loss.detach().reshape(1).double()}
+    for k, v in model.state_dict().items():
+        tensors['state.' + k] = v
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            tensors['grad.' + k] = p.grad
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in tensors.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(t.numel()))
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy() if t.dtype == torch.float64 else t.double().cpu().numpy() if not t.is_floating_point() \
+            else t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError(f'--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}')
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return dict(files=len(tensors), bytes=total)
+
+
 def _flush_c_stdio():
     try:
         import ctypes
@@ -415,6 +460,14 @@ def main():
                     help='multi-GPU runs: keep going (with "degraded" in the line) when the hipGraph capture fails; default: exit 3')
     ap.add_argument('--no-calibration', action='store_true', help='skip the 0.6 s box calibration (box_calibration in the line)')
     ap.add_argument('--deterministic', action='store_true', help='deterministic mode (vqvae/train.py:130): ordered partial sums instead of atomics; reports its cost')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure everything beyond the headline figure (sustained loop, kernel '
+                         'event pass and rooflines, box calibration, collective probe, VQ kernel, CPU baseline and parity cost, '
+                         'other BASELINE.json configs, HBM traffic passes); the --no-* / --sustain-s / --traffic / --cpu-* / '
+                         '--quick options shape those measurements')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, run the timed path\'s step once more from the seeded starting state and write '
+                         'what it computed (loss, model state, gradients; a fixed sample of each large tensor) as DIR/<name>.npy')
     ap.add_argument('--sustain-s', type=float, default=10.0,
                     help='after the K timed steps keep stepping for this many seconds and report the sustained ms/step '
                          '(clock / power settle below the short run; 0 = off; N=1 only)')
@@ -478,6 +531,8 @@ def main():
     model.on_train_start()
     g = torch.Generator().manual_seed(1234 + rank)
     images = torch.rand(args.batch, 3, args.image_size, args.image_size, generator=g).to(device)
+    # --dump-outputs: the seeded starting state (weights, buffers, optimizer moments, step counts, RNG), put back for the dumped step
+    start_state = trainer._snapshot(model) if args.dump_outputs else None
     native = importlib.import_module('vqvae-vqgan-pytorch-lightning_amd._native')
 
     def barrier():
@@ -561,7 +616,7 @@ def main():
     for i in range(args.warmup):
         step_fn(model, images, i)
     barrier()
-    if not use_graph and not args.no_kernel_events:
+    if args.full and not use_graph and not args.no_kernel_events:
         ops.KERNEL_EVENTS = []
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -570,8 +625,22 @@ def main():
     elapsed = time.perf_counter() - t0
     ops.check_kernel_health()          # a timed-out GroupNorm cluster = wrong gradients: the line must not be printed as if nothing happened
     events, ops.KERNEL_EVENTS = ops.KERNEL_EVENTS, None
+    final_loss = round(float(loss.item()), 6)
+    if args.dump_outputs:
+        # the state the last timed step starts from carries the arrival-order rounding of every earlier step's gradient atomics,
+        # which AdamW's sign-like updates (beta1 = 0) amplify: two runs drift apart within a few steps.  The dumped step is the
+        # timed path's step once more, with the last timed step's batch index, from the seeded starting state: the same inputs
+        # in every run, so two runs (and two builds) differ by the rounding of one step
+        trainer._restore(model, start_state)
+        del start_state
+        barrier()
+        last = step_fn(model, images, args.warmup + args.steps - 1)
+        barrier()
+        if rank == 0:
+            d = dump_outputs(args.dump_outputs, model, last)
+            print(f'[bench] --dump-outputs: {d["files"]} arrays, {d["bytes"] / 1e6:.1f} MB in {args.dump_outputs}', file=sys.stderr)
     sustained = None
-    if world == 1 and args.sustain_s > 0:
+    if args.full and world == 1 and args.sustain_s > 0:
         # the K timed steps above are the metric; this is the same loop held for seconds, not fractions of one
         n_sus, t1 = 0, time.perf_counter()
         chunk = max(10, int(0.5 / max(elapsed / args.steps, 1e-4)))
@@ -588,7 +657,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     event_steps = args.steps
-    if use_graph and not args.no_kernel_events:
+    if args.full and use_graph and not args.no_kernel_events:
         # per-kernel HIP-event timing cannot be recorded inside a replayed graph: time the SAME kernels (same
         # shapes, same stream) in eager steps right after the timed region
         event_steps = 3
@@ -601,7 +670,7 @@ def main():
         events, ops.KERNEL_EVENTS = ops.KERNEL_EVENTS, None
 
     calib = None
-    if rank == 0 and not args.no_calibration and os.environ.get('VQK_BENCH_CHILD') != '1':
+    if args.full and rank == 0 and not args.no_calibration and os.environ.get('VQK_BENCH_CHILD') != '1':
         try:
             calib = box_calibration(device, elapsed / args.steps * 1e3)
         except Exception as exc:
@@ -609,7 +678,7 @@ def main():
     if dist.is_initialized():
         dist.barrier()
     comm = None
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         # proof of what RCCL saw, and what the collectives cost on the critical path (same loop, collectives muted)
         opt0 = trainer.optimizers[0]
         vqm = importlib.import_module('vqvae-vqgan-pytorch-lightning_amd.modules.vector_quantizers')
@@ -729,7 +798,7 @@ def main():
 
     result_line = None
     vq_kernel = None
-    if rank == 0 and not args.no_kernel_events:
+    if args.full and rank == 0 and not args.no_kernel_events:
         # the other kernel BASELINE.json's north_star names: the VQ distance / argmin kernel at this config's (N, K, D)
         try:
             sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -742,7 +811,7 @@ def main():
             vq_kernel = dict(error=f'{type(exc).__name__}: {exc}')
     if rank == 0:
         cpu = parity = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, oracle_step = cpu_baseline(run, args.image_size, args.cpu_batch, args.cpu_steps)
             if qtype == 'standard' and not args.gan:
                 try:
@@ -767,16 +836,19 @@ def main():
                                         'tail all-reduce, AdamW') if (use_graph and getattr(trainer, '_graph2', None) is not None) else
                                        'three hipGraphs (AE half | discriminator half | discriminator half + R1), optimizer steps between' if (use_graph and args.gan) else
                                        'hipGraph replay (fwd+bwd) + eager all-reduce + AdamW' if use_graph else 'eager'),
-                               deterministic=bool(ops.DETERMINISTIC), final_loss=round(float(loss.item()), 6),
+                               deterministic=bool(ops.DETERMINISTIC), final_loss=final_loss,
                                rccl_ranks=None if comm is None else comm['rccl_ranks'],
-                               collectives_per_step=0 if comm is None else comm['collectives_per_step']),
-                   roofline=roofline, step_roofline=step_roofline, cpu_baseline=cpu, vq_kernel=vq_kernel, sustained=sustained, comm=comm,
-                   bf16_vs_fp32_oracle=parity, box_calibration=calib)
+                               # (counted by the collective probe of --full; a single process issues none)
+                               collectives_per_step=(comm['collectives_per_step'] if comm is not None else
+                                                     None if dist.is_initialized() else 0)))
+        if args.full:
+            out.update(roofline=roofline, step_roofline=step_roofline, cpu_baseline=cpu, vq_kernel=vq_kernel, sustained=sustained,
+                       comm=comm, bf16_vs_fp32_oracle=parity, box_calibration=calib)
         if degraded is not None:
             out['degraded'] = degraded
         if one_gpu and world > 1:
             out['degraded'] = f'dry run: {world} ranks share ONE GPU over gloo (VQK_BENCH_ONE_GPU=1) -- control flow only, not a scaling figure'
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             out['other_configs'] = other_configs()
         result_line = json.dumps(out)
     if dist.is_initialized():

@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 env = dict(os.environ, VQK_EVENT_SHAPES='1', VQK_BENCH_CHILD='1')
-cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--steps', '20', '--warmup', '5'] + sys.argv[1:]
+cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--steps', '20', '--warmup', '5'] + sys.argv[1:]
 r = subprocess.run(cmd, env=env, capture_output=True, text=True)
 line = next((l for l in reversed(r.stdout.splitlines()) if l.startswith('{')), None)
 if line is None:
