@@ -102,6 +102,7 @@ int launch_conv3x3_wgrad_x3(const void* x, const void* dy, float* dw, const Conv
 int launch_conv3x3_thin_out_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int n, int h, int wd,
                                 int cin, int act, float acc_scale, float out_gain, hipStream_t st);
 int launch_conv3x3_thin_in_f32(const float* x, const float* w, const float* bias, float* y, int n, int h, int wd, int cout, hipStream_t st);
+int thin_wgrad_rows(int h, int w);        // rows per block of the weight-gradient kernel, 0: the shape is not served
 int launch_conv3x3_wgrad_thin_f32(int mode, const float* wide, const float* thin, float* dw, int n, int h, int w, int cw, float scale,
                                   hipStream_t st);
 

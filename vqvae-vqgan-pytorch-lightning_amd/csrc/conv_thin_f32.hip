@@ -299,14 +299,27 @@ int launch_conv3x3_thin_out_f32(const float* x, const float* w, const float* bia
 
 static inline int thin_rows_per_block(int h) { return (h % 8) == 0 ? 8 : (h % 4) == 0 ? 4 : (h % 2) == 0 ? 2 : 1; }
 
+static inline size_t thin_wgrad_lds(int R, int w) {
+    const size_t lds = (size_t)(R + 2) * (w + 2) * 16;
+    return lds < 4 * 36 * 64 * 4 ? 4 * 36 * 64 * 4 : lds;        // the block reduction reuses the buffer
+}
+
+// output rows per block of the weight-gradient kernel: the largest R in {8, 4, 2, 1} that divides h and whose R + 2 staged thin
+// rows fit in 64 KiB of LDS (8 rows up to w = 407, 1 row up to w = 1363); 0 when no R fits -- wgrad_general then takes the
+// general fp32 kernel.  The dispatch (conv_wgrad.hip) and the launcher below both ask this, so they cannot disagree.
+int thin_wgrad_rows(int h, int w) {
+    for (int R = thin_rows_per_block(h); R >= 1; R >>= 1)
+        if (thin_wgrad_lds(R, w) <= 64 * 1024) return R;
+    return 0;
+}
+
 // mode 0: thin = x [n][h][w][4], wide = dy [n][h][w][cw], dw [cw][3][3][4]; mode 1: wide = x [..][cw], thin = dy [..][4], dw [4][3][3][cw]
 int launch_conv3x3_wgrad_thin_f32(int mode, const float* wide, const float* thin, float* dw, int n, int h, int w, int cw, float scale,
                                   hipStream_t st) {
     if ((cw != 64 && cw != 128 && cw != 256) || (w & 3) || w < 4) return VQK_ERR_SHAPE;
-    const int R = thin_rows_per_block(h);
-    size_t lds = (size_t)(R + 2) * (w + 2) * 16;
-    if (lds < 4 * 36 * 64 * 4) lds = 4 * 36 * 64 * 4;            // the block reduction reuses the buffer
-    if (lds > 64 * 1024) return VQK_ERR_SHAPE;
+    const int R = thin_wgrad_rows(h, w);
+    if (R == 0) return VQK_ERR_SHAPE;
+    const size_t lds = thin_wgrad_lds(R, w);
     const unsigned blocks = (unsigned)(n * (h / R));
     if (mode == 0)
         hipLaunchKernelGGL(conv3x3_wgrad_thin_f32_kernel<0>, dim3(blocks), dim3(256), lds, st, wide, thin, dw, n, h, w, cw, scale, R);

@@ -767,8 +767,10 @@ static int wgrad_general(int dtype, const void* x, const void* dy, float* dw, in
         VQK_CHECK_LAUNCH();
         return VQK_OK;
     }
-    if (plain && dtype == VQK_F32 && ksize == 3 && mode == 0 && !g_det && !dy_pool && g_force_variant != 0 && (g.w % 4) == 0) {
-        // the edge convs' weight gradients in the fp32 modes (conv_thin_f32.hip)
+    if (plain && dtype == VQK_F32 && ksize == 3 && mode == 0 && !g_det && !dy_pool && g_force_variant != 0 && (g.w % 4) == 0 &&
+        vqkd::thin_wgrad_rows(g.h, g.w) > 0) {
+        // the edge convs' weight gradients in the fp32 modes (conv_thin_f32.hip); maps too wide for one staged row in LDS take the
+        // general kernel below
         if (cin == 4 && (cout == 64 || cout == 128 || cout == 256))
             return vqkd::launch_conv3x3_wgrad_thin_f32(0, (const float*)dy, (const float*)x, dw, n, g.h, g.w, cout, dy_scale, vqk_stream(stream));
         if (cout == 4 && (cin == 64 || cin == 128 || cin == 256))
