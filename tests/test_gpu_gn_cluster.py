@@ -44,19 +44,34 @@ def _run(x, st, w, b, dy, groups, add=None, pooled=None):
 def test_cluster_backward_equals_two_kernel_form_and_fp64(dtype, n, c, h, mode):
     if mode == 'pooled' and h * h <= 1024:
         pytest.skip('the pooled addend exists for maps above 32x32 only')
-    g = torch.Generator().manual_seed(n * c + h)
+    _cluster_vs_two_kernel_and_fp64(dtype, n, c, h, h, mode)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize('n,c,h,wd', [(3, 128, 16, 64), (2, 128, 64, 16), (2, 256, 8, 128), (2, 128, 48, 80), (2, 256, 80, 48)])
+@pytest.mark.parametrize('mode', ['plain', 'add', 'pooled'])
+def test_cluster_backward_nonsquare_maps(dtype, n, c, h, wd, mode):
+    """rectangular maps: on the square power-of-two maps above, a block's pixel range is whole rows; at 48 x 80 it starts and ends
+    mid-row, where the pooled addend's (row / 2, col / 2) lookup must follow.  Pooled at <= 1024 pixels: the map doubled."""
+    if mode == 'pooled' and h * wd <= 1024:
+        return _cluster_vs_two_kernel_and_fp64(dtype, n, c, 2 * h, 2 * wd, mode)
+    _cluster_vs_two_kernel_and_fp64(dtype, n, c, h, wd, mode)
+
+
+def _cluster_vs_two_kernel_and_fp64(dtype, n, c, h, wd, mode):
+    g = torch.Generator().manual_seed(n * c + h + 7 * (wd - h))
     mk = lambda *s: torch.randn(*s, generator=g)
-    x32, dy32 = mk(n, c, h, h), mk(n, c, h, h)
+    x32, dy32 = mk(n, c, h, wd), mk(n, c, h, wd)
     x = x32.to(dtype).to(DEV).contiguous(memory_format=CL)
     dy = dy32.to(dtype).to(DEV).contiguous(memory_format=CL)
     w = (mk(c) * 0.2 + 1).to(DEV); b = (mk(c) * 0.2).to(DEV)
-    add = mk(n, c, h, h).to(dtype).to(DEV).contiguous(memory_format=CL) if mode == 'add' else None
-    pooled = mk(n, c, h // 2, h // 2).to(dtype).to(DEV).contiguous(memory_format=CL) if mode == 'pooled' else None
+    add = mk(n, c, h, wd).to(dtype).to(DEV).contiguous(memory_format=CL) if mode == 'add' else None
+    pooled = mk(n, c, h // 2, wd // 2).to(dtype).to(DEV).contiguous(memory_format=CL) if mode == 'pooled' else None
     _, st = ops.raw_gn_forward(x, w, b, 32, 1e-6, True)
     lib = native.lib()
     saved, ops.GN_CLUSTER_MAX_HW = ops.GN_CLUSTER_MAX_HW, 1 << 20
     lib.vqk_set_tuning(b'GN_CLUSTER_MAX_HW', 1 << 20)                   # (the shipped default keeps the cluster form to <= 32x32 maps)
-    assert ops._gn_cluster(dtype, h * h, c, 32)
+    assert ops._gn_cluster(dtype, h * wd, c, 32)
     got = _run(x, st, w, b, dy, 32, add, pooled)
     ws = ops._gn_ws(x.device, 0)
     torch.cuda.synchronize()

@@ -383,9 +383,23 @@ def test_group_norm_silu_golden(golden, tag, dtype):
     close(ops.group_norm_silu(x, w, b, 32, 1e-6, False), g[f'{tag}.gn'], rtol=2e-2 if lo else 1e-4, atol=3e-2 if lo else 2e-5)
     y = ops.group_norm_silu(x, w, b, 32, 1e-6, True)
     close(y, g[f'{tag}.y'], rtol=2e-2 if lo else 1e-4, atol=3e-2 if lo else 2e-5)
-    dx, dw, db = torch.autograd.grad(y, [x, w, b], dev(g[f'{tag}.dy'], dtype).contiguous(memory_format=torch.channels_last))
+    dy = dev(g[f'{tag}.dy'], dtype).contiguous(memory_format=torch.channels_last)
+    dx, dw, db = torch.autograd.grad(y, [x, w, b], dy)
     if lo:
         assert rel_err(dx, T(g[f'{tag}.dx'])) < 2e-2 and rel_err(dw.reshape(-1), T(g[f'{tag}.dw'])) < 2e-2
+        # and per element against float64 on the bf16-rounded inputs the kernels see: one bf16 rounding of y and dx
+        # (tests/test_gpu_conv_edges.py::_check_bf16), fp32-sum grade d gamma / d beta
+        xd = x.detach().double().cpu().requires_grad_(True)
+        wd, bd = w.detach().double().cpu().requires_grad_(True), b.detach().double().cpu().requires_grad_(True)
+        gn = O.group_norm(xd, wd, bd, 32, 1e-6)
+        yd = F.silu(gn)
+        rdx, rdw, rdb = torch.autograd.grad(yd, [xd, wd, bd], dy.double().cpu())
+        gn2 = ops.group_norm_silu(x.detach(), w.detach(), b.detach(), 32, 1e-6, False)
+        for got, want in ((gn2, gn), (y, yd), (dx, rdx)):
+            got, want = got.detach().double().cpu(), want.detach()
+            worst = float(((got - want).abs() / (2.0 ** -8 * (want.abs() + want.abs().mean()))).max())
+            assert worst < 1.0, worst
+        assert rel_err(dw, rdw) < 1e-5 and rel_err(db, rdb) < 1e-5
     else:
         close(dx, g[f'{tag}.dx'], rtol=1e-3, atol=2e-5)
         close(dw.reshape(-1), g[f'{tag}.dw'], rtol=1e-4, atol=2e-5)

@@ -382,13 +382,16 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
     float csum[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) csum[i] = 0.0f;
-    __shared__ float gk[256][2];                            // deterministic mode: (k1, k2) per group, summed once per block
+    // deterministic mode: (k1, k2) per group, summed once per block -- [groups][2] in dynamic LDS (the host sizes it: groups
+    // is any divisor of c, up to 2048)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* gk = reinterpret_cast<float*>(smem);
     if (gpart) {                                            // the reduce blocks' partials, in block order
         for (int g = threadIdx.x; g < groups; g += 256) {
             double r1 = 0.0, r2 = 0.0;
             const double* q = gpart + ((int64_t)n * groups + g) * nblk * 2;
             for (int k = 0; k < nblk; ++k) { r1 += q[2 * k]; r2 += q[2 * k + 1]; }
-            gk[g][0] = (float)(r1 / m); gk[g][1] = (float)(r2 / (m - 1.0));
+            gk[2 * g] = (float)(r1 / m); gk[2 * g + 1] = (float)(r2 / (m - 1.0));
         }
         __syncthreads();
     }
@@ -398,7 +401,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
         mean[i] = stats[((int64_t)n * groups + g) * 2]; rstd[i] = stats[((int64_t)n * groups + g) * 2 + 1];
         wv[i] = w[ch]; bv[i] = b[ch];
         if (gpart) {
-            k1[i] = gk[g][0]; k2[i] = gk[g][1];
+            k1[i] = gk[2 * g]; k2[i] = gk[2 * g + 1];
         } else {
             k1[i] = (float)(red[((int64_t)n * groups + g) * 2] / m);
             k2[i] = (float)(red[((int64_t)n * groups + g) * 2 + 1] / (m - 1.0));
@@ -470,6 +473,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
     }
     if (dx_colsum) {
         // the block's rows of a slot are added through LDS ([prow][channel], reusing nothing else), one atomic per channel
+        // (prow < 256 / vpp and c = vpp * V with vpp dividing 256 -- check_gn -- so the rows * c entries are exactly 256 * V <= 256 * 8)
         __shared__ float cs_part[256 * 8];
 #pragma unroll
         for (int i = 0; i < V; ++i) cs_part[prow * c + slot * V + i] = csum[i];      // vpp * V = c columns, 256 / vpp rows: 256 * V floats
@@ -498,6 +502,8 @@ __global__ __launch_bounds__(256) void gn_small_fwd_kernel(const T* __restrict__
     __shared__ double sh[2][32];                                 // per-channel sums of the slice
     __shared__ double shw[4][2][32];                             // ... per wave: added in wave order (no atomics: deterministic)
     __shared__ float gstat[32][2];                               // (mean, rstd) per channel of the slice
+    // (every index into these is a channel of the 32-channel slice, SLOTS * V = 32; the slice holds whole groups because
+    // gn_small_ppt admits only c % 32 == 0 and 32 % (c / groups) == 0 -- the same guard covers the backward below)
     const int slot = threadIdx.x % SLOTS, prow = threadIdx.x / SLOTS;
     const int n = blockIdx.y, ch0 = blockIdx.x * 32, cpg = c / groups;
     const int64_t off = (int64_t)n * HW * c + ch0 + slot * V;
@@ -998,7 +1004,8 @@ static int gn_backward_impl(int dtype, const void* x, const float* stats, const 
         cpart = reinterpret_cast<float*>(reinterpret_cast<char*>(det.ws) + gbytes);
     }
     const int acc = (accumulate || add) ? 1 : 0;
-#define VQK_GN_BWD_A(T, S, N, A) hipLaunchKernelGGL((gn_bwd_apply_kernel<T, N, S, A>), grid, dim3(256), 0, st, (const T*)x, stats, w, b, (const T*)dy, (T*)dx, (const T*)add, red, hw, c, groups, silu, acc, ppb, add_w, add_scale, (const double*)gpart, nblk, dx_colsum)
+    const size_t alds = gpart ? (size_t)groups * 2 * sizeof(float) : 0;      // gn_bwd_apply_kernel's per-group factors
+#define VQK_GN_BWD_A(T, S, N, A) hipLaunchKernelGGL((gn_bwd_apply_kernel<T, N, S, A>), grid, dim3(256), alds, st, (const T*)x, stats, w, b, (const T*)dy, (T*)dx, (const T*)add, red, hw, c, groups, silu, acc, ppb, add_w, add_scale, (const double*)gpart, nblk, dx_colsum)
 #define VQK_GN_BWD_N(T, S, N) do { if (!acc) VQK_GN_BWD_A(T, S, N, 0); else if (add_w) VQK_GN_BWD_A(T, S, N, 2); else VQK_GN_BWD_A(T, S, N, 1); } while (0)
 #define VQK_GN_BWD_S(T, S) do { \
         hipLaunchKernelGGL((gn_bwd_reduce_kernel<T, S>), rgrid, dim3(256), lds, st, (const T*)x, stats, w, b, (const T*)dy, dw, db, red, hw, c, groups, silu, rppb, gpart, cpart); \
