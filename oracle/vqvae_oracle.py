@@ -356,6 +356,77 @@ def upfirdn2d(x, f, up=(1, 1), down=(1, 1), pad=(0, 0, 0, 0), flip_filter: bool 
     return y[:, :, ::downy, ::downx]
 
 
+# --------------------------------------------------------------------------------------
+# StyleGAN2 'resnet' discriminator  (stylegan2_discriminator/discriminator.py), built from the twins above
+# --------------------------------------------------------------------------------------
+def mbstd(x, group_size=4, eps: float = 1e-8):
+    """discriminator.py:277-293 with one feature: G = min(group_size, N) (N when None); sample b = g * (N / G) + m belongs
+    to group column m; per column, the biased variance over its G samples, sqrt(var + eps), averaged over c, h, w, and
+    appended as one channel to every sample of the column."""
+    n, c, h, w = x.shape
+    g = n if group_size is None else min(group_size, n)
+    xs = x.reshape(g, n // g, c, h, w)
+    var = (xs - xs.mean(0, keepdim=True)).pow(2).mean(0)
+    stat = (var + eps).sqrt().mean((1, 2, 3))                   # [N / G]
+    col = stat.repeat(g).reshape(n, 1, 1, 1).expand(n, 1, h, w)
+    return torch.cat([x, col], 1)
+
+
+def disc_conv(x, p: P, pre: str, act: str = 'lrelu', down: int = 1, gain: float = 1.0):
+    """Conv2dLayer.forward (discriminator.py:164-173) with conv2d_resample.py:100-122 for up = 1: weight gain
+    1/sqrt(fan_in); down 2 pads by the filter's reach, then a 1x1 kernel blurs + decimates before the conv and a 3x3
+    kernel blurs before a stride-2 conv without padding; bias, activation and gain act_gain * gain (bias_act)."""
+    wt = p[pre + 'weight']
+    k = wt.shape[-1]
+    wt = wt * (1.0 / math.sqrt(wt[0].numel()))
+    pad = k // 2
+    if down == 1:
+        x = F.conv2d(x, wt, padding=pad)
+    else:
+        f = p[pre + 'resample_filter'].to(x.dtype)
+        p0, p1 = pad + (f.shape[0] - down + 1) // 2, pad + (f.shape[0] - down) // 2
+        if k == 1:
+            x = F.conv2d(upfirdn2d(x, f, down=(down, down), pad=(p0, p1, p0, p1)), wt)
+        else:
+            x = F.conv2d(upfirdn2d(x, f, pad=(p0, p1, p0, p1)), wt, stride=down)
+    act_gain = math.sqrt(2.0) if act == 'lrelu' else 1.0
+    return bias_act(x, p.get(pre + 'bias'), 1, act, 0.2, act_gain * gain)
+
+
+def disc_fc(x, p: P, pre: str, act: str = 'linear'):
+    """FullyConnectedLayer.forward (discriminator.py:108-121): weight gain 1/sqrt(in_features), bias gain 1."""
+    wt = p[pre + 'weight'] * (1.0 / math.sqrt(p[pre + 'weight'].shape[1]))
+    return bias_act(x.matmul(wt.t()), p[pre + 'bias'], 1, act, 0.2, math.sqrt(2.0) if act == 'lrelu' else 1.0)
+
+
+def discriminator_forward(img, p: P, mbstd_group: int = 4):
+    """Discriminator.forward (discriminator.py:404-412) for architecture='resnet', no conditioning: per block
+    (DiscriminatorBlock.forward, :237-265) fromrgb on the first one, then skip(x, sqrt(1/2)) + conv1(conv0(x), sqrt(1/2));
+    then the epilogue (:328-354): minibatch stddev, 3x3 conv, fc over the flattened (c, h, w) map, linear out.
+    ``p`` holds the Discriminator's state_dict keys (resample_filter buffers included)."""
+    blocks = sorted({int(k.split('.')[0][1:]) for k in p if k.split('.')[0] != 'b4' and k.startswith('b')}, reverse=True)
+    x = None
+    for res in blocks:
+        pre = f'b{res}.'
+        if x is None:
+            x = disc_conv(img, p, pre + 'fromrgb.')
+        y = disc_conv(x, p, pre + 'skip.', act='linear', down=2, gain=math.sqrt(0.5))
+        x = disc_conv(disc_conv(x, p, pre + 'conv0.'), p, pre + 'conv1.', down=2, gain=math.sqrt(0.5))
+        x = y + x
+    x = disc_conv(mbstd(x, mbstd_group), p, 'b4.conv.')
+    x = disc_fc(x.flatten(1), p, 'b4.fc.', 'lrelu')
+    return disc_fc(x, p, 'b4.out.')
+
+
+def r1_penalty(img, p: P, weight: float = 10.0, mbstd_group: int = 4):
+    """loss.py:98-112: weight * mean over samples of |d sum(logits) / d img|^2, differentiable in ``p`` (create_graph);
+    returns (r1, logits, image gradient)"""
+    img = img.detach().requires_grad_(True)
+    logits = discriminator_forward(img, p, mbstd_group)
+    gimg, = torch.autograd.grad(logits.sum(), img, create_graph=True)
+    return weight * gimg.pow(2).reshape(gimg.shape[0], -1).sum(1).mean(), logits, gimg
+
+
 def augment_crop_flip(images, box, flip):
     """Training augmentation of base_autoencoder.py:20-22,44-48 as a pure function of the draws: per-sample crop
     box = (x0, y0, w, h) resampled to the full size with corner-aligned bilinear interpolation (kornia's crop warp),

@@ -245,3 +245,45 @@ def test_augment_restatement_identity_and_flip():
     out = O.augment_crop_flip(x, box, torch.tensor([0, 1]))
     close(out[0], (x[0] - 0.5) / 0.5, rtol=1e-6, atol=1e-6)
     close(out[1], ((x[1] - 0.5) / 0.5).flip(-1), rtol=1e-6, atol=1e-6)
+
+
+def test_mbstd_restatement_groups():
+    """oracle.mbstd against an explicit loop: sample g * (N / G) + m is in group column m (the reshape of
+    discriminator.py:283), the statistic is the mean over c, h, w of the biased group standard deviation (eps 1e-8 inside
+    the root), G = min(group, N), and None means the whole batch"""
+    gen = torch.Generator().manual_seed(4)
+    for n, group, gsz in ((8, 4, 4), (6, 2, 2), (2, 4, 2), (3, None, 3), (4, 1, 1)):
+        x = torch.randn(n, 5, 3, 2, generator=gen, dtype=torch.float64)
+        y = O.mbstd(x, group)
+        assert y.shape == (n, 6, 3, 2) and torch.equal(y[:, :5], x)
+        cols = n // gsz
+        for m in range(cols):
+            members = torch.stack([x[g * cols + m] for g in range(gsz)])
+            sd = (members.var(0, unbiased=False) + 1e-8).sqrt().mean()
+            for g in range(gsz):
+                close(y[g * cols + m, 5], np.full((3, 2), sd.item()), rtol=1e-12, atol=0)
+
+
+def test_discriminator_restatement_golden(golden):
+    """oracle.discriminator_forward / r1_penalty in float64 against the reference Discriminator(32, channel_base=1024,
+    channel_max=64) of tests/golden/gan.npz (recorded in fp32): logits, input and parameter gradients, R1 value, the image
+    gradient and d(R1)/d(theta) -- the float64 restatement the GPU tests of tests/test_gpu_gan_forms.py compare against"""
+    g = golden('gan')
+    p = {k[2:]: T(v).double().requires_grad_(not k.endswith('resample_filter')) for k, v in g.items() if k.startswith('d.')}
+    names = sorted(k for k in p if p[k].requires_grad)
+    x = T(g['d_in.x']).double().requires_grad_(True)
+    logits = O.discriminator_forward(x, p)
+    close(logits, g['d_out.logits'], rtol=1e-5, atol=1e-6)
+    grads = torch.autograd.grad((logits * T(g['d_in.r']).double()).sum(), [x] + [p[n] for n in names])
+    close(grads[0], g['d_out.dx'], rtol=1e-4, atol=1e-8)
+    for n, gr in zip(names, grads[1:]):
+        close(gr, g['d_grad.' + n], rtol=1e-4, atol=1e-6)
+    r1, logits, gimg = O.r1_penalty(T(g['d_in.x']).double(), p)
+    close(gimg, g['r1.gimg'], rtol=1e-4, atol=1e-8)
+    close(r1, g['r1.value'], rtol=1e-5)
+    grads = torch.autograd.grad(r1, [p[n] for n in names], allow_unused=True)
+    for n, gr in zip(names, grads):
+        if 'r1_grad.' + n in g:
+            close(gr, g['r1_grad.' + n], rtol=1e-4, atol=1e-8)
+        else:                                                  # the reference's autograd returned None: not on the R1 path
+            assert gr is None or not gr.any(), n
