@@ -600,6 +600,28 @@ int vqk_l1l2_backward(int dtype, const void* recon, const float* target, int64_t
 int vqk_gan_loss(const float* logits_real, const float* logits_fake, int n, int mode, int which, float* loss,
                  float* dreal, float* dfake, const float* gscale_dev, void* stream);
 
+/* ---------------------------------------------------------------- FID Inception-v3 (csrc/fid.hip, fid.py) ----------
+ * fp32 storage, NHWC, products exact fp32 (v_mfma_f32_32x32x2_f32).  VQK_ERR_SHAPE for unsupported parameters, nothing
+ * launched.
+ * preprocess: x = a [n][3][h][w] view with element strides (sn, sc, sh, sw); y[n][299][299][4] = (resize(q) - 128) / 128,
+ *   q = trunc(clamp(x, 0, 1) * 255.999f), resize = TF1 bilinear (src = dst * in / 299, no half-pixel offset); channel 3 = 0. */
+int vqk_fid_preprocess(const float* x, int n, int h, int w, int64_t sn, int64_t sc, int64_t sh, int64_t sw, float* y,
+                       void* stream);
+/* y[pix][c_off + co] = relu(conv(x, w)[pix][co] + bias[co]) for co < cout, pixel stride c_total (a slice of a channel
+ * concat; nothing outside the slice is written).  x[n][h][wd][cin], w[cout][kh][kw][cin] (KRSC), cin % 4 == 0,
+ * 1 <= kh, kw <= 7, stride 1 or 2, 0 <= ph < kh, 0 <= pw < kw, oh / ow = the conv's output size. */
+int vqk_fid_conv(const float* x, const float* w, const float* bias, float* y, int n, int h, int wd, int cin, int cout, int kh,
+                 int kw, int stride, int ph, int pw, int oh, int ow, int c_total, int c_off, void* stream);
+/* 3 x 3 pool of x[n][h][w][c] into channels [c_off, c_off + c) of y (pixel stride c_total); mode 0 max (padding = -inf),
+ * mode 1 average over the in-bounds taps (count_include_pad=False); stride 1 or 2, pad 0 or 1; c, c_off, c_total % 4 == 0. */
+int vqk_fid_pool(const float* x, float* y, int n, int h, int w, int c, int mode, int stride, int pad, int oh, int ow, int c_total,
+                 int c_off, void* stream);
+/* y[n][c] = mean over the hw pixels of x[n][hw][c] */
+int vqk_fid_mean(const float* x, float* y, int n, int hw, int c, void* stream);
+/* sum[d] += sum_r f[r][:], gram[d][d] += f^T f in fp64 from f[n][d] fp32; one thread per output element, rows in order: bit-
+ * reproducible, and several calls equal one call on the concatenated rows. */
+int vqk_fid_stats(const float* f, int n, int d, double* sum, double* gram, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

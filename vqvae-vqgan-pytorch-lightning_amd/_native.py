@@ -129,6 +129,11 @@ _PROTOS = {
     'vqk_gan_loss': [P, P, I, I, I, P, P, P, P, P],
     'vqk_bias_act': [P, P, P, P, P, P, L, L, I, I, I, F, F, F, P],
     'vqk_upfirdn2d': [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, F, I, I, P],
+    'vqk_fid_preprocess': [P, I, I, I, L, L, L, L, P, P],
+    'vqk_fid_conv': [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
+    'vqk_fid_pool': [P, P, I, I, I, I, I, I, I, I, I, I, I, P],
+    'vqk_fid_mean': [P, P, I, I, I, P],
+    'vqk_fid_stats': [P, I, I, P, P, P],
 }
 _SPECIAL = {'vqk_set_tuning': (I, [c_char_p, I]), 'vqk_reset_tuning': (I, []), 'vqk_tuning_count': (I, []),
             'vqk_tuning_name': (c_char_p, [I]),

@@ -2,7 +2,8 @@
 torchmetrics defines them (MeanSquaredError, PeakSignalNoiseRatio(data_range=None), StructuralSimilarityIndexMeasure()
 with its defaults: Gaussian 11x11 window, sigma 1.5, k1 = 0.01, k2 = 0.03, data_range from the batch).  torchmetrics is
 not part of the reference tree, so its published algorithm is restated (oracle/vqvae_oracle.py::metric_*) -- parity
-unpinned.  rFID needs the pretrained Inception network (no weights offline) and is not computed.
+unpinned.  rFID (the 2048-feature Frechet Inception distance) is computed when a ``fid.FrechetInceptionDistance`` is given:
+real = the targets, fake = the predictions, as the reference's test loop feeds it.
 
 State lives on the device and ``update`` issues two HIP kernels (``vqk_pair_stats``, ``vqk_ssim_sum``) with no host
 synchronisation; ``compute`` reads the totals once."""
@@ -24,8 +25,9 @@ def gaussian_window(kernel_size: int = 11, sigma: float = 1.5) -> torch.Tensor:
 
 
 class ReconstructionMetrics:
-    def __init__(self, device, sigma: float = 1.5, k1: float = 0.01, k2: float = 0.03):
+    def __init__(self, device, sigma: float = 1.5, k1: float = 0.01, k2: float = 0.03, fid=None):
         self.device = torch.device(device)
+        self.fid = fid                                              # fid.FrechetInceptionDistance or None (no rfid)
         if self.device.type != 'cuda':
             raise RuntimeError('vqk: the test-loop metrics run on the GPU only (HIP kernels, no CPU fallback)')
         self.ksize = int(3.5 * sigma + 0.5) * 2 + 1                 # torchmetrics: 11 for sigma = 1.5
@@ -59,10 +61,16 @@ class ReconstructionMetrics:
         self.total[2] = torch.maximum(self.total[2], batch[2])
         self.n_elems += p.numel()
         self.n_images += b
+        if self.fid is not None:                                    # the un-copied views: the FID input transform reads strides
+            self.fid.update(target.detach().float(), True)
+            self.fid.update(preds.detach().float(), False)
 
     def compute(self) -> dict:
         sse, tmin, tmax = (float(v) for v in self.total[:3].tolist())
         mse = sse / max(self.n_elems, 1)
         data_range = tmax - tmin
         psnr = 10.0 * math.log10(data_range * data_range / mse) if mse > 0 and data_range > 0 else float('inf')
-        return dict(mse=mse, psnr=psnr, ssim=float(self.ssim_sum) / max(self.n_images, 1))
+        out = dict(mse=mse, psnr=psnr, ssim=float(self.ssim_sum) / max(self.n_images, 1))
+        if self.fid is not None:
+            out['rfid'] = self.fid.compute()
+        return out

@@ -86,6 +86,10 @@ class VQVAE(BaseVQVAE, _LightningBase):
         self.split_encoder = os.environ.get('VQK_SPLIT_ENCODER', '1') != '0'     # ... and behind the encoder's high-resolution head
         self._backward_cut = self._backward_terms = self._encoder_cut = None
         self.kl_warmup_epochs = self.temp_decay_epochs = self.temp_final = None
+        # rFID of the test loop: the Inception weights (a path or a state dict in the published naming, see fid.py); None = no
+        # rFID.  A plain attribute, not a constructor argument: the reference's signature stays as it is.
+        self.fid_weights = None
+        self._fid = None                       # (fid_weights, device, FrechetInceptionDistance): NOT a submodule
 
         qt, qp = q_conf['type'], q_conf['params']
         if qt == 'standard':
@@ -342,13 +346,23 @@ class VQVAE(BaseVQVAE, _LightningBase):
     # ------------------------------------------------------------------ test loop (model.py:491-553)
     def on_test_epoch_start(self):
         from .metrics import ReconstructionMetrics
-        self.test_metrics = ReconstructionMetrics(next(self.parameters()).device)
+        device = next(self.parameters()).device
+        fid = None
+        if self.fid_weights is not None:
+            from .fid import FrechetInceptionDistance
+            same = self._fid is not None and self._fid[1] == device and (
+                self._fid[0] is self.fid_weights or (isinstance(self.fid_weights, (str, os.PathLike)) and self._fid[0] == self.fid_weights))
+            if not same:
+                self._fid = (self.fid_weights, device, FrechetInceptionDistance(self.fid_weights, device))
+            fid = self._fid[2]
+            fid.reset()
+        self.test_metrics = ReconstructionMetrics(device, fid=fid)
         self.test_usage_count = None
 
     @torch.no_grad()
     def test_step(self, images: Any, _):
         """reconstructions in [0, 1] against the (clamped) inputs: MSE / PSNR / SSIM and the code histogram, all on the
-        device.  rFID (model.py:535-541) needs the pretrained Inception network and is not computed offline."""
+        device; with ``fid_weights`` set, the images (real) and the reconstructions (fake) also feed rFID (model.py:535-541)."""
         images = images[0] if isinstance(images, (tuple, list)) else images
         recon, _, used_indices = self(self.preprocess_batch(images))
         recon = self.preprocess_visualization(recon.float())[:, :3]
@@ -359,8 +373,9 @@ class VQVAE(BaseVQVAE, _LightningBase):
 
     def on_test_epoch_end(self):
         out = self.test_metrics.compute()
-        for name in ('mse', 'ssim', 'psnr'):
-            self.log(name, out[name], sync_dist=True)
+        for name in ('mse', 'ssim', 'psnr', 'rfid'):
+            if name in out:
+                self.log(name, out[name], sync_dist=True)
         _, perplexity, cb_usage = self.quantizer.get_codebook_usage(self.test_usage_count.float())
         self.log('used_codebook', cb_usage, sync_dist=True)
         self.log('perplexity', perplexity, sync_dist=True)

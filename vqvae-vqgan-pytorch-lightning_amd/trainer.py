@@ -463,6 +463,16 @@ class MiniTrainer:
         self.global_step = ckpt.get('global_step', 0)
         return ckpt
 
+    @torch.no_grad()
+    def test(self, model, batches: Iterable) -> dict:
+        """``Trainer.test`` of the reference's evaluate.py: eval mode, ``on_test_epoch_start``, ``test_step`` per batch; returns
+        the dict of ``on_test_epoch_end`` (mse, psnr, ssim, used_codebook, perplexity, and rfid when ``model.fid_weights`` is set)"""
+        model.eval()
+        model.on_test_epoch_start()
+        for i, batch in enumerate(batches):
+            model.test_step(batch, i)
+        return model.on_test_epoch_end()
+
     def fit(self, model, batches: Iterable):
         batches = list(batches)
         if self.num_training_batches is None:
