@@ -622,6 +622,37 @@ int vqk_fid_mean(const float* x, float* y, int n, int hw, int c, void* stream);
  * reproducible, and several calls equal one call on the concatenated rows. */
 int vqk_fid_stats(const float* f, int n, int d, double* sum, double* gram, void* stream);
 
+/* ---------------------------------------------------------------- dataset ingest (csrc/ingest.hip, data.py) --------
+ * The device half of the reference's standard loader (data/datasets.py:16,26: PIL decode -> ToTensor() -> Resize((S,S),
+ * antialias=True)): host threads decode to uint8, ONE launch turns a ragged batch into the tensor the steps take.
+ * pixels: one packed device buffer (4-byte aligned, pixels_bytes long) of uint8 HWC RGB images of any sizes; image i of the
+ * OUTPUT is described by desc[i] (several entries may name the same source).  out: fp32 NCHW, out[i * out_batch_stride +
+ * c * out_h * out_w + y * out_w + x] in [0,1], out_batch_stride >= 3 * out_h * out_w elements (a slice of a larger tensor is
+ * written in place; nothing outside the n images' 3 * out_h * out_w elements is touched).
+ * Arithmetic (ATen's antialiased bilinear, the kernel torchvision's Resize(antialias=True) runs on tensors), per axis for a box
+ * of length L resampled to S outputs:
+ *     scale = L / S;  support = max(scale, 1);  c = scale * (i + 0.5)
+ *     lo = max(0, (int)(c - support + 0.5));  hi = min(L, (int)(c + support + 0.5))
+ *     w_j = max(0, 1 - |(j - c + 0.5) / support|), j in [lo, hi), normalised to sum 1
+ * applied separably (columns, then rows) to float(u8) / 255.0f; no rounding to uint8 in between; flip != 0 mirrors the output
+ * columns.  Coordinates and weights are computed in fp64 and rounded to fp32 per tap, sums are fp32 in ascending source order:
+ * bit-reproducible, and at scale == 1 bit-identical to float(u8) / 255.0f.
+ * desc_host and desc_dev are the SAME table in host and in device memory (8-byte aligned): the host copy is checked before the
+ * launch, the kernel reads the device copy.  Supported: n >= 1, source sides 1..16384, out_h / out_w 1..4096, any ratio up or
+ * down, stride >= 3 * w, the box inside the image, every image inside [0, pixels_bytes); otherwise VQK_ERR_SHAPE and nothing
+ * is launched.  Allocates nothing, never synchronises (graph-capturable). */
+#define VQK_INGEST_MAX_SIDE 16384
+#define VQK_INGEST_MAX_OUT 4096
+typedef struct vqk_ingest_desc {
+    int64_t offset;             /* byte offset of the image's first pixel in `pixels` */
+    int32_t h, w;               /* source size in pixels */
+    int32_t stride;             /* bytes between source rows (>= 3 * w) */
+    int32_t x0, y0, bw, bh;     /* crop box in whole source pixels, inside the image */
+    int32_t flip;               /* != 0: mirror the output columns */
+} vqk_ingest_desc;              /* 40 bytes */
+int vqk_ingest_u8(const void* pixels, int64_t pixels_bytes, const vqk_ingest_desc* desc_host, const vqk_ingest_desc* desc_dev,
+                  int n, int out_h, int out_w, int64_t out_batch_stride, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,7 @@ _PROTOS = {
     'vqk_fid_pool': [P, P, I, I, I, I, I, I, I, I, I, I, I, P],
     'vqk_fid_mean': [P, P, I, I, I, P],
     'vqk_fid_stats': [P, I, I, P, P, P],
+    'vqk_ingest_u8': [P, L, P, P, I, I, I, L, P, P],
 }
 _SPECIAL = {'vqk_set_tuning': (I, [c_char_p, I]), 'vqk_reset_tuning': (I, []), 'vqk_tuning_count': (I, []),
             'vqk_tuning_name': (c_char_p, [I]),

@@ -7,9 +7,9 @@
 The checkpoint is loaded as in reference evaluate.py:49 (``load_from_checkpoint(..., l_conf=None, t_conf=None,
 init_cb=False, load_loss=False)``) and the test loop of vqvae/model.py:491-553 runs over the dataset: MSE, PSNR, SSIM, codebook
 usage and perplexity, plus rFID when ``--fid_weights`` names the Inception weights (fid.py).  One JSON line of metrics is
-printed.  The dataset is the tensor-file format train.py reads (``.pt`` / ``.npy`` of images [M,3,S,S] in [0,1]); the last
-batch may be short.  ``--workers`` is accepted for the reference's command line and unused (the data is one tensor); the ffcv
-loader is out of scope, as in train.py.
+printed.  The dataset is a DIRECTORY with the reference's layout -- its ``test/`` sub-folder is read in sorted file order
+through ``data.get_datamodule`` with ``--workers`` decode threads -- or the tensor-file format train.py reads (``.pt`` / ``.npy``
+of images [M,3,S,S] in [0,1]); the last batch may be short.  The ffcv loader is out of scope, as in train.py.
 """
 from __future__ import annotations
 
@@ -28,12 +28,13 @@ PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--params_file', type=str, required=True, help='yaml file with model params (example_confs/*.yaml)')
-    p.add_argument('--dataloader', type=str, choices=['standard'], default='standard', help='accepted; the data is one tensor file')
-    p.add_argument('--dataset_path', type=str, required=True, help='.pt / .npy tensor of test images [M,3,S,S] in [0,1]')
+    p.add_argument('--dataloader', type=str, choices=['standard'], default='standard', help="'standard' = image folders (data.py)")
+    p.add_argument('--dataset_path', type=str, required=True, help='directory holding a test/ image folder, or a .pt / .npy tensor of test images [M,3,S,S] in [0,1]')
     p.add_argument('--batch_size', type=int, required=True, help='evaluation is on one GPU')
     p.add_argument('--seed', type=int, required=True)
     p.add_argument('--loading_path', type=str, required=True, help='checkpoint to evaluate')
-    p.add_argument('--workers', type=int, default=1, help='accepted and unused')
+    p.add_argument('--workers', type=int, default=1, help='decode threads of the folder loader (at most 16 are used)')
+    p.add_argument('--resize', choices=['squash', 'center_crop'], default='squash', help='folder loader geometry (train.py --resize)')
     p.add_argument('--fid_weights', type=str, default=None,
                    help='Inception weights for rFID (pt_inception-2015-12-05-6726825d.pth); omitted: no rfid')
     p.add_argument('--dtype', choices=['bf16', 'f32', 'bf16x3'], default='bf16',
@@ -68,12 +69,19 @@ def main(argv=None) -> dict:
                                                  t_conf=None, init_cb=False, load_loss=False, compute_dtype=dtype)
     model = model.to(device)
     model.fid_weights = args.fid_weights
-    data = load_images(args.dataset_path)
     b = args.batch_size
-    batches = [data[i:i + b].to(device) for i in range(0, data.shape[0], b)]
-    if not batches:
+    if os.path.isdir(args.dataset_path):
+        batches = importlib.import_module(PKG + '.data').get_datamodule(
+            args.dataset_path, int(conf['image_size']), b, args.workers, args.seed, mode='test', device=device,
+            resize=args.resize).test
+    else:
+        data = load_images(args.dataset_path)
+        batches = [data[i:i + b].to(device) for i in range(0, data.shape[0], b)]
+    if not len(batches):
         raise SystemExit(f'evaluate.py: {args.dataset_path} holds no images')
     out = trainer_mod.MiniTrainer().test(model, batches)
+    if hasattr(batches, 'close'):
+        batches.close()
     out = {k: float(v) for k, v in out.items()}
     print(json.dumps(out), flush=True)
     return out

@@ -11,6 +11,7 @@ import os
 import threading
 import weakref
 
+import numpy as _np
 import torch
 
 from . import _native
@@ -1372,6 +1373,115 @@ def raw_augment_preprocess(images, box, flip, dtype, want_target: bool):
                                               _p(tgt), n, h, w, cp, _stream())
     _native.check(st, 'augment_preprocess')
     return xp, (xp if (want_target and tgt is None) else tgt)
+
+
+# ------------------------------------------------------------------------------------------------------
+# dataset ingest (csrc/ingest.hip): packed uint8 HWC images of any sizes -> fp32 NCHW [N,3,S_h,S_w] in [0,1]
+# ------------------------------------------------------------------------------------------------------
+INGEST_DESC = _np.dtype([('offset', '<i8'), ('h', '<i4'), ('w', '<i4'), ('stride', '<i4'), ('x0', '<i4'), ('y0', '<i4'),
+                         ('bw', '<i4'), ('bh', '<i4'), ('flip', '<i4')])       # vqk_ingest_desc (include/vqk.h), 40 bytes
+INGEST_MAX_SIDE, INGEST_MAX_OUT = 16384, 4096
+
+
+def random_crop_boxes(sizes, scale=(0.7, 1.0), generator=None):
+    """``random_crop_params`` for images of DIFFERENT sizes, drawn on the host: RandomResizedCrop(scale, ratio 1) taken from the
+    source resolution (one resampling instead of two) + RandomHorizontalFlip(0.5).  Area fraction ~ U(scale) of the centred
+    square of side min(h, w), whole pixels, top-left corner uniform over the valid range.  Returns (boxes [(x0, y0, bw, bh)],
+    flips [0 / 1]) for ``ingest_desc``."""
+    r = torch.rand(len(sizes), 4, generator=generator, dtype=torch.float64).tolist()
+    boxes, flips = [], []
+    for (h, w), (ra, rx, ry, rf) in zip(sizes, r):
+        m = min(h, w)
+        side = min(max(int((scale[0] + (scale[1] - scale[0]) * ra) ** 0.5 * m + 0.5), 1), m)
+        boxes.append((min(int(rx * (w - side + 1)), w - side), min(int(ry * (h - side + 1)), h - side), side, side))
+        flips.append(int(rf < 0.5))
+    return boxes, flips
+
+
+def ingest_desc(sizes, mode='squash', boxes=None, flips=None, offsets=None, strides=None):
+    """Descriptor table (numpy, dtype ``INGEST_DESC``) of a batch of uint8 HWC RGB images of ``sizes`` [(h, w)].
+    mode 'squash': the whole image (the reference's standard loader, data/datasets.py:16); 'center_crop': the centred square
+    of side min(h, w) (the geometry of the reference's ffcv pipeline, vqvae/common_utils.py:64; its cv2 area filter is not
+    reproduced); 'boxes': ``boxes`` [(x0, y0, bw, bh)] in whole source pixels.  ``flips``: per image, default none.
+    ``offsets`` / ``strides``: where each image starts in the packed buffer and its row pitch in bytes; default: tightly packed
+    rows (3 * w), each image starting at the next multiple of 16 bytes -- the layout ``pack_images`` writes."""
+    n = len(sizes)
+    d = _np.zeros(n, dtype=INGEST_DESC)
+    at = 0
+    for i, (h, w) in enumerate(sizes):
+        h, w = int(h), int(w)
+        if not (1 <= h <= INGEST_MAX_SIDE and 1 <= w <= INGEST_MAX_SIDE):
+            raise ValueError(f'vqk: image {i} is {h} x {w}; sides 1..{INGEST_MAX_SIDE} are served')
+        stride = 3 * w if strides is None else int(strides[i])
+        if stride < 3 * w:
+            raise ValueError(f'vqk: image {i}: row stride {stride} < 3 * {w}')
+        if mode == 'squash':
+            box = (0, 0, w, h)
+        elif mode == 'center_crop':
+            m = min(h, w)
+            box = ((w - m) // 2, (h - m) // 2, m, m)
+        elif mode == 'boxes':
+            box = tuple(int(v) for v in boxes[i])
+        else:
+            raise ValueError("vqk: ingest mode is 'squash', 'center_crop' or 'boxes'")
+        x0, y0, bw, bh = box
+        if x0 < 0 or y0 < 0 or bw < 1 or bh < 1 or x0 + bw > w or y0 + bh > h:
+            raise ValueError(f'vqk: image {i}: box {box} leaves the {h} x {w} image')
+        off = at if offsets is None else int(offsets[i])
+        d[i] = (off, h, w, stride, x0, y0, bw, bh, int(bool(flips[i])) if flips is not None else 0)
+        at = (off + (h - 1) * stride + 3 * w + 15) // 16 * 16 if offsets is None else at
+    return d
+
+
+def ingest_packed_bytes(desc) -> int:
+    """bytes a packed buffer needs to hold every image of ``desc``"""
+    return int(max(int(e['offset']) + (int(e['h']) - 1) * int(e['stride']) + 3 * int(e['w']) for e in desc)) if len(desc) else 0
+
+
+def pack_images(images, desc, buf) -> None:
+    """copy uint8 HWC arrays into the packed host buffer ``buf`` (1-D uint8 numpy view) at the offsets / strides of ``desc``"""
+    for img, e in zip(images, desc):
+        h, w, stride, off = int(e['h']), int(e['w']), int(e['stride']), int(e['offset'])
+        if img.shape != (h, w, 3) or img.dtype != _np.uint8:
+            raise ValueError(f'vqk: expected a uint8 image of shape {(h, w, 3)}, got {img.dtype} {img.shape}')
+        rows = _np.lib.stride_tricks.as_strided(buf[off:], shape=(h, 3 * w), strides=(stride, 1))
+        rows[...] = img.reshape(h, 3 * w)
+
+
+def ingest_u8(pixels, desc, size, out=None, desc_dev=None):
+    """ToTensor + crop + antialiased bilinear resize (+ flip) of a ragged uint8 batch in one launch (vqk_ingest_u8).
+    pixels: 1-D uint8 device tensor, the packed HWC RGB images; desc: the host table of ``ingest_desc`` (one entry per output
+    image); size: S or (S_h, S_w); out: optional fp32 [N,3,S_h,S_w] to write into -- a batch slice of a larger tensor is fine
+    (each image contiguous; nothing outside the slice is touched); desc_dev: the same table already on the device (uint8
+    [N * 40]), copied here when omitted.  Returns fp32 NCHW [N,3,S_h,S_w] in [0,1], what the steps take.  With ``out`` and
+    ``desc_dev`` given nothing is allocated and nothing synchronises."""
+    _require_gpu(pixels)
+    if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous():
+        raise RuntimeError('vqk: ingest expects one packed 1-D uint8 buffer')
+    desc = _np.ascontiguousarray(desc)
+    if desc.dtype != INGEST_DESC or desc.ndim != 1:
+        raise RuntimeError('vqk: ingest expects a descriptor table of dtype ops.INGEST_DESC (ops.ingest_desc)')
+    n = int(desc.shape[0])
+    sh, sw = (int(size), int(size)) if not isinstance(size, (tuple, list)) else (int(size[0]), int(size[1]))
+    if out is None:
+        if not (1 <= sh <= INGEST_MAX_OUT and 1 <= sw <= INGEST_MAX_OUT and n >= 1):
+            raise RuntimeError(f'vqk: ingest_u8 failed: output {n} x {sh} x {sw}; sizes 1..{INGEST_MAX_OUT}, n >= 1 are served')
+        out = torch.empty(n, 3, sh, sw, dtype=torch.float32, device=pixels.device)
+    else:
+        _require_gpu(out)
+        if out.dtype != torch.float32 or tuple(out.shape) != (n, 3, sh, sw) or not out[0].is_contiguous():
+            raise RuntimeError(f'vqk: ingest out= must be fp32 {(n, 3, sh, sw)} with contiguous images')
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(desc.view(_np.uint8)).to(pixels.device)
+    elif desc_dev.dtype != torch.uint8 or desc_dev.numel() < n * INGEST_DESC.itemsize or not desc_dev.is_cuda:
+        raise RuntimeError('vqk: ingest desc_dev must be the descriptor table as device uint8')
+    bstride = out.stride(0) if n > 1 else 3 * sh * sw
+    # (the stream handle is taken directly: _stream() would arm a 64 MiB workspace context for a loader's side stream, and this
+    # kernel uses no workspace)
+    st = _native.lib().vqk_ingest_u8(pixels.data_ptr(), pixels.numel(), desc.ctypes.data, desc_dev.data_ptr(), n, sh, sw, bstride,
+                                     out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _native.check(st, 'ingest_u8')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -10,8 +10,11 @@ WORLD_SIZE plays the role of ``num_nodes * gpus``).  Reproduced from the referen
   * :86-98  ``image_size / ae_conf / q_conf / l_conf`` pass-through and the derived ``t_conf``;
   * :101-103, :139-140  adversarial detection and the ``batch_size_per_device % 4`` guard (minibatch-stddev groups of 4);
   * :106-114  resume through ``VQVAE.load_from_checkpoint(..., strict=False, init_cb=False)``.
-Out of scope: the ffcv / folder data modules and wandb.  Batches come from ``--dataset_path`` when it is a
-``.pt`` / ``.npy`` tensor file of images [M,3,S,S] in [0,1], otherwise they are synthetic U(0,1) (the benchmark's input).
+  * :115-117, :131  ``get_datamodule(...)`` over ``--dataset_path`` and ``check_val_every_n_epoch=5``.
+Out of scope: the ffcv data module and wandb.  Batches come from ``--dataset_path``: a DIRECTORY with the reference's
+layout (``train/``, optionally ``validation/``) is read through ``data.get_datamodule`` (host threads decode, one HIP kernel
+resizes: data.py); a ``.pt`` / ``.npy`` tensor file holds images [M,3,S,S] in [0,1], resident on the device; omitted: synthetic
+U(0,1) batches (the benchmark's input).
 """
 from __future__ import annotations
 
@@ -79,8 +82,16 @@ def _deep_copy(x):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--params_file', type=str, required=True, help='yaml file with model params (example_confs/*.yaml)')
-    p.add_argument('--dataset_path', type=str, default=None, help='.pt / .npy tensor of images [M,3,S,S] in [0,1]; '
+    p.add_argument('--dataset_path', type=str, default=None, help='directory holding train/ (and validation/) image folders, or a '
+                                                                  '.pt / .npy tensor of images [M,3,S,S] in [0,1]; '
                                                                   'omitted: synthetic U(0,1) batches')
+    p.add_argument('--dataloader', type=str, choices=['standard'], default='standard',
+                   help="the reference's loader choice; 'standard' = image folders (ffcv is out of scope)")
+    p.add_argument('--workers', type=int, default=1, help='decode threads of the folder loader (at most 16 are used)')
+    p.add_argument('--resize', choices=['squash', 'center_crop'], default='squash',
+                   help="folder loader: 'squash' the whole image to image_size (the reference's standard loader) or the centred square")
+    p.add_argument('--check_val_every_n_epoch', type=int, default=5,
+                   help='folder loader with a validation/ folder: validate after every n-th epoch (reference: 5)')
     p.add_argument('--save_path', type=str, default=None, help='directory for checkpoints')
     p.add_argument('--save_every_n_epochs', type=int, default=1)
     p.add_argument('--run_name', type=str, default='run')
@@ -124,6 +135,16 @@ def parse_overrides(pairs) -> dict:
 
 
 def _batches(args, run, device, rank, world):
+    """(train batches: a list of resident tensors or a re-iterable loader with ``set_epoch``, validation loader or None)"""
+    b, s = run['batch_size_per_device'], run['image_size']
+    if args.dataset_path and os.path.isdir(args.dataset_path):
+        dm = importlib.import_module(PKG + '.data').get_datamodule(args.dataset_path, s, b, args.workers, args.seed, rank, world,
+                                                                   mode='train', device=device, resize=args.resize)
+        return dm.train, dm.validation
+    return _tensor_batches(args, run, device, rank, world), None
+
+
+def _tensor_batches(args, run, device, rank, world):
     b, s = run['batch_size_per_device'], run['image_size']
     if args.dataset_path:
         data = torch.load(args.dataset_path) if args.dataset_path.endswith('.pt') else \
@@ -166,8 +187,8 @@ def main(argv=None):
     if run['use_adversarial']:
         model.criterion.discriminator.compute_dtype = model.compute_dtype
         model.criterion.perceptual_loss.net.compute_dtype = model.compute_dtype
-    batches = _batches(args, run, device, rank, world)
-    if not batches:
+    batches, val_batches = _batches(args, run, device, rank, world)
+    if not len(batches):
         raise SystemExit(f'train.py: the dataset holds fewer than one batch per rank '
                          f'({run["batch_size_per_device"]} images x {world} ranks)')
     max_epochs = args.max_epochs or run['max_epochs']
@@ -186,7 +207,8 @@ def main(argv=None):
     graphed = False
     if not args.no_graph:
         try:
-            trainer.capture(model, batches[0], warmup=1, preserve_state=True)   # the settling step must not train
+            first = batches[0] if isinstance(batches, list) else next(iter(batches)).clone()
+            trainer.capture(model, first, warmup=1, preserve_state=True)   # the settling step must not train
             graphed = True
         except RuntimeError as exc:
             if rank == 0:
@@ -195,9 +217,15 @@ def main(argv=None):
     loss = None
     for epoch in range(start_epoch, max_epochs):
         model.current_epoch = epoch
+        if not isinstance(batches, list):
+            batches.set_epoch(epoch)
         for i, batch in enumerate(batches):
             loss = step(model, batch, i)
         model.on_train_epoch_end()
+        if val_batches is not None and len(val_batches) and (epoch + 1) % args.check_val_every_n_epoch == 0:
+            logged = trainer.validate(model, val_batches)
+            if rank == 0:
+                print(f'[epoch {epoch}] ' + ' '.join(f'{k} {v:.6f}' for k, v in sorted(logged.items())), flush=True)
         importlib.import_module(PKG + '.ops').check_kernel_health()       # a kernel that gave up on a rendezvous = untrustworthy gradients: stop
         if rank == 0:
             print(f'[epoch {epoch}] loss {float(loss):.6f}', flush=True)
@@ -205,6 +233,9 @@ def main(argv=None):
             os.makedirs(os.path.join(args.save_path, args.run_name), exist_ok=True)
             trainer.save_checkpoint(model, os.path.join(args.save_path, args.run_name, f'epoch={epoch:02d}.ckpt'))
     model.on_train_end()
+    for loader in (batches, val_batches):
+        if hasattr(loader, 'close'):
+            loader.close()
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return float(loss) if loss is not None else None

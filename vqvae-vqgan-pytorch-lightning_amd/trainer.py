@@ -473,6 +473,26 @@ class MiniTrainer:
             model.test_step(batch, i)
         return model.on_test_epoch_end()
 
+    @torch.no_grad()
+    def validate(self, model, batches: Iterable) -> dict:
+        """The validation loop Lightning runs every ``check_val_every_n_epoch`` epochs (vqvae/train.py:131): eval mode, no
+        gradients, ``validation_step`` per batch, ``on_validation_epoch_end``; the model goes back to the mode it was in.
+        Returns what the model logged as floats: 'validation/loss' (the mean over the images, Lightning's ``on_epoch=True``),
+        'val_metrics/used_codebook', 'val_metrics/perplexity'."""
+        was_training = model.training
+        model.eval()
+        total, count = None, 0
+        for i, batch in enumerate(batches):
+            loss = model.validation_step(batch, i).detach().float() * batch.shape[0]
+            total = loss if total is None else total + loss
+            count += batch.shape[0]
+        model.on_validation_epoch_end()
+        model.train(was_training)
+        out = {k: float(v) for k, v in model.logged.items() if k.startswith(('validation/', 'val_metrics/'))}
+        if count:
+            out['validation/loss'] = float(total) / count
+        return out
+
     def fit(self, model, batches: Iterable):
         batches = list(batches)
         if self.num_training_batches is None:
