@@ -653,6 +653,37 @@ typedef struct vqk_ingest_desc {
 int vqk_ingest_u8(const void* pixels, int64_t pixels_bytes, const vqk_ingest_desc* desc_host, const vqk_ingest_desc* desc_dev,
                   int n, int out_h, int out_w, int64_t out_batch_stride, float* out, void* stream);
 
+/* ---------------------------------------------------------------- image egress (csrc/egress.hip, imagelog.py) --------
+ * The counterpart of the ingest: device image tensors out as uint8 HWC RGB, laid out as torchvision's make_grid documents it
+ * (the reference's log_reconstructions, vqvae/model.py:442-456, builds its panel with make_grid(nrow=b)).  ONE launch, one pass.
+ * src: n images of h x w, fp32 (VQK_F32) or bf16 (VQK_BF16), element (i, ch, y, x) at src[i * stride_n + ch * stride_c +
+ * y * stride_y + x * stride_x] (strides in ELEMENTS): the padded NHWC reconstruction, the NHWC target and a plain NCHW batch --
+ * or a slice of one -- are read in place.  c >= 3 is the number of channels that exist at each pixel; only channels 0..2 are
+ * read (a pixel with contiguous channels, c >= 4 and 16-byte (fp32) / 8-byte (bf16) aligned pixels is fetched as one vector, the
+ * fourth element dropped).
+ * Quantisation, bit-exact in fp32, every operation rounded separately (no FMA); bf16 is widened exactly first:
+ *     VQK_RANGE_SYM  (the model's (-1,1)):  t = clip(x * 0.5f + 0.5f, 0, 1)
+ *     VQK_RANGE_UNIT ([0,1]):               t = clip(x, 0, 1)
+ *     q = (uint8) floorf(t * 255.0f + 0.5f)            -- the rule of torchvision.utils.save_image
+ * -Inf gives 0, +Inf gives 255, NaN gives 0.
+ * Layout: the canvas is (rows * (h + pad) + pad) x (cols * (w + pad) + pad) pixels, 3 bytes each, rows contiguous.  Image k goes
+ * to cell (row0 + k / cols, k % cols); a cell's top-left pixel is (pad + cell_y * (h + pad), pad + cell_x * (w + pad)).  A call
+ * writes EVERY byte of the canvas rows [row0 * (h + pad), (row0 + ceil(n / cols)) * (h + pad)) -- its images, the padding
+ * around them and the cells it leaves empty, as pad_value -- and, when its last cell row is the canvas's last, the closing pad
+ * rows too; it writes nothing else.  Calls whose cell rows tile 0..rows-1 therefore define the whole canvas: no memset.
+ * pad == 0, cols == 1, rows == n is the plain stack of n images [n][h][w][3].  The canvas pointer needs no alignment.
+ * VQK_ERR_SHAPE: n < 1, c < 3, h / w outside 1..4096, pad outside 0..4096, pad_value outside 0..255, rows / cols < 1, canvas
+ * bytes >= 2^31, cell rows outside the canvas, an unknown dtype or value range; VQK_ERR_ARG: NULL pointers; VQK_ERR_ALIGN: src
+ * not aligned to its element.  Allocates nothing, never synchronises (graph-capturable).
+ * vqk_egress_canvas_bytes: the canvas size in bytes, or -1 where vqk_egress_u8 would refuse the geometry. */
+#define VQK_EGRESS_MAX_SIDE 4096
+#define VQK_RANGE_UNIT 0
+#define VQK_RANGE_SYM 1
+int64_t vqk_egress_canvas_bytes(int h, int w, int rows, int cols, int pad);
+int vqk_egress_u8(int dtype, const void* src, int n, int c, int h, int w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                  int64_t stride_x, int value_range, uint8_t* canvas, int rows, int cols, int row0, int pad, int pad_value,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

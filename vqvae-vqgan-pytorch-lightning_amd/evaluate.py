@@ -7,7 +7,8 @@
 The checkpoint is loaded as in reference evaluate.py:49 (``load_from_checkpoint(..., l_conf=None, t_conf=None,
 init_cb=False, load_loss=False)``) and the test loop of vqvae/model.py:491-553 runs over the dataset: MSE, PSNR, SSIM, codebook
 usage and perplexity, plus rFID when ``--fid_weights`` names the Inception weights (fid.py).  One JSON line of metrics is
-printed.  The dataset is a DIRECTORY with the reference's layout -- its ``test/`` sub-folder is read in sorted file order
+printed.  ``--save_reconstructions DIR`` also writes every reconstruction as a PNG (the tensors the metrics read, through one HIP
+kernel and host encode threads: imagelog.py); the metrics are the same with and without it.  The dataset is a DIRECTORY with the reference's layout -- its ``test/`` sub-folder is read in sorted file order
 through ``data.get_datamodule`` with ``--workers`` decode threads -- or the tensor-file format train.py reads (``.pt`` / ``.npy``
 of images [M,3,S,S] in [0,1]); the last batch may be short.  The ffcv loader is out of scope, as in train.py.
 """
@@ -37,6 +38,12 @@ def parse_args(argv=None):
     p.add_argument('--resize', choices=['squash', 'center_crop'], default='squash', help='folder loader geometry (train.py --resize)')
     p.add_argument('--fid_weights', type=str, default=None,
                    help='Inception weights for rFID (pt_inception-2015-12-05-6726825d.pth); omitted: no rfid')
+    p.add_argument('--save_reconstructions', type=str, default=None, metavar='DIR',
+                   help='write every reconstruction as DIR/<source file stem>.png (folder datasets) or DIR/<index:06d>.png '
+                        '(tensor files); omitted: no images')
+    p.add_argument('--save_grid_every', type=int, default=None, metavar='N',
+                   help='with --save_reconstructions: also DIR/grids/batch=BBBBBB.png, ground truths over reconstructions, for '
+                        'every N-th batch')
     p.add_argument('--dtype', choices=['bf16', 'f32', 'bf16x3'], default='bf16',
                    help='compute mode of the autoencoder (train.py --dtype); the FID network is always fp32')
     return p.parse_args(argv)
@@ -79,7 +86,24 @@ def main(argv=None) -> dict:
         batches = [data[i:i + b].to(device) for i in range(0, data.shape[0], b)]
     if not len(batches):
         raise SystemExit(f'evaluate.py: {args.dataset_path} holds no images')
-    out = trainer_mod.MiniTrainer().test(model, batches)
+    saver = None
+    if args.save_reconstructions is not None:
+        imagelog = importlib.import_module(PKG + '.imagelog')
+        if isinstance(batches, list):
+            names = [f'{i:06d}.png' for i in range(data.shape[0])]
+            per_batch = [names[i:i + b] for i in range(0, len(names), b)]
+        else:
+            stems = imagelog.unique_stems([batches.folder.path(i) for i in range(len(batches.folder))])
+            per_batch = [[stems[i] + '.png' for i in ids] for ids in batches.epoch_batches()]
+        saver = imagelog.ReconstructionSaver(imagelog.ImageWriter(args.save_reconstructions, workers=max(args.workers, 2)),
+                                             per_batch, args.save_grid_every)
+        model.reconstruction_sink = saver
+    try:
+        out = trainer_mod.MiniTrainer().test(model, batches)
+    finally:
+        model.reconstruction_sink = None
+        if saver is not None:
+            saver.close()
     if hasattr(batches, 'close'):
         batches.close()
     out = {k: float(v) for k, v in out.items()}

@@ -90,6 +90,16 @@ class VQVAE(BaseVQVAE, _LightningBase):
         # rFID.  A plain attribute, not a constructor argument: the reference's signature stays as it is.
         self.fid_weights = None
         self._fid = None                       # (fid_weights, device, FrechetInceptionDistance): NOT a submodule
+        # image-grid logging (log_reconstructions, vqvae/model.py:442-456): the directory the PNG panels go to; None = no
+        # logging.  Plain attributes like fid_weights.  Set it BEFORE MiniTrainer.capture: the capture keeps the step's target
+        # and reconstruction as static tensors only while a directory is set.
+        self.image_log_dir = None
+        self.image_log_workers = 2
+        self.defer_image_logging = False       # MiniTrainer.capture: the settling steps and the captured region never log ...
+        self.keep_recon_pair = False           # ... but the captured step leaves (target, reconstruction) in _recon_pair
+        self._recon_pair = None
+        self._image_writer = None              # (image_log_dir, imagelog.ImageWriter)
+        self.reconstruction_sink = None        # test loop: callable(batch_index, images, reconstructions), both [0,1] (evaluate.py)
 
         qt, qp = q_conf['type'], q_conf['params']
         if qt == 'standard':
@@ -188,7 +198,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
             return ops.raw_augment_preprocess(images, box, flip, self.compute_dtype, want_target=True)
         return ops.raw_preprocess(images, self.compute_dtype, want_target=True)
 
-    def _step_losses(self, batch, training: bool):
+    def _step_losses(self, batch, training: bool, want_pair: bool = False):
         images = batch[0] if isinstance(batch, (tuple, list)) else batch
         x_pad, target = self._preprocess_train(images, training)                          # clamp, normalise, NHWC
         enc_split = self._encoder_split() if (training and self.split_backward and self.split_encoder) else None
@@ -203,6 +213,8 @@ class VQVAE(BaseVQVAE, _LightningBase):
             self._backward_cut = (quantized, dec_in)
         recon_pad = self.decoder.forward_padded(dec_in)
         l2_loss = ops.mse_loss(recon_pad, target, true_channels=3)
+        # the two rows of the logged panel, as the loss read them: padded NHWC, the model's (-1,1)
+        self._recon_pair = (target, recon_pad.detach()) if (want_pair or self.keep_recon_pair) else None
         return recon_pad, used_indices, q_loss, l2_loss
 
     def _gan_ae_half(self, batch: Any):
@@ -278,6 +290,8 @@ class VQVAE(BaseVQVAE, _LightningBase):
     def _gan_training_step(self, batch: Any, batch_index: int):
         """manual optimisation, model.py:244-264: AE step (nll + g_weight * g_loss + q_loss), then discriminator step"""
         res = self._gan_ae_half(batch)
+        if self.image_log_due(batch_index):                 # before the discriminator half releases the step's state
+            self.log_reconstructions(self._gan_state[0], self._gan_state[1], t_or_v='t')
         ae_opt, disc_opt = self.optimizers()
         ae_opt.all_reduce_grads()
         ae_opt.step()
@@ -293,7 +307,12 @@ class VQVAE(BaseVQVAE, _LightningBase):
     def training_step(self, batch: Any, batch_index: int):
         if isinstance(self.criterion, VQLPIPSWithDiscriminator):
             return self._gan_training_step(batch, batch_index)
-        _, used_indices, q_loss, l2_loss = self._step_losses(batch, training=True)
+        due = self.image_log_due(batch_index)
+        _, used_indices, q_loss, l2_loss = self._step_losses(batch, training=True, want_pair=due)
+        if due:                                             # model.py:240-242
+            self.log_reconstructions(*self._recon_pair, t_or_v='t')
+        if not self.keep_recon_pair:
+            self._recon_pair = None
         ae_loss = q_loss + l2_loss
         if self.split_backward:
             self._backward_terms = (l2_loss, q_loss)       # d(ae_loss)/d(l2_loss) = d(ae_loss)/d(q_loss) = 1
@@ -301,6 +320,46 @@ class VQVAE(BaseVQVAE, _LightningBase):
             self.log(name, value.detach(), sync_dist=True, on_step=False, on_epoch=True)      # device scalars: no sync
         self.accumulate_usage(self.quantizer.last_hist)
         return ae_loss
+
+    # ------------------------------------------------------------------ image-grid logging (model.py:240-242, :319-320, :442-456)
+    def image_log_due(self, batch_index: int) -> bool:
+        """the reference's training schedule: batch 2 of every fifth epoch.  False while no directory is set and while the
+        trainer captures (``defer_image_logging``, guarded like ``defer_usage_accumulation``: a captured copy to the host would
+        re-run on every replay, and the settling steps of a capture are not steps of the run)."""
+        return (self.image_log_dir is not None and not self.defer_image_logging and batch_index == 2
+                and self.current_epoch % 5 == 0)
+
+    def image_writer(self):
+        from .imagelog import ImageWriter
+        if self._image_writer is None or self._image_writer[0] != self.image_log_dir:
+            self.close_image_log()
+            self._image_writer = (self.image_log_dir, ImageWriter(self.image_log_dir, workers=self.image_log_workers))
+        return self._image_writer[1]
+
+    @torch.no_grad()
+    def log_reconstructions(self, ground_truths, reconstructions, t_or_v='t'):
+        """The reference's panel (model.py:442-456): ``make_grid`` of the first b = min(B, 8) ground truths (top row) over
+        their reconstructions (bottom row), ``nrow=b``, padding 2, written as
+        ``<image_log_dir>/{train|validation}/reconstructions_epoch=EEEE.png`` instead of a ``wandb.Image``.  Both batches are
+        in the model's (-1,1) ([B,3|4|8,H,W], any layout: the step's padded NHWC tensors are read in place by one HIP kernel
+        on a side stream, imagelog.py); nothing here synchronises.  A no-op while ``image_log_dir`` is None."""
+        if self.image_log_dir is None or self.defer_image_logging:
+            return
+        b = min(ground_truths.shape[0], 8)
+        panel_name = 'train' if t_or_v == 't' else 'validation'
+        self.image_writer().write_grid(f'{panel_name}/reconstructions_epoch={self.current_epoch:04d}.png',
+                                       [ground_truths.detach()[:b], reconstructions.detach()[:b]], nrow=b, padding=2,
+                                       value_ranges='sym')
+
+    def flush_image_log(self) -> None:
+        """every panel asked for so far is on disk"""
+        if self._image_writer is not None:
+            self._image_writer[1].flush()
+
+    def close_image_log(self) -> None:
+        if self._image_writer is not None:
+            writer, self._image_writer = self._image_writer[1], None
+            writer.close()
 
     def accumulate_usage(self, hist: torch.Tensor) -> None:
         """epoch code histogram += this step's (model.py:289-293; the reference's ``else + used_indices`` keeps only the
@@ -328,7 +387,12 @@ class VQVAE(BaseVQVAE, _LightningBase):
 
     @torch.no_grad()
     def validation_step(self, batch: Any, batch_index: int):
-        _, _, q_loss, l2_loss = self._step_losses(batch, training=False)
+        due = self.image_log_dir is not None and batch_index == 2 and not self.defer_image_logging      # model.py:319-320
+        _, _, q_loss, l2_loss = self._step_losses(batch, training=False, want_pair=due)
+        if due:
+            self.log_reconstructions(*self._recon_pair, t_or_v='v')
+        if not self.keep_recon_pair:
+            self._recon_pair = None
         loss = q_loss + l2_loss
         self.log('validation/loss', loss, sync_dist=True, on_step=False, on_epoch=True)
         hist = self.quantizer.last_hist
@@ -360,7 +424,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         self.test_usage_count = None
 
     @torch.no_grad()
-    def test_step(self, images: Any, _):
+    def test_step(self, images: Any, batch_index: int):
         """reconstructions in [0, 1] against the (clamped) inputs: MSE / PSNR / SSIM and the code histogram, all on the
         device; with ``fid_weights`` set, the images (real) and the reconstructions (fake) also feed rFID (model.py:535-541)."""
         images = images[0] if isinstance(images, (tuple, list)) else images
@@ -369,7 +433,10 @@ class VQVAE(BaseVQVAE, _LightningBase):
         hist = torch.bincount(used_indices.reshape(-1), minlength=self.cb_size)
         # (the reference writes `else + used_indices`, i.e. keeps the LAST batch's histogram; the sum is what it logs as usage)
         self.test_usage_count = hist if self.test_usage_count is None else self.test_usage_count + hist
-        self.test_metrics.update(recon, images.to(recon.device).float())
+        images = images.to(recon.device).float()
+        self.test_metrics.update(recon, images)
+        if self.reconstruction_sink is not None:            # the tensors the metrics read, out as uint8 files (evaluate.py)
+            self.reconstruction_sink(batch_index, images, recon)
 
     def on_test_epoch_end(self):
         out = self.test_metrics.compute()

@@ -1485,6 +1485,93 @@ def ingest_u8(pixels, desc, size, out=None, desc_dev=None):
 
 
 # ------------------------------------------------------------------------------------------------------
+# image egress (csrc/egress.hip): fp32 / bf16 image tensors in any of the tree's layouts -> uint8 HWC RGB images or one grid
+# ------------------------------------------------------------------------------------------------------
+EGRESS_RANGES = {'unit': 0, 'sym': 1}       # VQK_RANGE_UNIT: values in [0,1]; VQK_RANGE_SYM: the model's (-1,1)
+
+
+def _egress_source(src, value_range):
+    _require_gpu(src)
+    if src.dim() != 4 or src.shape[1] not in (3, 4, 8) or src.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f'vqk: egress expects fp32 / bf16 images [N,3|4|8,H,W] (any strides), got {src.dtype} {tuple(src.shape)}')
+    if value_range not in EGRESS_RANGES:
+        raise RuntimeError(f"vqk: egress value range is 'unit' ([0,1]) or 'sym' ((-1,1)), got {value_range!r}")
+    return EGRESS_RANGES[value_range]
+
+
+def _egress_launch(src, rng, canvas, rows, cols, row0, pad, pad_value, what):
+    n, c, h, w = src.shape
+    sn, sc, sy, sx = src.stride()
+    # (the stream handle is taken directly, as ingest_u8 does: the kernel uses no workspace)
+    st = _native.lib().vqk_egress_u8(dcode(src.dtype), src.data_ptr(), n, c, h, w, sn, sc, sy, sx, rng, canvas.data_ptr(), rows, cols,
+                                     row0, pad, pad_value, torch.cuda.current_stream().cuda_stream)
+    _native.check(st, what)
+
+
+def _egress_canvas(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    _require_gpu(out)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise RuntimeError(f'vqk: {what} out= must be a contiguous uint8 tensor of shape {tuple(shape)}')
+    return out
+
+
+def egress_u8(src, value_range, out=None):
+    """Images out as uint8 (vqk_egress_u8): src fp32 / bf16 [N,3|4|8,H,W] with ANY strides -- the padded NHWC reconstruction of
+    ``Decoder.forward_padded``, the NHWC target of ``raw_preprocess``, a plain NCHW batch, a slice of any of them -- is read in
+    place (channels 0..2).  value_range 'unit': q = floor(clip(x, 0, 1) * 255 + 0.5); 'sym': the same of x * 0.5 + 0.5 (every
+    operation rounded in fp32; NaN gives 0).  Returns uint8 [N,H,W,3]; with ``out`` given nothing is allocated."""
+    rng = _egress_source(src, value_range)
+    n, _, h, w = src.shape
+    if _native.lib().vqk_egress_canvas_bytes(h, w, max(n, 1), 1, 0) < 0 or n < 1:
+        raise RuntimeError(f'vqk: egress_u8 failed: {n} images of {h} x {w}; n >= 1, sides 1..4096, less than 2 GiB of output are served')
+    canvas = _egress_canvas(out, (n, h, w, 3), src.device, 'egress_u8')
+    _egress_launch(src, rng, canvas, n, 1, 0, 0, 0, 'egress_u8')
+    return canvas
+
+
+def image_grid_shape(count: int, h: int, w: int, nrow: int, padding: int = 2):
+    """(rows, cols, H_g, W_g) of torchvision's ``make_grid`` for ``count`` images of h x w: cols = min(nrow, count), rows =
+    ceil(count / cols), the canvas is rows * (h + padding) + padding by cols * (w + padding) + padding."""
+    cols = max(1, min(int(nrow), count))
+    rows = -(-count // cols)
+    return rows, cols, rows * (h + padding) + padding, cols * (w + padding) + padding
+
+
+def image_grid_u8(sources, nrow, padding=2, pad_value=0, value_ranges='sym', out=None):
+    """``make_grid(pack(sources, '* c h w'), nrow, padding)`` as uint8 HWC (the panel of the reference's log_reconstructions,
+    vqvae/model.py:451-454): the batches of ``sources`` (each as ``egress_u8`` takes them, equal H x W) are concatenated in
+    order; image k of the whole goes to cell (k // cols, k % cols), cols = min(nrow, count).  One launch per source, each
+    writing its own cell rows, padding included -- so every source but the last must fill whole rows (its N a multiple of
+    cols); no fill launch.  value_ranges: one of 'unit' / 'sym' for all, or one per source; pad_value: the uint8 level of the
+    padding.  Returns uint8 [H_g, W_g, 3]; with ``out`` given nothing is allocated."""
+    sources = list(sources)
+    if not sources:
+        raise RuntimeError('vqk: image_grid_u8 needs at least one batch')
+    ranges = [value_ranges] * len(sources) if isinstance(value_ranges, str) else list(value_ranges)
+    if len(ranges) != len(sources):
+        raise RuntimeError('vqk: image_grid_u8: one value range per source')
+    codes = [_egress_source(s, r) for s, r in zip(sources, ranges)]
+    h, w = sources[0].shape[2:]
+    count = sum(int(s.shape[0]) for s in sources)
+    if any(tuple(s.shape[2:]) != (h, w) or s.device != sources[0].device for s in sources):
+        raise RuntimeError('vqk: image_grid_u8: the batches must share H x W and the device')
+    padding, pad_value = int(padding), int(pad_value)
+    rows, cols, hg, wg = image_grid_shape(count, h, w, nrow, padding)
+    if count < 1 or _native.lib().vqk_egress_canvas_bytes(h, w, rows, cols, padding) < 0 or not 0 <= pad_value <= 255:
+        raise RuntimeError(f'vqk: image_grid_u8 failed: {count} images of {h} x {w}, padding {padding}, pad_value {pad_value}')
+    if any(int(s.shape[0]) % cols or int(s.shape[0]) < 1 for s in sources[:-1]) or sources[-1].shape[0] < 1:
+        raise RuntimeError(f'vqk: image_grid_u8: every batch but the last must fill whole rows of {cols} images')
+    canvas = _egress_canvas(out, (hg, wg, 3), sources[0].device, 'image_grid_u8')
+    row0 = 0
+    for s, code in zip(sources, codes):
+        _egress_launch(s, code, canvas, rows, cols, row0, padding, pad_value, 'image_grid_u8')
+        row0 += -(-int(s.shape[0]) // cols)
+    return canvas
+
+
+# ------------------------------------------------------------------------------------------------------
 # autograd functions
 # ------------------------------------------------------------------------------------------------------
 def _weight_mem(weight, cin_pad: int, cout_pad: int) -> torch.Tensor:

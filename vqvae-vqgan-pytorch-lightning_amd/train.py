@@ -14,7 +14,8 @@ WORLD_SIZE plays the role of ``num_nodes * gpus``).  Reproduced from the referen
 Out of scope: the ffcv data module and wandb.  Batches come from ``--dataset_path``: a DIRECTORY with the reference's
 layout (``train/``, optionally ``validation/``) is read through ``data.get_datamodule`` (host threads decode, one HIP kernel
 resizes: data.py); a ``.pt`` / ``.npy`` tensor file holds images [M,3,S,S] in [0,1], resident on the device; omitted: synthetic
-U(0,1) batches (the benchmark's input).
+U(0,1) batches (the benchmark's input).  ``--image_log_dir`` writes the reference's reconstruction panels (model.py:442-456) as PNG
+files instead of ``wandb.Image``s (imagelog.py), under hipGraph replay too.
 """
 from __future__ import annotations
 
@@ -94,6 +95,10 @@ def parse_args(argv=None):
                    help='folder loader with a validation/ folder: validate after every n-th epoch (reference: 5)')
     p.add_argument('--save_path', type=str, default=None, help='directory for checkpoints')
     p.add_argument('--save_every_n_epochs', type=int, default=1)
+    p.add_argument('--image_log_dir', type=str, default=None,
+                   help='directory for reconstruction panels (ground truths over reconstructions, PNG): '
+                        'DIR/run_name/{train|validation}/reconstructions_epoch=EEEE.png at batch 2 of every fifth epoch and of '
+                        'every validation; omitted: no images')
     p.add_argument('--run_name', type=str, default='run')
     p.add_argument('--seed', type=int, required=True)
     p.add_argument('--loading_path', type=str, default=None, help='checkpoint to resume from')
@@ -187,6 +192,8 @@ def main(argv=None):
     if run['use_adversarial']:
         model.criterion.discriminator.compute_dtype = model.compute_dtype
         model.criterion.perceptual_loss.net.compute_dtype = model.compute_dtype
+    if args.image_log_dir is not None:                               # before the capture: it keeps the step's image tensors then
+        model.image_log_dir = os.path.join(args.image_log_dir, args.run_name)
     batches, val_batches = _batches(args, run, device, rank, world)
     if not len(batches):
         raise SystemExit(f'train.py: the dataset holds fewer than one batch per rank '
@@ -226,6 +233,7 @@ def main(argv=None):
             logged = trainer.validate(model, val_batches)
             if rank == 0:
                 print(f'[epoch {epoch}] ' + ' '.join(f'{k} {v:.6f}' for k, v in sorted(logged.items())), flush=True)
+        model.flush_image_log()
         importlib.import_module(PKG + '.ops').check_kernel_health()       # a kernel that gave up on a rendezvous = untrustworthy gradients: stop
         if rank == 0:
             print(f'[epoch {epoch}] loss {float(loss):.6f}', flush=True)
@@ -233,6 +241,7 @@ def main(argv=None):
             os.makedirs(os.path.join(args.save_path, args.run_name), exist_ok=True)
             trainer.save_checkpoint(model, os.path.join(args.save_path, args.run_name, f'epoch={epoch:02d}.ckpt'))
     model.on_train_end()
+    model.close_image_log()
     for loader in (batches, val_batches):
         if hasattr(loader, 'close'):
             loader.close()

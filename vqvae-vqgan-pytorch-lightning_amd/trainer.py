@@ -6,6 +6,7 @@ this trainer issues ONE RCCL all-reduce of the flat gradient arena per optimizer
 (:meth:`FlatAdamW.all_reduce_grads`); the EMA quantizer all-reduces its own statistics."""
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Iterable
 
@@ -176,13 +177,36 @@ class MiniTrainer:
         takes exactly the optimizer steps an eager run takes (train.py)."""
         opt = self.optimizers[0]
         snap = self._snapshot(model) if preserve_state else None
+        # image-grid logging (VQVAE.log_reconstructions): neither the settling steps nor the captured region log; with a directory
+        # set, the captured step's target and reconstruction are kept as static tensors and the panel is written after the replay
+        # of a due step -- nothing is added to the graphs
+        with self._image_logging_deferred(model) as logs:
+            return self._capture(model, example_batch, warmup, snap, logs)
+
+    @contextlib.contextmanager
+    def _image_logging_deferred(self, model):
+        """around a capture, its settling steps included; yields whether the capture keeps the static pair"""
+        self._static_pair = None
+        if not hasattr(model, 'defer_image_logging'):
+            yield False
+            return
+        model.defer_image_logging = True
+        try:
+            yield model.image_log_dir is not None
+        finally:
+            model.defer_image_logging = False
+            model.keep_recon_pair = False
+            model._recon_pair = None
+
+    def _capture(self, model, example_batch, warmup, snap, logs):
+        opt = self.optimizers[0]
         q = getattr(model, 'quantizer', None)
         if hasattr(q, 'enable_device_schedule'):
             # the Gumbel temperature / KL weight are scheduled per step (model.py:218-225): the kernels read them from a device
             # buffer that set_consts() refreshes, so a replay follows the schedule
             q.enable_device_schedule(example_batch.device)
         if not getattr(model, 'automatic_optimization', True):
-            return self._capture_gan(model, example_batch, warmup, snap)
+            return self._capture_gan(model, example_batch, warmup, snap, logs)
         self._static_in = example_batch.clone()
         # the settling steps run on the stream the capture will use: every per-(device, stream) workspace of ops.py (split-K
         # scratch, GroupNorm sums, deterministic-mode slices) exists before the capture starts -- a first use INSIDE the
@@ -207,6 +231,8 @@ class MiniTrainer:
         # thread_local: the autograd worker thread and (multi-GPU) the RCCL watchdog thread issue runtime calls
         # of their own while this thread captures
         model.defer_usage_accumulation = True      # host-side bookkeeping stays out of the captured region
+        if logs:
+            model.keep_recon_pair = True           # held from inside the capture on: the pool never reuses the two tensors
         split = self._use_split(model, opt)
         try:
             if split:
@@ -238,10 +264,11 @@ class MiniTrainer:
             model.defer_usage_accumulation = False
             model.split_backward = False
         self._static_hist = model.quantizer.last_hist          # rewritten by every replay
+        self._static_pair = model._recon_pair if logs else None
         return self._graph
 
     # ------------------------------------------------------------------ VQ-GAN step (manual optimisation) as three graphs
-    def _capture_gan(self, model, example_batch, warmup: int, snap=None):
+    def _capture_gan(self, model, example_batch, warmup: int, snap=None, logs: bool = False):
         """model.py:244-264 under hipGraph replay: [AE half: zero_grad, forward, LPIPS + generator loss, backward] /
         [discriminator half] / [discriminator half with the R1 term] -- the two optimizer steps, the gradient all-reduces and
         the choice of the R1 variant (every ``r1_reg_every`` steps) stay on the host between the replays."""
@@ -277,6 +304,8 @@ class MiniTrainer:
             with torch.cuda.graph(g_ae, stream=side, capture_error_mode='thread_local'):
                 res = model._gan_ae_half(self._static_in)
             self._gan['ae'] = (g_ae, res, model._gan_state[2])
+            if logs:                                # (target, reconstruction) of the captured step: held from here on
+                self._static_pair = (model._gan_state[0], model._gan_state[1].detach())
             for key, step in (('d', 1), ('d_r1', 0)):
                 if key == 'd_r1' and not every:
                     continue
@@ -303,7 +332,8 @@ class MiniTrainer:
             # replaying a step without generator loss and never step the discriminator.  Capture this phase's graphs; the
             # settling steps of the capture do not train (state snapshot put back).
             self._gan = None
-            self._capture_gan(model, batch, warmup=2, snap=self._snapshot(model))
+            with self._image_logging_deferred(model) as logs:
+                self._capture_gan(model, batch, warmup=2, snap=self._snapshot(model), logs=logs)
         model.on_train_batch_start(batch, batch_index)
         if batch is not self._static_in:
             self._static_in.copy_(batch, non_blocking=True)
@@ -334,8 +364,15 @@ class MiniTrainer:
             disc_opt.step()
         model._gan_log(res, q_loss, d_loss, r1_penalty)
         model.accumulate_usage(self._static_hist)
+        self._log_static_pair(model, batch_index)
         self.global_step += 1
         return res[0]
+
+    def _log_static_pair(self, model, batch_index: int) -> None:
+        """after the replays of a due step: the panel from the static target / reconstruction the replay left"""
+        pair = getattr(self, '_static_pair', None)
+        if pair is not None and model.image_log_due(batch_index):
+            model.log_reconstructions(pair[0], pair[1], t_or_v='t')
 
     def _snapshot(self, model):
         return dict(state={k: v.detach().clone() for k, v in model.state_dict().items()},
@@ -413,6 +450,7 @@ class MiniTrainer:
             self._finish_deferred(model, opt)
             opt.all_reduce_grads()
         opt.step()
+        self._log_static_pair(model, batch_index)
         self.global_step += 1
         return self._static_loss
 
@@ -487,6 +525,8 @@ class MiniTrainer:
             total = loss if total is None else total + loss
             count += batch.shape[0]
         model.on_validation_epoch_end()
+        if hasattr(model, 'flush_image_log'):
+            model.flush_image_log()
         model.train(was_training)
         out = {k: float(v) for k, v in model.logged.items() if k.startswith(('validation/', 'val_metrics/'))}
         if count:
@@ -509,4 +549,6 @@ class MiniTrainer:
             model.on_train_epoch_end()
             ops.check_kernel_health()                   # (the epoch end synchronises for the code-usage statistics anyway)
         model.on_train_end()
+        if hasattr(model, 'flush_image_log'):
+            model.flush_image_log()
         return loss
