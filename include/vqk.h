@@ -148,7 +148,8 @@ int vqk_vq_backward_f32(const float* z, const float* e, const int64_t* idx, cons
 int vqk_vq_backward_fused_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype,
                               int64_t n, int k, int d, float cz, float ce, const float* gscale_dev, float* dz, float* de,
                               void* stream);
-/* EMA statistics (vector_quantizers.py:159-169): counts[k] += 1, dw[idx] += z (both pre-zeroed) ... */
+/* EMA statistics (vector_quantizers.py:159-169): counts[k] += 1, dw[idx] += z (both pre-zeroed) ...  fp32 atomics in arrival order;
+ * in deterministic mode (this entry and the fused one): one block per code adds its rows in row order, no atomics -- the same bits every run. */
 int vqk_ema_stats_f32(const float* z, const int64_t* idx, int64_t n, int k, int d,
                       float* counts, float* dw, void* stream);
 /* vqk_ema_stats_f32 with the rows of a 32-row block that share a code summed in LDS first (d == 256): one coalesced atomic row
@@ -334,7 +335,8 @@ int vqk_conv_set_variant(int variant);
  * per-code sums of the codebook gradient -- go through `ws` (>= 64 MiB recommended; VQK_ERR_WORKSPACE when a call needs more)
  * as per-block partials that are added in index order, or run unsplit.  THREAD-LOCAL like the block caps; the workspace must
  * belong to the stream the following launches go to (two streams = two workspaces, re-armed on every switch).  The scalar
- * loss sums and the EMA statistics keep their atomics (values, not gradients). */
+ * loss sums keep their atomics (values, not gradients); the EMA statistics, which the codebook is trained from, are added in row order
+ * (vqk_ema_stats_f32). */
 int vqk_set_deterministic(int on, void* ws, int64_t ws_bytes);
 /* Optional fp32 scratch of the CURRENT stream (thread-local like the block caps; NULL = none; contents need not be
  * initialised).  With it the general conv kernel splits K for problems whose pixel x cout tile grid would leave most of the
@@ -683,6 +685,38 @@ int64_t vqk_egress_canvas_bytes(int h, int w, int rows, int cols, int pad);
 int vqk_egress_u8(int dtype, const void* src, int n, int c, int h, int w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
                   int64_t stride_x, int value_range, uint8_t* canvas, int rows, int cols, int row0, int pad, int pad_value,
                   void* stream);
+
+/* ---------------------------------------------------------------- running statistics (csrc/runstats.hip, scalarlog.py) --------
+ * The device half of the scalar log: what the reference hands to self.log(..., on_epoch=True, sync_dist=True) (vqvae/model.py:
+ * 229-230, :277-286, :342-348, :365-366) is averaged over the epoch without a host synchronisation per step.  Both calls
+ * allocate nothing, never synchronise and can be captured.
+ * vqk_scalar_accum: n <= VQK_SCALAR_MAX device scalars into epoch accumulators, ONE launch.  src / dtype / weight / slot are
+ * HOST arrays of n entries: src[k] a device pointer to one fp32 (VQK_F32) or bf16 (VQK_BF16) value -- the pointers travel as kernel
+ * arguments, no device table --, weight[k] an integer in [0, 2^20) (the batch size in validation, 1 in training), slot[k] in
+ * [0, nslots) the accumulator it goes to, no slot twice in one call.  acc: nslots x VQK_SCALAR_SLOT_DOUBLES doubles on the device,
+ * slot = {sum += (double)x * w, wsum += w, last = x, min, max, nonfinite += !isfinite(x), calls += 1, reserved}.  A non-finite x
+ * enters `sum` like any other (the mean turns NaN) and is counted; min / max skip NaN.  The caller resets a slot to
+ * {0, 0, any, +Inf, -Inf, 0, 0, 0}.  One thread owns one slot and launches are ordered by the stream: `sum` is a fixed-order fp64
+ * sum with exact products, bit-identical to a float64 host loop over the same values. */
+#define VQK_SCALAR_MAX 16
+#define VQK_SCALAR_SLOT_DOUBLES 8
+int vqk_scalar_accum(const void* const* src, const int* dtype, const double* weight, const int* slot, int n, double* acc,
+                     int nslots, void* stream);
+/* vqk_arena_stats: one read-only pass over a FlatAdamW gradient arena g[numel] (fp32) before the optimizer step.  seg_end[nseg]:
+ * the arena's ascending segment ends (the table vqk_adamw takes); seg_group[nseg]: a group id in [0, ngroups) per segment, or -1
+ * for segments that belong to no group (the alignment padding: its elements never reach a result).  With x = (double)g *
+ * (double)scale (exact; scale = the optimizer's grad_scale, finite) the step's result is out[ngroups + 1][3] = {sum of x^2 over the
+ * finite x, max |x| over the finite x, the count of non-finite elements} per group and, in row ngroups, for all groups together
+ * (the groups' rows combined in id order).  Everything accumulates in fp64: per thread, per wave by shuffles, per block in LDS,
+ * the per-block partials in `ws`; a second one-block launch adds them in index order -- no float atomics, the same bits every run.
+ * acc (optional): epoch accumulators [ngroups + 1][VQK_ARENA_ACC_DOUBLES] = {sum of norms, max norm, max of max |x|, sum of
+ * nonfinite, steps}, norm = sqrt(sum x^2), zero-initialised by the caller.  ws: >= vqk_arena_stats_ws_bytes(numel, ngroups) bytes
+ * (-1 for an unsupported size), 8-byte aligned, need not be initialised.  ngroups <= VQK_ARENA_MAX_GROUPS. */
+#define VQK_ARENA_MAX_GROUPS 8
+#define VQK_ARENA_ACC_DOUBLES 5
+int64_t vqk_arena_stats_ws_bytes(int64_t numel, int ngroups);
+int vqk_arena_stats(const float* g, int64_t numel, const int64_t* seg_end, const int32_t* seg_group, int nseg, int ngroups,
+                    float scale, void* ws, int64_t ws_bytes, double* out, double* acc, void* stream);
 
 #ifdef __cplusplus
 }

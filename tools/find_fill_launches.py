@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Which host lines issue the NON-vqk launches of a train step (ATen fills / copies / elementwise kernels, hipMemcpy)?
 torch.profiler with stacks over one eager step; printed: count, op, innermost frame inside this repository.
-Usage: python tools/find_fill_launches.py [--gan] [--batch 8]"""
+Usage: python tools/find_fill_launches.py [--gan] [--batch 8] [--scalar_log]   (--scalar_log: with a scalarlog.ScalarLog attached)"""
 import argparse
 import collections
 import importlib
@@ -18,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--gan', action='store_true')
 ap.add_argument('--batch', type=int, default=8)
 ap.add_argument('--quantizer', default='standard')
+ap.add_argument('--scalar_log', action='store_true')
 a = ap.parse_args()
 trainer_mod = importlib.import_module('vqvae-vqgan-pytorch-lightning_amd.trainer')
 model_mod = importlib.import_module('vqvae-vqgan-pytorch-lightning_amd.model')
@@ -31,6 +32,8 @@ if a.gan:
 tr = trainer_mod.MiniTrainer(num_training_batches=100)
 tr.attach(m)
 m.on_train_start()
+if a.scalar_log:
+    m.scalar_log = importlib.import_module('vqvae-vqgan-pytorch-lightning_amd.scalarlog').ScalarLog(None)
 x = torch.rand(a.batch, 3, 256, 256).cuda()
 for i in range(3):
     tr.train_batch(m, x, i)

@@ -136,10 +136,12 @@ _PROTOS = {
     'vqk_fid_stats': [P, I, I, P, P, P],
     'vqk_ingest_u8': [P, L, P, P, I, I, I, L, P, P],
     'vqk_egress_u8': [I, P, I, I, I, I, L, L, L, L, I, P, I, I, I, I, I, P],
+    'vqk_scalar_accum': [P, P, P, P, I, P, I, P],
+    'vqk_arena_stats': [P, L, P, P, I, I, F, P, L, P, P, P],
 }
 _SPECIAL = {'vqk_set_tuning': (I, [c_char_p, I]), 'vqk_reset_tuning': (I, []), 'vqk_tuning_count': (I, []),
             'vqk_tuning_name': (c_char_p, [I]),
-            'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
+            'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_arena_stats_ws_bytes': (c_int64, [L, I]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
 EXPORTS = sorted(list(_PROTOS) + list(_SPECIAL))
 
 

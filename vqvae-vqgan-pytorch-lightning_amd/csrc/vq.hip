@@ -640,6 +640,41 @@ __global__ __launch_bounds__(256) void ema_stats_kernel(const float* __restrict_
     }
 }
 
+// Deterministic mode: the same statistics with every sum in ROW ORDER and no atomics.  One block per code scans idx in chunks of
+// 256 rows (a wave's matches as one ballot mask, the four masks through LDS); every thread owns channels and adds the matching
+// rows of z as the masks list them, lowest row first.  K x N index reads instead of N: the price of the order.
+__global__ __launch_bounds__(256) void ema_stats_ordered_kernel(const float* __restrict__ z, const int64_t* __restrict__ idx,
+                                                                int64_t n, int d, float* __restrict__ counts,
+                                                                float* __restrict__ dw) {
+    __shared__ unsigned long long masks[4];
+    const int64_t code = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int c0 = 0; c0 < d; c0 += 256) {
+        const int c = c0 + tid;
+        float acc = 0.f;
+        int cnt = 0;
+        for (int64_t r0 = 0; r0 < n; r0 += 256) {
+            const int64_t r = r0 + tid;
+            const unsigned long long m = __ballot(r < n && idx[r] == code);
+            if (lane == 0) masks[wave] = m;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                unsigned long long mm = masks[w];          // the same for every thread: no divergence
+                cnt += __popcll(mm);
+                while (mm) {
+                    const int b = __ffsll((long long)mm) - 1;
+                    if (c < d) acc += z[(r0 + w * 64 + b) * d + c];
+                    mm &= mm - 1;
+                }
+            }
+            __syncthreads();
+        }
+        if (c < d) dw[code * d + c] += acc;
+        if (c0 == 0 && tid == 0) counts[code] += (float)cnt;
+    }
+}
+
 // vector_quantizers.py:161,164
 __global__ void ema_count_kernel(float* __restrict__ ema_count, const float* __restrict__ counts, int k, float decay,
                                  float eps, float batch) {
@@ -796,6 +831,11 @@ int vqk_ema_stats_f32(const float* z, const int64_t* idx, int64_t n, int k, int 
     VQK_REQUIRE(z && idx && counts && dw, VQK_ERR_ARG);
     VQK_REQUIRE(n >= 0 && k > 0 && d > 0, VQK_ERR_SHAPE);
     if (n == 0) return VQK_OK;
+    if (vqkd::det_state().on) {
+        hipLaunchKernelGGL(ema_stats_ordered_kernel, dim3((unsigned)k), dim3(256), 0, vqk_stream(stream), z, idx, n, d, counts, dw);
+        VQK_CHECK_LAUNCH();
+        return VQK_OK;
+    }
     hipLaunchKernelGGL(ema_stats_kernel, dim3(vqk_grid_1d(n, 4)), dim3(256), 0, vqk_stream(stream), z, idx, n, d, counts, dw);
     VQK_CHECK_LAUNCH();
     return VQK_OK;

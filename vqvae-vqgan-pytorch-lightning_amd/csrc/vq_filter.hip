@@ -716,6 +716,7 @@ int vqk_ema_stats_fused_f32(const float* z, const int64_t* idx, int64_t n, int k
     VQK_REQUIRE(n >= 0 && k > 0 && d == FD, VQK_ERR_SHAPE);
     VQK_REQUIRE(vqk_aligned16(z), VQK_ERR_ALIGN);
     if (n == 0) return VQK_OK;
+    if (vqkd::det_state().on) return vqk_ema_stats_f32(z, idx, n, k, d, counts, dw, stream);      // the ordered form (vq.hip)
     hipLaunchKernelGGL(ema_stats_block_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, vqk_stream(stream), z, idx, n, counts, dw);
     VQK_CHECK_LAUNCH();
     return VQK_OK;

@@ -100,6 +100,9 @@ class VQVAE(BaseVQVAE, _LightningBase):
         self._recon_pair = None
         self._image_writer = None              # (image_log_dir, imagelog.ImageWriter)
         self.reconstruction_sink = None        # test loop: callable(batch_index, images, reconstructions), both [0,1] (evaluate.py)
+        # scalar logging (scalarlog.ScalarLog): epoch means of what self.log receives, gradient statistics, JSON lines.  None = no
+        # log: nothing below changes.  MiniTrainer drives it; self.log itself is unchanged.
+        self.scalar_log = None
 
         qt, qp = q_conf['type'], q_conf['params']
         if qt == 'standard':
@@ -294,15 +297,23 @@ class VQVAE(BaseVQVAE, _LightningBase):
             self.log_reconstructions(self._gan_state[0], self._gan_state[1], t_or_v='t')
         ae_opt, disc_opt = self.optimizers()
         ae_opt.all_reduce_grads()
+        self._log_grad_stats(ae_opt, 'autoencoder')
         ae_opt.step()
         step = self.current_epoch * self.trainer.num_training_batches + batch_index
         loss, d_loss, r1_penalty = self._gan_disc_half(step)
         if loss is not None:
             disc_opt.all_reduce_grads()
+            self._log_grad_stats(disc_opt, 'discriminator')
             disc_opt.step()
         self._gan_log(res, self._gan_state[2], d_loss, r1_penalty)
         self.accumulate_usage(self.quantizer.last_hist)
         return res[0].detach()
+
+    def _log_grad_stats(self, opt, name: str) -> None:
+        """manual optimisation: the gradient statistics of the scalar log, between the all-reduce and the optimizer step"""
+        log_grads = getattr(self.trainer, '_log_grads', None)
+        if self.scalar_log is not None and log_grads is not None:
+            log_grads(self, opt, name)
 
     def training_step(self, batch: Any, batch_index: int):
         if isinstance(self.criterion, VQLPIPSWithDiscriminator):

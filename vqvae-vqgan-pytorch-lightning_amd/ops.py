@@ -1572,6 +1572,63 @@ def image_grid_u8(sources, nrow, padding=2, pad_value=0, value_ranges='sym', out
 
 
 # ------------------------------------------------------------------------------------------------------
+# running statistics (csrc/runstats.hip): epoch accumulators of the step's scalars, gradient-arena statistics -- scalarlog.py
+# ------------------------------------------------------------------------------------------------------
+SCALAR_MAX = 16              # VQK_SCALAR_MAX
+SCALAR_SLOT = 8              # VQK_SCALAR_SLOT_DOUBLES: sum, wsum, last, min, max, nonfinite, calls, reserved
+ARENA_MAX_GROUPS = 8         # VQK_ARENA_MAX_GROUPS
+ARENA_ACC = 5                # VQK_ARENA_ACC_DOUBLES: sum of norms, max norm, max of max |x|, sum of nonfinite, steps
+
+
+def scalar_accum(sources, weights, slots, acc) -> None:
+    """``vqk_scalar_accum``: the 0-dim (or one-element) fp32 / bf16 device tensors ``sources`` into the fp64 accumulator block
+    ``acc`` [nslots, 8], source k with the integer weight ``weights[k]`` into slot ``slots[k]``; any number of sources (16 per
+    launch).  Nothing is allocated on the device, nothing synchronises; the pointers travel as kernel arguments."""
+    import ctypes
+    _require_gpu(acc)
+    if acc.dtype != torch.float64 or not acc.is_contiguous() or acc.numel() % SCALAR_SLOT:
+        raise RuntimeError('vqk: scalar_accum needs a contiguous float64 accumulator block of 8 doubles per slot')
+    nslots = acc.numel() // SCALAR_SLOT
+    for t in sources:
+        if not t.is_cuda or t.numel() != 1 or t.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f'vqk: scalar_accum takes one-element fp32 / bf16 device tensors, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    lib, stream = _native.lib(), torch.cuda.current_stream().cuda_stream
+    for lo in range(0, len(sources), SCALAR_MAX):
+        part = sources[lo:lo + SCALAR_MAX]
+        n = len(part)
+        st = lib.vqk_scalar_accum((ctypes.c_void_p * n)(*[t.data_ptr() for t in part]), (ctypes.c_int * n)(*[dcode(t.dtype) for t in part]),
+                                  (ctypes.c_double * n)(*[float(w) for w in weights[lo:lo + n]]),
+                                  (ctypes.c_int * n)(*[int(s) for s in slots[lo:lo + n]]), n, acc.data_ptr(), nslots, stream)
+        _native.check(st, 'scalar_accum')
+
+
+def arena_stats_ws_doubles(numel: int, ngroups: int) -> int:
+    nbytes = _native.lib().vqk_arena_stats_ws_bytes(int(numel), int(ngroups))
+    if nbytes < 0:
+        raise RuntimeError(f'vqk: arena_stats serves 1..{ARENA_MAX_GROUPS} groups and at most 2^38 elements, got {ngroups} / {numel}')
+    return nbytes // 8
+
+
+def arena_stats(flat_g, seg_end, seg_group, ngroups: int, scale: float, ws, out, acc=None) -> None:
+    """``vqk_arena_stats``: one pass over the fp32 gradient arena ``flat_g``; out [ngroups + 1, 3] float64 = (sum x^2, max |x|,
+    non-finite count) of x = g * scale per group and for all groups, acc [ngroups + 1, 5] float64 the epoch accumulators it is
+    folded into.  ``seg_end`` int64 / ``seg_group`` int32: the arena's segment table; ``ws``: float64 scratch of at least
+    ``arena_stats_ws_doubles`` elements.  Two launches on the current stream."""
+    for t in (flat_g, seg_end, seg_group, ws, out) + (() if acc is None else (acc,)):
+        _require_gpu(t)
+    if (flat_g.dtype != torch.float32 or seg_end.dtype != torch.int64 or seg_group.dtype != torch.int32 or ws.dtype != torch.float64
+            or out.dtype != torch.float64 or (acc is not None and acc.dtype != torch.float64)):
+        raise RuntimeError('vqk: arena_stats takes an fp32 arena, int64 segment ends, int32 group ids and float64 buffers')
+    if (seg_group.numel() != seg_end.numel() or out.numel() < (ngroups + 1) * 3 or (acc is not None and acc.numel() < (ngroups + 1) * ARENA_ACC)
+            or not all(t.is_contiguous() for t in (flat_g, seg_end, seg_group, ws, out) + (() if acc is None else (acc,)))):
+        raise RuntimeError('vqk: arena_stats: one group id per segment, out [G+1,3], acc [G+1,5], all contiguous')
+    st = _native.lib().vqk_arena_stats(flat_g.data_ptr(), flat_g.numel(), seg_end.data_ptr(), seg_group.data_ptr(), seg_end.numel(),
+                                       int(ngroups), float(scale), ws.data_ptr(), ws.numel() * 8, out.data_ptr(), _p(acc),
+                                       torch.cuda.current_stream().cuda_stream)
+    _native.check(st, 'arena_stats')
+
+
+# ------------------------------------------------------------------------------------------------------
 # autograd functions
 # ------------------------------------------------------------------------------------------------------
 def _weight_mem(weight, cin_pad: int, cout_pad: int) -> torch.Tensor:

@@ -99,6 +99,12 @@ def parse_args(argv=None):
                    help='directory for reconstruction panels (ground truths over reconstructions, PNG): '
                         'DIR/run_name/{train|validation}/reconstructions_epoch=EEEE.png at batch 2 of every fifth epoch and of '
                         'every validation; omitted: no images')
+    p.add_argument('--log_dir', type=str, default=None,
+                   help='directory for the scalar log: DIR/run_name/metrics.jsonl, one JSON object per line (epoch means of the '
+                        'losses, lr, gradient statistics); omitted: no log')
+    p.add_argument('--log_every_n_steps', type=int, default=50, help="scalar log: a 'step' record (lr, Gumbel schedule) every n-th optimizer step")
+    p.add_argument('--grad_stats_every', type=int, default=1,
+                   help='scalar log: gradient norm / max / non-finite count of every N-th optimizer step (0: off)')
     p.add_argument('--run_name', type=str, default='run')
     p.add_argument('--seed', type=int, required=True)
     p.add_argument('--loading_path', type=str, default=None, help='checkpoint to resume from')
@@ -194,6 +200,10 @@ def main(argv=None):
         model.criterion.perceptual_loss.net.compute_dtype = model.compute_dtype
     if args.image_log_dir is not None:                               # before the capture: it keeps the step's image tensors then
         model.image_log_dir = os.path.join(args.image_log_dir, args.run_name)
+    if args.log_dir is not None:
+        scalarlog = importlib.import_module(PKG + '.scalarlog')
+        model.scalar_log = scalarlog.ScalarLog(os.path.join(args.log_dir, args.run_name), rank, world,
+                                               log_every_n_steps=args.log_every_n_steps, grad_stats_every=args.grad_stats_every)
     batches, val_batches = _batches(args, run, device, rank, world)
     if not len(batches):
         raise SystemExit(f'train.py: the dataset holds fewer than one batch per rank '
@@ -235,13 +245,19 @@ def main(argv=None):
                 print(f'[epoch {epoch}] ' + ' '.join(f'{k} {v:.6f}' for k, v in sorted(logged.items())), flush=True)
         model.flush_image_log()
         importlib.import_module(PKG + '.ops').check_kernel_health()       # a kernel that gave up on a rendezvous = untrustworthy gradients: stop
-        if rank == 0:
+        epoch_rec = trainer.log_train_epoch(model)                        # None without --log_dir
+        if rank == 0 and epoch_rec is not None:                           # the epoch means, as the log file holds them
+            means = {k: v for k, v in epoch_rec.items() if k.startswith('train/') or k in ('g_weight', 'r1_penalty')}
+            print(f'[epoch {epoch}] ' + ' '.join(f'{k} {v:.6f}' for k, v in sorted(means.items())), flush=True)
+        elif rank == 0:
             print(f'[epoch {epoch}] loss {float(loss):.6f}', flush=True)
         if args.save_path and (epoch + 1) % args.save_every_n_epochs == 0:
             os.makedirs(os.path.join(args.save_path, args.run_name), exist_ok=True)
             trainer.save_checkpoint(model, os.path.join(args.save_path, args.run_name, f'epoch={epoch:02d}.ckpt'))
     model.on_train_end()
     model.close_image_log()
+    if model.scalar_log is not None:
+        model.scalar_log.close()
     for loader in (batches, val_batches):
         if hasattr(loader, 'close'):
             loader.close()

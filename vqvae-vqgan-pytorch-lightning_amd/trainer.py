@@ -80,6 +80,7 @@ class MiniTrainer:
         if not getattr(model, 'automatic_optimization', True):       # VQ-GAN: the module steps both optimizers itself
             loss = model.training_step(batch, batch_index)
             self.global_step += 1
+            self._log_step(model)
             return loss
         opt.zero_grad()
         if self._use_split(model, opt):
@@ -90,9 +91,60 @@ class MiniTrainer:
             ops.join_side_streams()
             self._finish_deferred(model, opt)
             opt.all_reduce_grads()
+        self._log_grads(model, opt, 'autoencoder')
         opt.step()
         self.global_step += 1
+        self._log_step(model)
         return loss
+
+    # ------------------------------------------------------------------ scalar log (scalarlog.ScalarLog on model.scalar_log)
+    # Opt-in: with no log attached every path below returns at once.  The log reads the tensors training_step / _gan_log left in
+    # model.logged -- under replay the static tensors the replay just rewrote -- with one launch and no host synchronisation.
+    @staticmethod
+    def _slog(model):
+        log = getattr(model, 'scalar_log', None)
+        return None if (log is None or log.paused) else log
+
+    def _slog_groups(self, model, log) -> None:
+        """name the autoencoder optimizer's parameter groups by owning module, once per (log, optimizer)"""
+        opt = self.optimizers[0]
+        if getattr(log, '_grouped_for', None) is not opt:
+            log.register_optimizer(opt, 'autoencoder', {n: list(getattr(model, n).parameters()) for n in ('encoder', 'decoder', 'quantizer')})
+            log._grouped_for = opt
+
+    def _log_grads(self, model, opt, name: str) -> None:
+        """after the all-reduce, before ``opt.step()``, on the current stream (the one the step is issued to)"""
+        log = self._slog(model)
+        if log is not None:
+            self._slog_groups(model, log)
+            log.grad_stats(opt, name)
+
+    def _log_step(self, model) -> None:
+        """after a finished step (``global_step`` already counts it)"""
+        log = self._slog(model)
+        if log is not None:
+            log.train_step(model.logged)
+            from .scalarlog import STEP_EXTRA_KEYS
+            log.step_event(self.global_step, model.current_epoch, self.optimizers[0].param_groups[0]['lr'],
+                           {k: model.logged[k] for k in STEP_EXTRA_KEYS if k in model.logged})
+
+    def log_train_epoch(self, model) -> dict | None:
+        """at the end of a training epoch (the one host synchronisation of the log): the written ``train_epoch`` record"""
+        log = self._slog(model)
+        return None if log is None else log.epoch_end('train_epoch', model.current_epoch, self.global_step)
+
+    @contextlib.contextmanager
+    def _scalar_log_deferred(self, model):
+        """around a capture: neither its settling steps nor the captured region accumulate (guarded like defer_usage_accumulation)"""
+        log = getattr(model, 'scalar_log', None)
+        if log is None:
+            yield
+            return
+        was, log.paused = log.paused, True
+        try:
+            yield
+        finally:
+            log.paused = was
 
     # ------------------------------------------------------------------ gradient all-reduce under the backward
     # Lightning's DDP overlaps its bucketed all-reduce with the backward (vqvae/train.py:128).  Here the backward is cut at
@@ -180,7 +232,7 @@ class MiniTrainer:
         # image-grid logging (VQVAE.log_reconstructions): neither the settling steps nor the captured region log; with a directory
         # set, the captured step's target and reconstruction are kept as static tensors and the panel is written after the replay
         # of a due step -- nothing is added to the graphs
-        with self._image_logging_deferred(model) as logs:
+        with self._image_logging_deferred(model) as logs, self._scalar_log_deferred(model):
             return self._capture(model, example_batch, warmup, snap, logs)
 
     @contextlib.contextmanager
@@ -332,7 +384,7 @@ class MiniTrainer:
             # replaying a step without generator loss and never step the discriminator.  Capture this phase's graphs; the
             # settling steps of the capture do not train (state snapshot put back).
             self._gan = None
-            with self._image_logging_deferred(model) as logs:
+            with self._image_logging_deferred(model) as logs, self._scalar_log_deferred(model):
                 self._capture_gan(model, batch, warmup=2, snap=self._snapshot(model), logs=logs)
         model.on_train_batch_start(batch, batch_index)
         if batch is not self._static_in:
@@ -352,20 +404,24 @@ class MiniTrainer:
             osd.wait_stream(cur)
             with torch.cuda.stream(osd):
                 ae_opt.all_reduce_grads()
+                self._log_grads(model, ae_opt, 'autoencoder')
                 ae_opt.step()
             g.replay()
             cur.wait_stream(osd)
         else:
             ae_opt.all_reduce_grads()
+            self._log_grads(model, ae_opt, 'autoencoder')
             ae_opt.step()
             g.replay()
         if loss is not None:
             disc_opt.all_reduce_grads()
+            self._log_grads(model, disc_opt, 'discriminator')
             disc_opt.step()
         model._gan_log(res, q_loss, d_loss, r1_penalty)
         model.accumulate_usage(self._static_hist)
         self._log_static_pair(model, batch_index)
         self.global_step += 1
+        self._log_step(model)
         return res[0]
 
     def _log_static_pair(self, model, batch_index: int) -> None:
@@ -381,7 +437,8 @@ class MiniTrainer:
                     step=self.global_step,
                     # the settling steps draw Gumbel noise / augmentation boxes and log: neither may leak into the run
                     rng=(torch.cuda.get_rng_state() if torch.cuda.is_available() else None, torch.get_rng_state()),
-                    logged=(dict(model.logged) if isinstance(getattr(model, 'logged', None), dict) else None))
+                    logged=(dict(model.logged) if isinstance(getattr(model, 'logged', None), dict) else None),
+                    scalar_log=(model.scalar_log.snapshot() if getattr(model, 'scalar_log', None) is not None else None))
 
     @torch.no_grad()
     def _restore(self, model, snap):
@@ -406,6 +463,8 @@ class MiniTrainer:
             torch.set_rng_state(snap['rng'][1])
         if snap.get('logged') is not None:
             model.logged = snap['logged']
+        if snap.get('scalar_log') is not None and getattr(model, 'scalar_log', None) is not None:
+            model.scalar_log.restore(snap['scalar_log'])
 
     def _eager_step(self, model, batch, batch_index):
         opt = self.optimizers[0]
@@ -449,9 +508,11 @@ class MiniTrainer:
             model.accumulate_usage(self._static_hist)      # epoch code histogram: eager add of the replay's histogram
             self._finish_deferred(model, opt)
             opt.all_reduce_grads()
+        self._log_grads(model, opt, 'autoencoder')
         opt.step()
         self._log_static_pair(model, batch_index)
         self.global_step += 1
+        self._log_step(model)
         return self._static_loss
 
     # ------------------------------------------------------------------ checkpoints (vqvae/train.py:106-122)
@@ -520,10 +581,13 @@ class MiniTrainer:
         was_training = model.training
         model.eval()
         total, count = None, 0
+        log = self._slog(model)
         for i, batch in enumerate(batches):
             loss = model.validation_step(batch, i).detach().float() * batch.shape[0]
             total = loss if total is None else total + loss
             count += batch.shape[0]
+            if log is not None:
+                log.validation_step(model.logged, batch.shape[0])
         model.on_validation_epoch_end()
         if hasattr(model, 'flush_image_log'):
             model.flush_image_log()
@@ -531,6 +595,11 @@ class MiniTrainer:
         out = {k: float(v) for k, v in model.logged.items() if k.startswith(('validation/', 'val_metrics/'))}
         if count:
             out['validation/loss'] = float(total) / count
+        if log is not None:
+            # with a log attached: the batch-size-weighted mean of EVERY validation/* key, over all ranks, and the record written
+            rec = log.epoch_end('validation', model.current_epoch, self.global_step,
+                                {k: v for k, v in out.items() if k.startswith('val_metrics/')})
+            out.update({k: v for k, v in rec.items() if k.startswith('validation/')})
         return out
 
     def fit(self, model, batches: Iterable):
@@ -548,6 +617,7 @@ class MiniTrainer:
                 loss = self.train_batch(model, batch, i)
             model.on_train_epoch_end()
             ops.check_kernel_health()                   # (the epoch end synchronises for the code-usage statistics anyway)
+            self.log_train_epoch(model)
         model.on_train_end()
         if hasattr(model, 'flush_image_log'):
             model.flush_image_log()
