@@ -536,6 +536,48 @@ int vqk_axpby(int dtype, const void* x, const void* y2, void* y, float a, float 
 int vqk_adamw(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end, const float* seg_wd,
               int nseg, float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* shadow,
               void* stream);
+/* Guarded optimizer step: the decision "skip a step whose gradients hold an Inf / NaN" (torch.amp.GradScaler's rule) and
+ * "scale the gradients so that their global norm is at most max_norm" (torch.nn.utils.clip_grad_norm_) is taken AND obeyed on
+ * the device, without the host waiting for it.  Per step, in stream order: vqk_arena_stats -> vqk_step_guard -> vqk_adamw_guarded.
+ * None of the three allocates or synchronises; all can be captured.
+ *
+ * vqk_step_guard: one launch of one wave.  stats_row: a device {sum x^2, max |x|, nonfinite} row of doubles as vqk_arena_stats
+ * writes it (the row "all groups", taken at scale = grad_scale).  apply = !(skip_nonfinite && nonfinite > 0);
+ * coef = max_norm > 0 ? min(1, max_norm / (sqrt(sum x^2) + 1e-6)) : 1 in fp64 (the norm over the FINITE elements);
+ * control block (VQK_GUARD_CTRL_BYTES, 16-byte aligned) = {int32 apply, float eff_scale = (float)((double)grad_scale * coef),
+ * float step_size = (float)((double)lr / bc1(t)), float inv_sqrt_bc2 = (float)(1 / sqrt(bc2(t)))} with t = applied + 1: the
+ * pair vqk_adamw derives on the host for step t, so a skipped step does not advance the bias correction.  bc1 / bc2 come from
+ * bias_table[bias_len][2] (device doubles, entry t - 1 = {1 - beta1^t, 1 - beta2^t}, t clamped to bias_len), filled on the host by
+ * vqk_adamw_bias_table with vqk_adamw's own pow() -- the device's pow need not round like the host's.
+ * State block: VQK_GUARD_STATE_DOUBLES doubles (counts are exact integers), indexed by the VQK_GUARD_* names below; the caller
+ * resets it to zeros with COEF_MIN = 1.  CLIPPED, COEF_SUM and COEF_MIN cover applied steps only; LAST_NORM is written by every
+ * launch.  One lane owns both blocks and launches are stream-ordered: every field is reproducible bit for bit.
+ *
+ * vqk_adamw_bias_table: host only.  Returns T, the first step at which 1 - beta^t == 1.0 for both betas (from there on the pair
+ * is constant), and fills min(T, capacity) entries when table != NULL; -1 for betas outside [0, 1) or T > VQK_GUARD_TABLE_MAX.
+ *
+ * vqk_adamw_guarded: vqk_adamw with step_size, inv_sqrt_bc2, the gradient scale and the apply flag read from `control`.  With
+ * apply == 0 every block returns after reading the control block: p / m / v / shadow keep their bits.  With apply == 1 the result
+ * is bit-identical to vqk_adamw(step = t, grad_scale = eff_scale): the same device function.
+ * Both validate before any launch (VQK_ERR_ARG: NULL pointers, nseg <= 0, m == NULL with beta1 != 0, non-finite max_norm / lr /
+ * grad_scale, bias_len < 1). */
+#define VQK_GUARD_CTRL_BYTES 16
+#define VQK_GUARD_STATE_DOUBLES 8
+#define VQK_GUARD_APPLIED 0        /* steps taken */
+#define VQK_GUARD_SKIPPED 1        /* steps left out */
+#define VQK_GUARD_CLIPPED 2        /* applied steps with coef < 1 */
+#define VQK_GUARD_SKIP_RUN 3       /* current run of consecutive skips */
+#define VQK_GUARD_MAX_SKIP_RUN 4   /* longest such run */
+#define VQK_GUARD_COEF_SUM 5       /* sum of coef over applied steps */
+#define VQK_GUARD_COEF_MIN 6       /* minimum of coef over applied steps (reset value 1) */
+#define VQK_GUARD_LAST_NORM 7      /* sqrt(sum x^2) of the last launch */
+#define VQK_GUARD_TABLE_MAX (1 << 22)
+int64_t vqk_adamw_bias_table(float beta1, float beta2, double* table, int64_t capacity);
+int vqk_step_guard(const double* stats_row, int skip_nonfinite, double max_norm, float lr, float grad_scale,
+                   const double* bias_table, int64_t bias_len, double* state, void* control, void* stream);
+int vqk_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end, const float* seg_wd,
+                      int nseg, float lr, float beta1, float beta2, float eps, const void* control, void* shadow,
+                      void* stream);
 
 /* ---------------------------------------------------------------- StyleGAN2 plugin ops ------
  * Same argument meaning as the reference's pybind functions (bias_act.cpp:32, upfirdn2d.cpp:16), with raw

@@ -114,6 +114,8 @@ _PROTOS = {
     'vqk_tanh_backward': [I, P, P, P, L, P],
     'vqk_axpby': [I, P, P, P, F, F, L, P],
     'vqk_adamw': [P, P, P, P, L, P, P, I, F, F, F, F, I, F, P, P],
+    'vqk_step_guard': [P, I, c_double, F, F, P, L, P, P, P],
+    'vqk_adamw_guarded': [P, P, P, P, L, P, P, I, F, F, F, F, P, P, P],
     'vqk_act_backward': [I, P, P, P, L, I, F, P],
     'vqk_act_backward_colsum': [I, P, P, P, L, I, I, F, P, P],
     'vqk_act_backward_colsum_scaled': [I, P, P, P, L, I, I, F, F, P, P],
@@ -141,7 +143,7 @@ _PROTOS = {
 }
 _SPECIAL = {'vqk_set_tuning': (I, [c_char_p, I]), 'vqk_reset_tuning': (I, []), 'vqk_tuning_count': (I, []),
             'vqk_tuning_name': (c_char_p, [I]),
-            'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_arena_stats_ws_bytes': (c_int64, [L, I]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
+            'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_arena_stats_ws_bytes': (c_int64, [L, I]), 'vqk_adamw_bias_table': (c_int64, [F, F, P, L]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
 EXPORTS = sorted(list(_PROTOS) + list(_SPECIAL))
 
 

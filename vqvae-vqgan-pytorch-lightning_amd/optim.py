@@ -5,6 +5,8 @@ two groups, weight decay only on conv weights; betas (0, 0.99) => the first mome
 and is not stored)."""
 from __future__ import annotations
 
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -69,6 +71,55 @@ def quiesce_collectives(timeout_s: float = 30.0) -> None:
 
 def _is_channels_last_param(p: torch.Tensor) -> bool:
     return p.dim() == 4 and not p.is_contiguous() and p.is_contiguous(memory_format=torch.channels_last)
+
+
+# the guard's state block (include/vqk.h: VQK_GUARD_*)
+GUARD_APPLIED, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_SKIP_RUN, GUARD_MAX_SKIP_RUN, GUARD_COEF_SUM, GUARD_COEF_MIN, GUARD_LAST_NORM = range(8)
+GUARD_STATE_INIT = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def check_guard_settings(skip_nonfinite, max_grad_norm):
+    """(bool, float | None); refuses a non-positive or non-finite ``max_grad_norm``"""
+    if max_grad_norm is not None:
+        max_grad_norm = float(max_grad_norm)
+        if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+            raise ValueError(f'max_grad_norm must be a positive finite number or None, got {max_grad_norm}')
+    return bool(skip_nonfinite), max_grad_norm
+
+
+def guard_state_dict(block) -> dict:
+    """the eight doubles of a guard state block -> named values (``clip_coef_mean`` is None before the first applied step)"""
+    b = [float(x) for x in block]
+    applied = b[GUARD_APPLIED]
+    return dict(applied=int(applied), skipped=int(b[GUARD_SKIPPED]), clipped=int(b[GUARD_CLIPPED]),
+                consecutive_skipped=int(b[GUARD_SKIP_RUN]), max_consecutive_skipped=int(b[GUARD_MAX_SKIP_RUN]),
+                clip_coef_sum=b[GUARD_COEF_SUM], clip_coef_min=b[GUARD_COEF_MIN], last_norm=b[GUARD_LAST_NORM])
+
+
+def guard_epoch_record(name: str, now: dict, before: dict | None = None) -> dict:
+    """``guard/<name>/*`` of a ``train_epoch`` record from two readings of a state block (``guard_state_dict``; ``before`` None: a
+    fresh block): the counts and the mean clip coefficient of the steps in between; ``max_consecutive_skipped`` and
+    ``clip_coef_min`` are the block's values (``FlatAdamW.guard_epoch_end`` restarts both every epoch)"""
+    before = before or guard_state_dict(GUARD_STATE_INIT)
+    applied = now['applied'] - before['applied']
+    coef_sum = now['clip_coef_sum'] - before['clip_coef_sum']
+    pre = f'guard/{name}/'
+    return {pre + 'applied': applied, pre + 'skipped': now['skipped'] - before['skipped'],
+            pre + 'clipped': now['clipped'] - before['clipped'], pre + 'max_consecutive_skipped': now['max_consecutive_skipped'],
+            pre + 'clip_coef_mean': coef_sum / applied if applied > 0 else math.nan, pre + 'clip_coef_min': now['clip_coef_min']}
+
+
+def bias_table(beta1: float, beta2: float) -> torch.Tensor:
+    """[T, 2] float64 on the host: {1 - beta1^t, 1 - beta2^t} for t = 1..T, by ``vqk_adamw``'s own host expressions
+    (``vqk_adamw_bias_table``); from T on both are exactly 1"""
+    lib = _native.lib()
+    n = lib.vqk_adamw_bias_table(float(beta1), float(beta2), 0, 0)
+    if n < 1:
+        raise ValueError(f'FlatAdamW guard: betas {beta1}, {beta2} are outside [0, 1) or too close to 1 for the bias-correction table')
+    table = torch.empty(n, 2, dtype=torch.float64)
+    if lib.vqk_adamw_bias_table(float(beta1), float(beta2), table.data_ptr(), n) != n:
+        raise RuntimeError('vqk: adamw_bias_table changed its mind')
+    return table
 
 
 class FlatAdamW(torch.optim.Optimizer):
@@ -136,11 +187,112 @@ class FlatAdamW(torch.optim.Optimizer):
         self.grad_scale = 1.0
         self.shadow = None                    # optional bf16 copy of flat_p refreshed by step()
         self.generation = 0                   # bumped by every step(): cache key for packed weights
+        self.guard = None                     # enable_guard(): the device-side step guard (skip non-finite, clip by global norm)
 
     def enable_bf16_shadow(self):
         if self.shadow is None:
             self.shadow = self.flat_p.to(torch.bfloat16)
         return self.shadow
+
+    # ---- step guard (csrc/optim.hip: vqk_step_guard / vqk_adamw_guarded): GradScaler's "leave out a step whose gradients hold an
+    # Inf / NaN" and clip_grad_norm_'s global-norm clipping, decided and obeyed on the device.  Off unless enabled: without a guard
+    # step() issues the launches it always did.
+    def enable_guard(self, skip_nonfinite: bool = True, max_grad_norm: float | None = None) -> None:
+        """Allocate the guard's device blocks (outside any capture).  ``max_grad_norm`` None: no clipping."""
+        skip_nonfinite, max_grad_norm = check_guard_settings(skip_nonfinite, max_grad_norm)
+        settings = (skip_nonfinite, max_grad_norm)
+        if self.guard is not None:
+            if self.guard['settings'] == settings:
+                return
+            if self.guard['steps']:
+                raise RuntimeError('FlatAdamW.enable_guard: the guard has taken a step with other settings '
+                                   f'{self.guard["settings"]}; call disable_guard() first')
+        if not self.flat_p.is_cuda:
+            raise RuntimeError('vqk: FlatAdamW.enable_guard runs on the GPU only (HIP kernels, no CPU fallback)')
+        from . import ops
+        from .scalarlog import build_seg_group
+        dev = self.flat_g.device
+        b1, b2 = self.param_groups[0]['betas']
+        self.guard = dict(settings=settings, steps=0, hint=None,
+                          seg_group=torch.tensor(build_seg_group(self, {id(p): 0 for p in self._params_in_order()}),
+                                                 dtype=torch.int32, device=dev),
+                          ws=torch.empty(ops.arena_stats_ws_doubles(self.flat_g.numel(), 1), dtype=torch.float64, device=dev),
+                          out=torch.zeros(2 * 3, dtype=torch.float64, device=dev),
+                          state=torch.tensor(GUARD_STATE_INIT, dtype=torch.float64, device=dev),
+                          ctrl=torch.zeros(4, dtype=torch.int32, device=dev),
+                          bias=bias_table(b1, b2).to(dev), betas=(float(b1), float(b2)))
+        self._guard_set_applied(self.step_count)
+
+    def disable_guard(self) -> None:
+        if self.guard is not None:
+            self.step_count = self.applied_steps()
+            self.guard = None
+
+    def guard_state(self) -> dict | None:
+        """the state block as a dict (synchronises: epoch ends and checkpoints only); None without a guard"""
+        return None if self.guard is None else guard_state_dict(self.guard['state'].tolist())
+
+    def guard_epoch_end(self, name: str) -> dict | None:
+        """at an epoch end (synchronises): the epoch's ``guard/<name>/*`` values; the longest skip run restarts from the current
+        one and the smallest coefficient from 1.  None without a guard."""
+        if self.guard is None:
+            return None
+        now = self.guard_state()
+        rec = guard_epoch_record(name, now, self.guard.get('epoch_start'))
+        st = self.guard['state']
+        st[GUARD_MAX_SKIP_RUN:GUARD_MAX_SKIP_RUN + 1].copy_(st[GUARD_SKIP_RUN:GUARD_SKIP_RUN + 1])
+        st[GUARD_COEF_MIN:GUARD_COEF_MIN + 1].fill_(1.0)
+        self.guard['epoch_start'] = now
+        return rec
+
+    def applied_steps(self) -> int:
+        """optimizer steps really taken: the device's count with a guard (synchronises), ``step_count`` without"""
+        return self.step_count if self.guard is None else int(self.guard['state'][GUARD_APPLIED].item())
+
+    def _guard_set_applied(self, n: int) -> None:
+        self.guard['state'][GUARD_APPLIED:GUARD_APPLIED + 1].fill_(float(n))
+
+    def offer_grad_stats(self, row: torch.Tensor, scale: float) -> None:
+        """``ScalarLog.grad_stats`` just read the whole arena at ``scale``: ``row`` is its "all groups" {sum x^2, max |x|,
+        nonfinite}.  The next ``step()`` takes its verdict from it instead of reading the arena again -- if nothing stepped in
+        between and the scale is still the optimizer's."""
+        if self.guard is not None:
+            self.guard['hint'] = (row, float(scale), self.generation, torch.cuda.current_stream().cuda_stream)
+
+    def _guarded_step(self, g0, b1, b2):
+        from . import ops
+        gd = self.guard
+        if (float(b1), float(b2)) != gd['betas']:
+            raise RuntimeError('FlatAdamW: betas changed after enable_guard(); call disable_guard() / enable_guard() again')
+        stream = torch.cuda.current_stream().cuda_stream
+        hint, gd['hint'] = gd['hint'], None
+        if hint is not None and hint[1:] == (float(self.grad_scale), self.generation, stream):
+            row = hint[0]
+        else:
+            ops.arena_stats(self.flat_g, self.seg_end, gd['seg_group'], 1, float(self.grad_scale), gd['ws'], gd['out'])
+            row = gd['out'][3:6]
+        skip, max_norm = gd['settings']
+        lib = _native.lib()
+        _native.check(lib.vqk_step_guard(row.data_ptr(), int(skip), 0.0 if max_norm is None else float(max_norm), float(g0['lr']),
+                                         float(self.grad_scale), gd['bias'].data_ptr(), gd['bias'].shape[0],
+                                         gd['state'].data_ptr(), gd['ctrl'].data_ptr(), stream), 'step_guard')
+        gd['steps'] += 1
+        return lib.vqk_adamw_guarded(self.flat_p.data_ptr(), self.flat_g.data_ptr(),
+                                     0 if self.flat_m is None else self.flat_m.data_ptr(), self.flat_v.data_ptr(),
+                                     self.flat_p.numel(), self.seg_end.data_ptr(), self.seg_wd.data_ptr(),
+                                     self.seg_end.numel(), float(g0['lr']), float(b1), float(b2), float(g0['eps']),
+                                     gd['ctrl'].data_ptr(), 0 if self.shadow is None else self.shadow.data_ptr(), stream)
+
+    # MiniTrainer._snapshot / _restore: the settling steps of a capture leave nothing behind
+    def guard_snapshot(self):
+        return None if self.guard is None else (self.guard['state'].clone(), self.guard['ctrl'].clone(), self.guard['steps'])
+
+    def guard_restore(self, snap) -> None:
+        if self.guard is not None and snap is not None:
+            self.guard['state'].copy_(snap[0])
+            self.guard['ctrl'].copy_(snap[1])
+            self.guard['steps'] = snap[2]
+            self.guard['hint'] = None
 
     # ---- checkpoint format: the same layout ``torch.optim.AdamW.state_dict()`` produces (what Lightning stores under
     # 'optimizer_states', vqvae/train.py:121-122), so optimizer states move between the reference and this build
@@ -150,11 +302,12 @@ class FlatAdamW(torch.optim.Optimizer):
     def state_dict(self):
         state, idx = {}, 0
         groups = []
+        step_count = self.applied_steps()      # with a guard: the steps really taken, read from the device
         for g in self.param_groups:
             ids = []
             for p in g['params']:
                 off, n = self.offsets[id(p)], p.numel()
-                entry = {'step': torch.tensor(float(self.step_count)),
+                entry = {'step': torch.tensor(float(step_count)),
                          'exp_avg_sq': self._logical(self.flat_v[off:off + n], p).clone()}
                 entry['exp_avg'] = (self._logical(self.flat_m[off:off + n], p).clone() if self.flat_m is not None
                                     else torch.zeros_like(p, memory_format=torch.contiguous_format))
@@ -205,6 +358,8 @@ class FlatAdamW(torch.optim.Optimizer):
                     src = src.permute(0, 2, 3, 1)
                 buf[off:off + n].copy_(src.reshape(-1))
             self.step_count = int(float(st['step']))
+        if self.guard is not None:
+            self._guard_set_applied(self.step_count)
 
     def zero_grad(self, set_to_none: bool = False):
         self.flat_g.zero_()
@@ -262,7 +417,7 @@ class FlatAdamW(torch.optim.Optimizer):
             raise RuntimeError('vqk: FlatAdamW.step runs on the GPU only (HIP kernel, no CPU fallback)')
         from . import ops
         with ops.trace_range('vqk::FlatAdamW.step'):
-            st = self._launch_adamw(g0, b1, b2)
+            st = self._launch_adamw(g0, b1, b2) if self.guard is None else self._guarded_step(g0, b1, b2)
         _native.check(st, 'adamw')
         self.generation += 1
         with ops.trace_range('vqk::repack_owned'):

@@ -223,18 +223,22 @@ class ScalarLog:
             return
         self._accumulate('validation', [(k, v) for k, v in logged.items() if k.startswith('validation/')], int(batch_size))
 
-    def grad_stats(self, opt, name: str) -> None:
+    def grad_stats(self, opt, name: str):
         """between the gradient all-reduce and ``opt.step()``, on the stream the step uses: the arena's statistics at the
-        optimizer's ``grad_scale`` into the epoch accumulators (every ``grad_stats_every``-th call per optimizer)"""
+        optimizer's ``grad_scale`` into the epoch accumulators (every ``grad_stats_every``-th call per optimizer).  Returns the
+        device row {sum x^2, max |x|, nonfinite} over ALL groups when the pass ran (the groups cover every parameter segment:
+        ``build_seg_group`` refuses anything else) -- what the optimizer's step guard decides on -- else None."""
         if self.paused or not self.grad_stats_every:
-            return
+            return None
         from . import ops
         st = self._opt_state(opt, name)
         st['calls'] += 1
         if (st['calls'] - 1) % self.grad_stats_every:
-            return
+            return None
         ops.arena_stats(opt.flat_g, opt.seg_end, st['seg_group'], len(st['names']), float(opt.grad_scale), st['ws'], st['out'],
                         self._grad_acc(st))
+        g = len(st['names'])
+        return st['out'][3 * g:3 * g + 3]
 
     def step_event(self, global_step: int, epoch: int, lr: float, extras: dict | None = None) -> dict | None:
         """after optimizer step number ``global_step`` (1-based count of finished steps): host floats only"""

@@ -105,6 +105,12 @@ def parse_args(argv=None):
     p.add_argument('--log_every_n_steps', type=int, default=50, help="scalar log: a 'step' record (lr, Gumbel schedule) every n-th optimizer step")
     p.add_argument('--grad_stats_every', type=int, default=1,
                    help='scalar log: gradient norm / max / non-finite count of every N-th optimizer step (0: off)')
+    p.add_argument('--skip_nonfinite_steps', action='store_true',
+                   help="leave out every optimizer step whose gradients hold an Inf / NaN, per optimizer, without advancing its "
+                        "step count (what GradScaler does under the reference's precision='16-mixed'); decided on the device")
+    p.add_argument('--gradient_clip_val', type=float, default=None,
+                   help="Lightning's gradient_clip_val: scale the gradients of each optimizer so that their global 2-norm is at "
+                        "most this (torch.nn.utils.clip_grad_norm_); omitted: no clipping")
     p.add_argument('--run_name', type=str, default='run')
     p.add_argument('--seed', type=int, required=True)
     p.add_argument('--loading_path', type=str, default=None, help='checkpoint to resume from')
@@ -212,6 +218,8 @@ def main(argv=None):
     trainer = trainer_mod.MiniTrainer(max_epochs=max_epochs, num_training_batches=len(batches),
                                       deterministic=True if args.deterministic else None)
     trainer.attach(model)
+    if args.skip_nonfinite_steps or args.gradient_clip_val is not None:      # before the capture: the guard allocates
+        trainer.enable_guards(args.skip_nonfinite_steps, args.gradient_clip_val)
     start_epoch = 0
     if args.loading_path is not None:
         ckpt = trainer.load_checkpoint(model, args.loading_path, strict=False)
@@ -245,7 +253,13 @@ def main(argv=None):
                 print(f'[epoch {epoch}] ' + ' '.join(f'{k} {v:.6f}' for k, v in sorted(logged.items())), flush=True)
         model.flush_image_log()
         importlib.import_module(PKG + '.ops').check_kernel_health()       # a kernel that gave up on a rendezvous = untrustworthy gradients: stop
-        epoch_rec = trainer.log_train_epoch(model)                        # None without --log_dir
+        guard_rec = trainer.guard_epoch_end(model)                        # {} without a guard; stops a run that skips every step
+        for name in trainer.OPTIMIZER_NAMES:
+            skipped, clipped = guard_rec.get(f'guard/{name}/skipped', 0), guard_rec.get(f'guard/{name}/clipped', 0)
+            if rank == 0 and (skipped or clipped):
+                print(f'[epoch {epoch}] {name}: {skipped} steps skipped (non-finite gradients), {clipped} clipped, '
+                      f'{guard_rec[f"guard/{name}/applied"]} applied', flush=True)
+        epoch_rec = trainer.log_train_epoch(model, guard_rec)             # None without --log_dir
         if rank == 0 and epoch_rec is not None:                           # the epoch means, as the log file holds them
             means = {k: v for k, v in epoch_rec.items() if k.startswith('train/') or k in ('g_weight', 'r1_penalty')}
             print(f'[epoch {epoch}] ' + ' '.join(f'{k} {v:.6f}' for k, v in sorted(means.items())), flush=True)

@@ -117,7 +117,9 @@ class MiniTrainer:
         log = self._slog(model)
         if log is not None:
             self._slog_groups(model, log)
-            log.grad_stats(opt, name)
+            row = log.grad_stats(opt, name)
+            if row is not None and opt.guard is not None:
+                opt.offer_grad_stats(row, opt.grad_scale)      # one statistics pass per step: the guard decides on this row
 
     def _log_step(self, model) -> None:
         """after a finished step (``global_step`` already counts it)"""
@@ -128,10 +130,34 @@ class MiniTrainer:
             log.step_event(self.global_step, model.current_epoch, self.optimizers[0].param_groups[0]['lr'],
                            {k: model.logged[k] for k in STEP_EXTRA_KEYS if k in model.logged})
 
-    def log_train_epoch(self, model) -> dict | None:
-        """at the end of a training epoch (the one host synchronisation of the log): the written ``train_epoch`` record"""
+    def log_train_epoch(self, model, extras: dict | None = None) -> dict | None:
+        """at the end of a training epoch (the one host synchronisation of the log): the written ``train_epoch`` record;
+        ``extras``: further keys of the record (``guard_epoch_end``'s)"""
         log = self._slog(model)
-        return None if log is None else log.epoch_end('train_epoch', model.current_epoch, self.global_step)
+        return None if log is None else log.epoch_end('train_epoch', model.current_epoch, self.global_step, extras or None)
+
+    OPTIMIZER_NAMES = ('autoencoder', 'discriminator')
+
+    def enable_guards(self, skip_nonfinite: bool, max_grad_norm: float | None) -> None:
+        """the step guard on every optimizer (before a capture: it allocates)"""
+        for o in self.optimizers:
+            o.enable_guard(skip_nonfinite=skip_nonfinite, max_grad_norm=max_grad_norm)
+
+    def guard_epoch_end(self, model) -> dict:
+        """at the end of a training epoch, where the run synchronises already: every guarded optimizer's ``guard/<name>/*`` values
+        of the epoch ({} without a guard).  Raises when an optimizer was stepped and every one of its steps was skipped: training
+        on from there moves nothing."""
+        out = {}
+        for name, o in zip(self.OPTIMIZER_NAMES, self.optimizers):
+            rec = o.guard_epoch_end(name)
+            if rec is None:
+                continue
+            out.update(rec)
+            if rec[f'guard/{name}/skipped'] > 0 and rec[f'guard/{name}/applied'] == 0:
+                raise RuntimeError(f'step guard: every one of the {rec[f"guard/{name}/skipped"]} {name} optimizer steps of epoch '
+                                   f'{model.current_epoch} had non-finite gradients and was skipped; last gradient norm '
+                                   f'{o.guard_state()["last_norm"]}')
+        return out
 
     @contextlib.contextmanager
     def _scalar_log_deferred(self, model):
@@ -433,6 +459,7 @@ class MiniTrainer:
     def _snapshot(self, model):
         return dict(state={k: v.detach().clone() for k, v in model.state_dict().items()},
                     opts=[(o.flat_v.clone(), None if o.flat_m is None else o.flat_m.clone(), o.step_count) for o in self.optimizers],
+                    guards=[o.guard_snapshot() for o in self.optimizers],
                     usage=(None if getattr(model, 'train_epoch_usage_count', None) is None else model.train_epoch_usage_count.clone()),
                     step=self.global_step,
                     # the settling steps draw Gumbel noise / augmentation boxes and log: neither may leak into the run
@@ -445,11 +472,12 @@ class MiniTrainer:
         own = model.state_dict()
         for k, v in snap['state'].items():
             own[k].copy_(v)                                          # in place: parameters stay views of the flat arena
-        for o, (v, m, n) in zip(self.optimizers, snap['opts']):
+        for o, (v, m, n), guard in zip(self.optimizers, snap['opts'], snap.get('guards') or [None] * len(self.optimizers)):
             o.flat_v.copy_(v)
             if m is not None:
                 o.flat_m.copy_(m)
             o.step_count = n
+            o.guard_restore(guard)
             o.generation += 1
             ops.repack_owned(o)
             if o.shadow is not None:
