@@ -148,6 +148,31 @@ int vqk_vq_backward_f32(const float* z, const float* e, const int64_t* idx, cons
 int vqk_vq_backward_fused_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype,
                               int64_t n, int k, int d, float cz, float ce, const float* gscale_dev, float* dz, float* de,
                               void* stream);
+/* ---------------------------------------------------------------- finite scalar quantizer ---------
+ * Mentzer et al. 2023 (csrc/fsq.hip).  z[N][D] fp32 rows, w_in[d][D], b_in[d], w_out[D][d], b_out[D] fp32; levels: d ints on the HOST
+ * (they travel by value in the launch arguments).  u = W_in z + b_in; half_l = (L - 1)(1 + 1e-3) / 2, offset = 0.5 for an even L, shift =
+ * atanh(offset / half_l); bounded = tanh(u + shift) half_l - offset; r = rint(bounded); idx = sum_j (r_j + L_j / 2) basis_j with basis =
+ * (1, L_1, L_1 L_2, ...); q = W_out (r / (L / 2)) + b_out.  Served: 4 <= D <= 1024, D % 4 == 0, 1 <= d <= 8, every level >= 2, prod(levels)
+ * < 2^31 (VQK_ERR_SHAPE otherwise); z, q, q_lo, dq, dz and ws 16-byte aligned, the parameters need no alignment.  No call allocates
+ * or synchronises.
+ * forward: ONE launch; idx[N]; u[N][d] (optional: what the backward needs); q as fp32 (q) and / or bf16 (q_lo), both optional;
+ * hist[idx] += 1 (int32 [prod(levels)], optional, pre-zeroed by the caller). */
+int vqk_fsq_forward(const float* z, const float* w_in, const float* b_in, const float* w_out, const float* b_out, int64_t n,
+                    int dm, int d, const int32_t* levels, int64_t* idx, float* u /* optional */, float* q /* optional */,
+                    void* q_lo /* optional */, int32_t* hist /* optional */, void* stream);
+/* idx[N] -> q (fp32 and / or bf16): the digits by integer arithmetic on the index -- no table, an index outside [0, prod(levels)) reads
+ * nothing out of bounds -- through the forward's own device function: the same bits of q for the same index. */
+int vqk_fsq_decode(const int64_t* idx, const float* w_out, const float* b_out, int64_t n, int dm, int d, const int32_t* levels,
+                   float* q /* optional */, void* q_lo /* optional */, void* stream);
+/* Straight-through backward from dq (fp32 or bf16: dq_dtype) and the forward's u: dz[N][D] and the four parameter gradients
+ * (accumulate = 1: added to what the targets hold).  The parameter gradients are sums over the N rows in an order that depends on
+ * (n, D, d) only -- registers per lane, the waves of a block through LDS in wave order, one slab per block in ws, a second launch
+ * that adds the slabs in an order fixed by their count: no atomics, the same bits every run.  ws: >= vqk_fsq_backward_ws_bytes(n, D, d) bytes
+ * (VQK_ERR_WORKSPACE); that function returns VQK_ERR_SHAPE for an unserved (D, d). */
+int64_t vqk_fsq_backward_ws_bytes(int64_t n, int dm, int d);
+int vqk_fsq_backward(const float* z, const float* u, const void* dq, int dq_dtype, const float* w_in, const float* w_out, int64_t n,
+                     int dm, int d, const int32_t* levels, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out,
+                     int accumulate, void* ws, int64_t ws_bytes, void* stream);
 /* EMA statistics (vector_quantizers.py:159-169): counts[k] += 1, dw[idx] += z (both pre-zeroed) ...  fp32 atomics in arrival order;
  * in deterministic mode (this entry and the fused one): one block per code adds its rows in row order, no atomics -- the same bits every run. */
 int vqk_ema_stats_f32(const float* z, const int64_t* idx, int64_t n, int k, int d,

@@ -1,0 +1,203 @@
+"""The finite scalar quantizer without a GPU: the float64 reference (tests/fsq_reference.py) against torch.autograd on a float64
+transcription of the specification, the token arithmetic, the input generator, ``FSQuantizer`` / ``VQVAE`` construction on the CPU, the
+shipped config, and the argument validation of the three entry points.
+
+Bound of the reference check: both sides are float64 (unit roundoff 1.1e-16); the sums run over at most 64 rows of O(1) terms and
+the two formulations differ only in association -- below 1e-13 relative to the largest element.  rtol = 1e-10 (on the max-abs metric
+of the GPU tests) leaves three decades and is five decades below anything a float32 slip or a wrong term would show."""
+import ctypes
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import fsq_reference as R
+
+PKG = 'vqvae-vqgan-pytorch-lightning_amd'
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LEVEL_SETS = [[3, 3], [2, 2, 2], [8, 5, 5, 5], [7, 5, 5, 5, 5], [8, 8, 8, 6, 5]]
+
+AE = dict(channels=32, num_res_blocks=1, channel_multipliers=(1, 2))
+TC = dict(lr=1e-4, betas=(0.0, 0.99), eps=1e-8, weight_decay=1e-4, warmup_epochs=None, decay_epochs=None)
+
+
+def q_conf(levels=(8, 5, 5, 5), k=1000, dim=64, reinit=None):
+    return dict(num_embeddings=k, embedding_dim=dim, reinit_every_n_epochs=reinit, type='fsq', params=dict(levels=list(levels)))
+
+
+# ---------------------------------------------------------------------------------------------- reference vs torch.autograd
+class _RoundSTE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return torch.round(x)                       # ties to even, like rint
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+@pytest.mark.parametrize('levels,d_model', [([8, 5, 5, 5], 32), ([2], 8), ([2, 3, 4, 5, 6, 7, 8, 9], 20), ([3, 3], 64)])
+def test_reference_backward_matches_autograd(levels, d_model):
+    inp = R.make_inputs(5, 64, d_model, levels)
+    t = {k: torch.tensor(inp[k], dtype=torch.float64, requires_grad=k != 'dq') for k in ('z', 'w_in', 'b_in', 'w_out', 'b_out', 'dq')}
+    half_l, offset, shift, half_width, _ = (torch.tensor(c) for c in R.consts(levels))
+    u = t['z'] @ t['w_in'].T + t['b_in']
+    bounded = torch.tanh(u + shift) * half_l - offset
+    c = _RoundSTE.apply(bounded) / half_width
+    q = c @ t['w_out'].T + t['b_out']
+    q.backward(t['dq'])
+    fwd = R.forward(*(inp[k] for k in ('z', 'w_in', 'b_in', 'w_out', 'b_out')), levels)
+    assert R.distance(fwd['q'], q.detach().numpy()) <= 1e-10
+    ref = R.backward(*(inp[k] for k in ('z', 'w_in', 'b_in', 'w_out', 'b_out', 'dq')), levels)
+    for name, key in (('dz', 'z'), ('dw_in', 'w_in'), ('db_in', 'b_in'), ('dw_out', 'w_out'), ('db_out', 'b_out')):
+        assert R.distance(ref[name], t[key].grad.numpy()) <= 1e-10, name
+
+
+# ---------------------------------------------------------------------------------------------- tokens
+@pytest.mark.parametrize('levels', LEVEL_SETS)
+def test_indices_and_codes_are_a_bijection(levels):
+    k = int(np.prod(levels))
+    idx = np.arange(k)
+    codes = R.indices_to_codes(idx, levels)
+    lv = np.asarray(levels)
+    assert codes.shape == (k, len(levels)) and (codes >= -(lv // 2)).all() and (codes <= lv - 1 - lv // 2).all()
+    assert len({tuple(row) for row in codes.tolist()}) == k                   # distinct code vectors
+    np.testing.assert_array_equal(R.codes_to_indices(codes, levels), idx)
+    cb = R.implicit_codebook(levels)
+    np.testing.assert_array_equal(cb, codes / (lv // 2))
+    assert np.abs(cb).max() <= 1.0
+
+
+@pytest.mark.parametrize('levels,d_model', [([2], 20), ([3, 3], 64), ([8, 5, 5, 5], 256), ([2, 3, 4, 5, 6, 7, 8, 9], 64)])
+def test_generator_indices_in_range_and_off_the_boundaries(levels, d_model):
+    inp = R.make_inputs(1, 512, d_model, levels)
+    f64 = R.forward(*(inp[k] for k in ('z', 'w_in', 'b_in', 'w_out', 'b_out')), levels)
+    assert f64['idx'].min() >= 0 and f64['idx'].max() < int(np.prod(levels))
+    assert R.boundary_distance(f64['bounded']).min() >= 1e-3
+    assert inp['resampled'] <= 0.1
+    np.testing.assert_array_equal(R.indices_to_codes(f64['idx'], levels), f64['r'].astype(np.int64))
+    # the float32 evaluation is far inside the margin and lands on the same tokens
+    f32 = R.forward(*(inp[k] for k in ('z', 'w_in', 'b_in', 'w_out', 'b_out')), levels, dtype=np.float32)
+    assert np.abs(f32['bounded'] - f64['bounded']).max() <= 1e-4
+    np.testing.assert_array_equal(f32['idx'], f64['idx'])
+
+
+# ---------------------------------------------------------------------------------------------- module and model on the CPU
+def test_constructor_validation():
+    vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
+    with pytest.raises(ValueError, match='prod'):
+        vqm.FSQuantizer(1024, 64, [8, 5, 5, 5])
+    with pytest.raises(ValueError, match='between 1 and 8'):
+        vqm.FSQuantizer(512, 64, [2] * 9)
+    with pytest.raises(ValueError, match='between 1 and 8'):
+        vqm.FSQuantizer(1, 64, [])
+    with pytest.raises(ValueError, match='>= 2'):
+        vqm.FSQuantizer(25, 64, [5, 1, 5])
+
+
+def test_module_state_and_implicit_codebook():
+    vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
+    ae = importlib.import_module(PKG + '.modules.autoencoder')
+    q = vqm.FSQuantizer(1000, 64, [8, 5, 5, 5])
+    assert set(q.state_dict()) == {'codebook.weight', 'project_in.weight', 'project_in.bias', 'project_out.weight', 'project_out.bias'}
+    assert isinstance(q.project_in, ae.Conv2d) and isinstance(q.project_out, ae.Conv2d)
+    assert tuple(q.project_in.weight.shape) == (4, 64, 1, 1) and tuple(q.project_out.weight.shape) == (64, 4, 1, 1)
+    assert tuple(q.codebook.weight.shape) == (1000, 4) and not q.codebook.weight.requires_grad
+    np.testing.assert_array_equal(q.codebook.weight.numpy(), R.implicit_codebook([8, 5, 5, 5], np.float32))
+    with torch.no_grad():
+        q.codebook.weight.zero_()
+    q.init_codebook()                                                        # writes the implicit rows, not noise
+    np.testing.assert_array_equal(q.codebook.weight.numpy(), R.implicit_codebook([8, 5, 5, 5], np.float32))
+    with pytest.raises(RuntimeError, match='no learned codebook'):
+        q.reinit_unused_codes(torch.ones(1000))
+    with pytest.raises(RuntimeError, match='GPU only'):
+        q(torch.zeros(1, 64, 2, 2))
+
+
+def test_model_builds_and_groups_parameters():
+    model_mod = importlib.import_module(PKG + '.model')
+    m = model_mod.VQVAE(32, AE, q_conf(), None, TC)
+    assert type(m.quantizer).__name__ == 'FSQuantizer' and m.encoder.conv_out.out_channels == 64
+    keys = {k for k in m.state_dict() if k.startswith('quantizer.')}
+    assert keys == {'quantizer.codebook.weight', 'quantizer.project_in.weight', 'quantizer.project_in.bias',
+                    'quantizer.project_out.weight', 'quantizer.project_out.bias'}
+    decay, no_decay = ({n for n, _ in grp} for grp in m.optimizer_groups())
+    assert {'quantizer.project_in.weight', 'quantizer.project_out.weight'} <= decay
+    assert {'quantizer.project_in.bias', 'quantizer.project_out.bias'} <= no_decay
+    assert 'quantizer.codebook.weight' not in decay | no_decay                # frozen: not handed to the optimizer
+    np.testing.assert_array_equal(m.quantizer.codebook.weight.numpy(), R.implicit_codebook([8, 5, 5, 5], np.float32))
+    with pytest.raises(ValueError, match='reinit_every_n_epochs'):
+        model_mod.VQVAE(32, AE, q_conf(reinit=10), None, TC)
+    with pytest.raises(ValueError, match='prod'):
+        model_mod.VQVAE(32, AE, q_conf(k=1024), None, TC)
+
+
+def test_shipped_config():
+    train = importlib.import_module(PKG + '.train')
+    model_mod = importlib.import_module(PKG + '.model')
+    conf = train.get_model_conf(os.path.join(ROOT, 'example_confs', 'fsq_vqvae.yaml'))
+    q = conf['quantizer']
+    assert (q['type'], q['num_embeddings'], q['embedding_dim'], q['reinit_every_n_epochs']) == ('fsq', 1000, 256, None)
+    assert q['params'] == dict(levels=[8, 5, 5, 5])
+    std = train.get_model_conf(os.path.join(ROOT, 'example_confs', 'standard_vqvae.yaml'))
+    assert conf['autoencoder'] == std['autoencoder'] and conf['training'] == std['training'] and conf['image_size'] == std['image_size']
+    run = train.derive_run_config(conf, 8, {'autoencoder.channels': 32, 'quantizer.params.levels': [3, 3], 'quantizer.num_embeddings': 9})
+    assert run['batch_size_per_device'] == 32 and run['l_conf'] is None
+    m = model_mod.VQVAE(run['image_size'], run['ae_conf'], run['q_conf'], run['l_conf'], run['t_conf'])
+    assert m.quantizer.levels == (3, 3) and type(m.criterion).__name__ == 'MSELoss'
+
+
+# ---------------------------------------------------------------------------------------------- the entry points, no device
+def _lv(*levels):
+    return (ctypes.c_int32 * 8)(*levels)
+
+
+def test_entry_points_validate_without_gpu():
+    native = importlib.import_module(PKG + '._native')
+    native.build()
+    lib = native.lib()
+    for name in ('vqk_fsq_forward', 'vqk_fsq_backward', 'vqk_fsq_decode', 'vqk_fsq_backward_ws_bytes'):
+        assert hasattr(lib, name) and name in native.EXPORTS
+    ok = _lv(8, 5, 5, 5)
+    p = 4096                                                  # a non-NULL, 16-byte aligned address: validation never dereferences it
+
+    def fwd(dm=256, d=4, lv=ok, z=p):
+        return lib.vqk_fsq_forward(z, p, p, p, p, 16, dm, d, lv, p, p, p, 0, p, 0)
+
+    def bwd(dm=256, d=4, lv=ok, z=p, dtype=0, ws_bytes=1 << 30):
+        return lib.vqk_fsq_backward(z, p, p, dtype, p, p, 16, dm, d, lv, p, p, p, p, p, 0, p, ws_bytes, 0)
+
+    def dec(dm=256, d=4, lv=ok, idx=p):
+        return lib.vqk_fsq_decode(idx, p, p, 16, dm, d, lv, p, 0, 0)
+
+    for fn in (fwd, bwd, dec):
+        assert fn(dm=6) == -1 and fn(dm=1028) == -1 and fn(dm=0) == -1       # D % 4, D > 1024
+        assert fn(d=0) == -1 and fn(d=9) == -1
+        assert fn(lv=_lv(8, 1, 5, 5)) == -1                                  # a level of 1
+        assert fn(d=8, lv=_lv(*[64] * 8)) == -1                              # prod(levels) >= 2^31
+        assert fn(lv=None) == -5
+    assert fwd(z=0) == -5 and bwd(z=0) == -5 and dec(idx=0) == -5            # NULL pointers
+    assert fwd(z=p + 4) == -3 and bwd(z=p + 4) == -3                         # alignment
+    assert bwd(dtype=7) == -2
+    assert lib.vqk_fsq_forward(p, p, p, 0, 0, 16, 256, 4, ok, p, 0, p, 0, 0, 0) == -5     # q asked for without W_out
+    assert lib.vqk_fsq_decode(p, p, p, 16, 256, 4, ok, 0, 0, 0) == -5                     # no output
+    assert lib.vqk_fsq_backward_ws_bytes(16, 6, 4) == -1 and lib.vqk_fsq_backward_ws_bytes(16, 256, 9) == -1
+    need = lib.vqk_fsq_backward_ws_bytes(8192, 256, 4)
+    assert need > 0 and need % 16 == 0
+    assert lib.vqk_fsq_backward_ws_bytes(8192, 256, 4) == need               # a function of the shape only
+    assert lib.vqk_fsq_backward_ws_bytes(1, 256, 4) < need <= lib.vqk_fsq_backward_ws_bytes(1 << 20, 256, 4)
+    assert bwd(ws_bytes=lib.vqk_fsq_backward_ws_bytes(16, 256, 4) - 4) == -6
+    assert bwd(ws_bytes=-1) == -5
+
+
+def test_launchers_refuse_cpu_tensors():
+    ops = importlib.import_module(PKG + '.ops')
+    w_in, b_in, w_out, b_out = torch.zeros(4, 64), torch.zeros(4), torch.zeros(64, 4), torch.zeros(64)
+    with pytest.raises(RuntimeError, match='GPU only'):
+        ops.FSQFn.apply(torch.zeros(1, 64, 2, 2), w_in, b_in, w_out, b_out, (8, 5, 5, 5), torch.float32)
+    with pytest.raises(RuntimeError, match='GPU only'):
+        ops.fsq_assign(torch.zeros(4, 64), w_in, b_in, (8, 5, 5, 5))
+    with pytest.raises(RuntimeError, match='GPU only'):
+        ops.fsq_decode(torch.zeros(4, dtype=torch.int64), w_out, b_out, (8, 5, 5, 5))

@@ -27,7 +27,7 @@ from torch import nn
 from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
-from .modules.vector_quantizers import (EMAVectorQuantizer, EntropyVectorQuantizer, GumbelVectorQuantizer,
+from .modules.vector_quantizers import (EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer,
                                         VectorQuantizer)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
@@ -120,6 +120,10 @@ class VQVAE(BaseVQVAE, _LightningBase):
             self.kl_warmup_epochs = qp.get('kl_warmup_epochs')
             self.temp_decay_epochs = qp.get('temp_decay_epochs')
             self.temp_final = qp.get('temp_final')
+        elif qt == 'fsq':
+            if self.reinit_every_n_epochs is not None:
+                raise ValueError('fsq has no learned codebook: reinit_every_n_epochs must be empty')
+            self.quantizer = FSQuantizer(self.cb_size, self.latent_dim, qp['levels'])
         else:
             raise ValueError(f'unrecognized quantizer: {qt}')
 

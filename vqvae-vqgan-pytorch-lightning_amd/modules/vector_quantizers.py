@@ -1,11 +1,14 @@
 """Quantizers on the vqk kernels; same classes / ctor signatures / return conventions as the reference's
 ``vqvae/modules/vector_quantizers.py`` (VectorQuantizer :8-84, EMAVectorQuantizer :87-203,
-EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274).
+EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274); ``FSQuantizer`` (finite scalar quantization, no counterpart in
+the reference) is the fifth member of the family.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
 indices are bit-exact.  The EMA statistics are all-reduced over the data-parallel
 ranks (a capability the reference lacks -- its ranks silently diverge)."""
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -177,3 +180,69 @@ class GumbelVectorQuantizer(BaseVectorQuantizer):
         noise = torch.empty_like(lg).exponential_()
         _, idx, _, _ = ops.GumbelVQFn.apply(lg, self.codebook.weight, noise, 1.0, 0.0, True, self.compute_dtype)
         return idx
+
+
+class FSQuantizer(BaseVectorQuantizer):
+    """Finite scalar quantization (Mentzer et al. 2023): the D-channel latent is projected to ``len(levels)`` channels, each is
+    tanh-bounded and rounded to one of its ``levels[j]`` integer values, the mixed-radix number of the rounded vector is the
+    token, and the rounded vector is projected back to D channels.  No learned codebook, no latent loss, no dead codes, no
+    statistics to all-reduce; training and evaluation behave the same.  One fused kernel each way (csrc/fsq.hip): the two 1x1
+    projections are ``Conv2d`` modules for their parameters (names, initialisation, weight-decay group) only -- the kernels read
+    their [d, D] / [D, d] weight memory directly.  ``codebook`` holds the IMPLICIT codebook, frozen: row i = the rounded vector
+    of token i, scaled to [-1, 1]."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, levels):
+        levels = [int(v) for v in levels]
+        if not 1 <= len(levels) <= 8:
+            raise ValueError(f'fsq: between 1 and 8 levels, got {len(levels)}')
+        if any(v < 2 for v in levels):
+            raise ValueError(f'fsq: every level must be >= 2, got {levels}')
+        if math.prod(levels) != num_embeddings:
+            raise ValueError(f'fsq: num_embeddings = {num_embeddings} must equal prod(levels) = {math.prod(levels)}')
+        super().__init__(num_embeddings, len(levels))         # the codebook the base class owns is the implicit one: [K, d], frozen
+        self.embedding_dim = embedding_dim
+        self.codebook.requires_grad_(False)
+        self.levels = tuple(levels)
+        self.project_in = Conv2d(embedding_dim, len(levels), 1, bias=True)
+        self.project_out = Conv2d(len(levels), embedding_dim, 1, bias=True)
+        self.init_codebook()
+
+    def implicit_codebook(self) -> torch.Tensor:
+        """[K, d] fp32: row i = (digit_j(i) - L_j // 2) / (L_j // 2), digit_j the j-th mixed-radix digit of i (first level fastest)"""
+        rem = torch.arange(self.num_embeddings, dtype=torch.int64)
+        cols = []
+        for lv in self.levels:
+            cols.append(((rem % lv) - lv // 2).to(torch.float32) / float(lv // 2))
+            rem = rem // lv
+        return torch.stack(cols, 1)
+
+    @torch.no_grad()
+    def init_codebook(self) -> None:
+        self.codebook.weight.copy_(self.implicit_codebook())
+
+    def _projections(self):
+        return self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias
+
+    def forward(self, x: torch.Tensor):
+        q, idx, loss, hist = ops.FSQFn.apply(x, *self._projections(), self.levels, self.compute_dtype)
+        self.last_hist = hist
+        return q, idx, loss
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.fsq_assign(_flat_view(z), self.project_in.weight, self.project_in.bias, self.levels).view(x.shape[0], -1)
+
+    @torch.no_grad()
+    def get_codebook(self) -> torch.Tensor:
+        """the [K, D] decoder-side vectors: every token decoded"""
+        tokens = torch.arange(self.num_embeddings, dtype=torch.int64, device=self.project_out.weight.device)
+        return ops.fsq_decode(tokens, self.project_out.weight, self.project_out.bias, self.levels)
+
+    @torch.no_grad()
+    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes (B,N) -> (B,N,D), by arithmetic on the token (no [K, D] table is built)"""
+        return ops.fsq_decode(codes, self.project_out.weight, self.project_out.bias, self.levels)
+
+    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
+        raise RuntimeError('fsq: there is no learned codebook to re-initialise')

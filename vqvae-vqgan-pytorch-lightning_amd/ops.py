@@ -2245,4 +2245,5 @@ if TRACE:
 # operator families kept in their own files (this module stays the one import: `ops.VQLookupFn`, `ops.conv_act`, ...)
 # ------------------------------------------------------------------------------------------------------
 from ._ops_vq import *        # noqa: E402,F401,F403  quantizers
+from ._ops_fsq import *       # noqa: E402,F401,F403  finite scalar quantizer
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins
