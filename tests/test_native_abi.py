@@ -52,6 +52,25 @@ def test_stride2_entry_points_validate_without_gpu():
     assert lib.vqk_conv_packed_elems(256, 128, 3, 3) == 256 * 128 * 9            # layout 3: the nine taps, grouped by parity
 
 
+def test_pack_weights_validates_without_gpu():
+    """vqk_conv_pack_weights refuses before any launch: NULL pointers and unknown layouts, tap counts other than 1x1 / 3x3, input
+    channels that are no whole chunks, unknown dtypes, and -- the fragment-major layouts move 16-byte pieces -- misaligned buffers"""
+    lib = importlib.import_module(PKG + '._native').lib()
+    w, out = 0x10000, 0x20000                                                    # never dereferenced: every call below is refused
+    assert lib.vqk_conv_pack_weights(0, out, 1, 128, 64, 3, 0, 1, 0) == -5       # VQK_ERR_ARG
+    assert lib.vqk_conv_pack_weights(w, 0, 1, 128, 64, 3, 0, 1, 0) == -5
+    assert lib.vqk_conv_pack_weights(w, out, 1, 128, 64, 3, 0, 4, 0) == -5       # no layout 4
+    assert lib.vqk_conv_pack_weights(w, out, 1, 128, 64, 2, 0, 1, 0) == -1       # VQK_ERR_SHAPE: ksize 2
+    assert lib.vqk_conv_pack_weights(w, out, 1, 128, 32, 3, 0, 1, 0) == -1       # bf16 chunks are 64 channels
+    assert lib.vqk_conv_pack_weights(w, out, 1, 32, 128, 3, 1, 1, 0) == -1       # (transposed: the chunks are of Cout)
+    assert lib.vqk_conv_pack_weights(w, out, 0, 128, 32, 3, 0, 2, 0) == -1       # the phase operand is bf16, its split form fp32
+    assert lib.vqk_conv_pack_weights(w, out, 1, 128, 64, 3, 0, 6, 0) == -1
+    assert lib.vqk_conv_pack_weights(w, out, 1, 128, 64, 3, 0, 3, 0) == -1       # layout 3 is a data-gradient operand
+    assert lib.vqk_conv_pack_weights(w, out, 7, 128, 64, 3, 0, 1, 0) == -2       # VQK_ERR_DTYPE
+    assert lib.vqk_conv_pack_weights(w + 4, out, 1, 128, 64, 3, 0, 1, 0) == -3   # VQK_ERR_ALIGN
+    assert lib.vqk_conv_pack_weights(w, out + 8, 0, 128, 32, 3, 0, 5, 0) == -3
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     ops = importlib.import_module(PKG + '.ops')

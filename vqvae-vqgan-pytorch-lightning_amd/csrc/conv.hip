@@ -1,19 +1,22 @@
-// Implicit-GEMM convolution for gfx950: fprop (= dgrad with repacked weights) and wgrad, NHWC,
-// bf16 (v_mfma_f32_32x32x16_bf16) and exact fp32 (v_mfma_f32_32x32x2_f32) with fp32 accumulation.
+// Implicit-GEMM convolution for gfx950, forward pass: fprop kernels and their launchers, NHWC, bf16
+// (v_mfma_f32_32x32x16_bf16) and exact fp32 (v_mfma_f32_32x32x2_f32) with fp32 accumulation.  The data gradient is the
+// same kernels on repacked weights (conv_pack.hip builds every weight operand); the weight gradients are in conv_wgrad.hip.
 // Replaces the F.conv2d calls of vqvae/modules/autoencoder.py:57-60, :102-105, :114, :132, :153, :170
 // (3x3 / 1x1, stride 1, 'same' padding) including the nearest x2 upsample of :104-106, which is folded
 // into the input addressing.
 //
-// fprop:  C[M = N*H*W pixels][Cout] = im2col(x)[M][ks*ks*Cin] . W[Cout][ks*ks*Cin]^T
+// conv_fprop_kernel:  C[M = N*H*W pixels][Cout] = im2col(x)[M][ks*ks*Cin] . W[Cout][ks*ks*Cin]^T
 //   block 256 threads = 2x2 waves, tile 128 pixels x 128 couts, K-step = 8 chunks of 16 bytes
 //   (64 bf16 / 32 fp32 channels).  Both tiles are [128 rows][128 B] in LDS, filled by
 //   global_load_lds (16 B per lane, the im2col gather is done by the per-lane SOURCE address; padding
 //   rows read a caller-provided zero page), XOR-swizzled on the source side so that the ds_read_b128
-//   fragment reads are bank-conflict-free.
-// wgrad:  dW[co][tap][ci] = sum_pix dy[pix][co] * x[pix (+) tap][ci]; contraction over pixels, so
-//   both operands are pixel-major in LDS and the bf16 fragments come from ds_read_b64_tr_b16
-//   (hardware transpose read); fp32 fragments are plain ds_read_b32.  Split-K over pixel ranges,
-//   partials combined with fp32 atomics.
+//   fragment reads are bank-conflict-free.  Also serves strided / padded / odd shapes (vqk_conv2d_general) and the parity
+//   classes of the stride-2 data gradient; split-K partials are combined by conv_splitk_epilogue_kernel.
+// conv3x3_halo_kernel / conv3x3_halo_breg_kernel / conv3x3_stream_kernel: 3x3 convs on pixel patches with a halo (weights
+//   staged in LDS / held in registers from the fragment-major operand / a persistent software pipeline over tiles).
+// conv3x3_thin_in_kernel: the 3-channel input conv on the padded 8-channel image.
+// The launchers at the end of the file choose among these and the kernels of conv_mx.hip, conv_x3.hip, conv_thin_f32.hip and
+// conv_edge.hip (vqk_conv_weight_layout tells callers which weight operand the choice wants).
 #include "conv_geom.h"
 #include <type_traits>
 #include <stdlib.h>
@@ -1140,436 +1143,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_thin_in_kernel(const bf16_raw*
     }
 }
 
-// fragment-major weight pack (layout 1).  src w: fp32 [Cout][taps][Cin]; transpose: produce the dgrad operand
-// (roles of Cout/Cin swapped, taps flipped).  dst element order: [cot][cc][tap][ks][kg][co32][EPC] with
-// cc = 64-byte channel chunk (4 x 16 B), ks in {0,1}: channel = ((cc*2 + ks)*2 + kg)*EPC + e.  All 18
-// (tap, ks) fragments of one (cout tile, chunk) are contiguous (18 KiB), which is what one pipeline unit reads.
-template <typename TD>
-__global__ void pack_frag_kernel(const float* __restrict__ w, TD* __restrict__ out, int cout, int cin, int taps,
-                                 int transpose, int cot_tiles) {
-    constexpr int E = Elem<TD>::kPer16B;
-    const int dcout = transpose ? cin : cout, dcin = transpose ? cout : cin;
-    const int ncc = dcin / (4 * E);
-    const int64_t total = (int64_t)cot_tiles * ncc * taps * 2 * 64 * E;
-    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
-        int64_t r = o;
-        const int e = (int)(r % E); r /= E;
-        const int co32 = (int)(r % 32); r /= 32;
-        const int kg = (int)(r % 2); r /= 2;
-        const int ks = (int)(r % 2); r /= 2;
-        const int tap = (int)(r % taps); r /= taps;
-        const int cc = (int)(r % ncc);
-        const int cot = (int)(r / ncc);
-        const int co = cot * 32 + co32;
-        const int ci = ((cc * 2 + ks) * 2 + kg) * E + e;
-        float v = 0.0f;
-        if (co < dcout) {
-            v = transpose ? w[((int64_t)ci * taps + (taps - 1 - tap)) * cin + co]
-                          : w[((int64_t)co * taps + tap) * cin + ci];
-        }
-        Elem<TD>::st(out + o, v);
-    }
-}
-
-// w [Cout][taps][Cin] fp32 -> wt [Cin][taps (flipped)][Cout] as TD
-template <typename TD>
-__global__ void pack_dgrad_kernel(const float* __restrict__ w, TD* __restrict__ wt, int cout, int cin, int taps) {
-    const int64_t total = (int64_t)cout * taps * cin;
-    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
-        // o indexes the destination [ci][tap][co]
-        const int co = (int)(o % cout);
-        const int64_t r = o / cout;
-        const int tap = (int)(r % taps), ci = (int)(r / taps);
-        Elem<TD>::st(wt + o, w[((int64_t)co * taps + (taps - 1 - tap)) * cin + ci]);
-    }
-}
-
-template <typename TD>
-__global__ void cast_kernel(const float* __restrict__ s, TD* __restrict__ d, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        Elem<TD>::st(d + i, s[i]);
-}
-
-// One launch for every conv operand of the model: desc d is packed by blocks (blockIdx.y == d).  The descriptor
-// is eight int64 words {src, dst, dtype, cout, cin, ksize, transpose, layout} with the meaning of the arguments of
-// vqk_conv_pack_weights (src: fp32 [Cout][taps][Cin] master memory, typically a view into the AdamW arena).
-template <typename TD>
-__device__ __forceinline__ void pack_any(const float* __restrict__ w, TD* __restrict__ out, int cout, int cin, int taps,
-                                         int transpose, int layout) {
-    constexpr int E = Elem<TD>::kPer16B;
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    if (layout == 0) {
-        const int64_t total = (int64_t)cout * taps * cin;
-        if (!transpose) {
-            for (int64_t o = tid; o < total; o += nthr) Elem<TD>::st(out + o, w[o]);
-        } else {
-            for (int64_t o = tid; o < total; o += nthr) {
-                const int co = (int)(o % cout);
-                const int64_t r = o / cout;
-                const int tap = (int)(r % taps), ci = (int)(r / taps);
-                Elem<TD>::st(out + o, w[((int64_t)co * taps + (taps - 1 - tap)) * cin + ci]);
-            }
-        }
-        return;
-    }
-    if (layout == 2) {
-        // upsample-phase form (conv_mx.hip, ConvGeom::ntap == 4): four phases (a, b) x fragment-major blocks of FOUR taps
-        // (r, s); the tap of phase (a, b) is the SUM of the 3x3 taps that land on the same low-resolution pixel:
-        // rows R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}, columns alike.  transpose: the data-gradient
-        // form (output channels = ci, input = co, taps mirrored: tap (r', s') carries W_ab[1-r'][1-s']).
-        const int dcout = transpose ? cin : cout, dcin = transpose ? cout : cin;
-        const int cot_tiles = ((dcout + 127) / 128) * 4;
-        const int ncc = dcin / (4 * E);
-        const int64_t per_phase = (int64_t)cot_tiles * ncc * 4 * 2 * 64;
-        for (int64_t o = tid; o < 4 * per_phase; o += nthr) {
-            int64_t r = o;
-            const int co32 = (int)(r & 31); r >>= 5;
-            const int kg = (int)(r & 1); r >>= 1;
-            const int ks = (int)(r & 1); r >>= 1;
-            int tap = (int)(r & 3); r >>= 2;
-            const int cc = (int)(r % ncc); r /= ncc;
-            const int cot = (int)(r % cot_tiles);
-            const int ph = (int)(r / cot_tiles), pa = ph >> 1, pb = ph & 1;
-            const int co = cot * 32 + co32;
-            const int ci = ((cc * 2 + ks) * 2 + kg) * E;
-            if (transpose) tap = 3 - tap;
-            const int tr = tap >> 1, ts = tap & 1;
-            const int ky0 = pa == 0 ? (tr == 0 ? 0 : 1) : (tr == 0 ? 0 : 2), ky1 = pa == 0 ? (tr == 0 ? 0 : 2) : (tr == 0 ? 1 : 2);
-            const int kx0 = pb == 0 ? (ts == 0 ? 0 : 1) : (ts == 0 ? 0 : 2), kx1 = pb == 0 ? (ts == 0 ? 0 : 2) : (ts == 0 ? 1 : 2);
-            float v[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = 0.0f;
-            if (co < dcout) {
-                for (int ky = ky0; ky <= ky1; ++ky)
-                    for (int kx = kx0; kx <= kx1; ++kx) {
-                        if (!transpose) {
-                            const float* src = w + ((int64_t)co * 9 + ky * 3 + kx) * cin + ci;
-#pragma unroll
-                            for (int e = 0; e < E; ++e) v[e] += src[e];
-                        } else {
-                            const float* src = w + ((int64_t)ci * 9 + ky * 3 + kx) * cin + co;
-#pragma unroll
-                            for (int e = 0; e < E; ++e) v[e] += src[(int64_t)e * 9 * cin];
-                        }
-                    }
-            }
-            Vec16<TD>::store(out + o * E, v);
-        }
-        return;
-    }
-    if (layout == 3) {
-        // data gradient of a STRIDE-2 3x3 conv without padding, by output parity (vqk_conv2d_s2_dgrad): dx[2i+a][2j+b] sums the
-        // taps ky = a (mod 2), kx = b (mod 2) -- 4 / 2 / 2 / 1 of them for (a, b) = (0,0) / (0,1) / (1,0) / (1,1), nine in all.
-        // Four fragment-major blocks (output channels = ci, input = co) in that order; the window tap (wy, wx) of a phase
-        // reads dy[i - 1 + wy] when the phase has two rows (wy = 0: ky = 2, wy = 1: ky = 0), dy[i] (ky = 1) otherwise.
-        const int dcout = cin, dcin = cout;
-        const int cot_tiles = ((dcout + 127) / 128) * 4;
-        const int ncc = dcin / (4 * E);
-        const int64_t per_tap = (int64_t)cot_tiles * ncc * 2 * 64;       // 16-byte pieces
-        for (int64_t o = tid; o < 9 * per_tap; o += nthr) {
-            const int ph = o < 4 * per_tap ? 0 : o < 6 * per_tap ? 1 : o < 8 * per_tap ? 2 : 3;
-            const int pa = ph >> 1, pb = ph & 1, nb = pb ? 1 : 2, nt = (pa ? 1 : 2) * nb;
-            int64_t r = o - (ph == 0 ? 0 : ph == 1 ? 4 : ph == 2 ? 6 : 8) * per_tap;
-            const int co32 = (int)(r & 31); r >>= 5;
-            const int kg = (int)(r & 1); r >>= 1;
-            const int ks = (int)(r & 1); r >>= 1;
-            const int tap = (int)(r % nt); r /= nt;
-            const int cc = (int)(r % ncc);
-            const int cot = (int)(r / ncc);
-            const int wy = tap / nb, wx = tap - wy * nb;
-            const int ky = pa ? 1 : (wy == 0 ? 2 : 0), kx = pb ? 1 : (wx == 0 ? 2 : 0);
-            const int co = cot * 32 + co32;                              // output channel of the gradient = input channel of the layer
-            const int ci = ((cc * 2 + ks) * 2 + kg) * E;                 // first of E input channels = output channels of the layer
-            float v[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = 0.0f;
-            if (co < dcout) {
-                const float* src = w + ((int64_t)ci * 9 + ky * 3 + kx) * cin + co;
-#pragma unroll
-                for (int e = 0; e < E; ++e) v[e] = src[(int64_t)e * 9 * cin];
-            }
-            Vec16<TD>::store(out + o * E, v);
-        }
-        return;
-    }
-    // fragment-major: one thread builds one 16-byte piece (E consecutive input channels of one output channel)
-    const int dcout = transpose ? cin : cout, dcin = transpose ? cout : cin;
-    const int cot_tiles = ((dcout + 127) / 128) * 4;
-    const int ncc = dcin / (4 * E);
-    const int64_t total = (int64_t)cot_tiles * ncc * taps * 2 * 64;
-    for (int64_t o = tid; o < total; o += nthr) {
-        int64_t r = o;
-        const int co32 = (int)(r & 31); r >>= 5;
-        const int kg = (int)(r & 1); r >>= 1;
-        const int ks = (int)(r & 1); r >>= 1;
-        const int tap = (int)(r % taps); r /= taps;
-        const int cc = (int)(r % ncc);
-        const int cot = (int)(r / ncc);
-        const int co = cot * 32 + co32;
-        const int ci = ((cc * 2 + ks) * 2 + kg) * E;
-        float v[E];
-        if (co >= dcout) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = 0.0f;
-        } else if (!transpose) {
-            const float* src = w + ((int64_t)co * taps + tap) * cin + ci;
-#pragma unroll
-            for (int q = 0; q < E / 4; ++q) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(src + 4 * q);
-                v[4 * q] = t[0]; v[4 * q + 1] = t[1]; v[4 * q + 2] = t[2]; v[4 * q + 3] = t[3];
-            }
-        } else {
-            const float* src = w + ((int64_t)ci * taps + (taps - 1 - tap)) * cin + co;
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = src[(int64_t)e * taps * cin];
-        }
-        Vec16<TD>::store(out + o * E, v);
-    }
-}
-
-// layout 5 (split-product mode, conv_x3.hip): fragment-major like layout 1 in bf16, every fragment TWICE -- hi = bf16_rne(w),
-// lo = bf16_rne(w - hi): [cot][chunk of 32 channels][tap][ks][hi | lo][kg][co32][8].  The buffer has the byte size of the fp32
-// fragment-major operand (4 B per weight), which is how the fp32 descriptor / vqk_conv_packed_elems size it.
-__device__ __forceinline__ void pack_x3(const float* __restrict__ w, bf16_raw* __restrict__ out, int cout, int cin, int taps,
-                                        int transpose) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const int dcout = transpose ? cin : cout, dcin = transpose ? cout : cin;
-    const int cot_tiles = ((dcout + 127) / 128) * 4;
-    const int ncc = dcin / 32;
-    const int64_t total = (int64_t)cot_tiles * ncc * taps * 2 * 64;       // (hi, lo) pairs of 16-byte pieces
-    for (int64_t o = tid; o < total; o += nthr) {
-        int64_t r = o;
-        const int co32 = (int)(r & 31); r >>= 5;
-        const int kg = (int)(r & 1); r >>= 1;
-        const int ks = (int)(r & 1); r >>= 1;
-        const int tap = (int)(r % taps); r /= taps;
-        const int cc = (int)(r % ncc);
-        const int cot = (int)(r / ncc);
-        const int co = cot * 32 + co32;
-        const int ci = ((cc * 2 + ks) * 2 + kg) * 8;
-        float v[8], lo[8];
-        if (co >= dcout) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = 0.0f;
-        } else if (!transpose) {
-            const float* src = w + ((int64_t)co * taps + tap) * cin + ci;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = src[e];
-        } else {
-            const float* src = w + ((int64_t)ci * taps + (taps - 1 - tap)) * cin + co;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = src[(int64_t)e * taps * cin];
-        }
-        const vqk_u32x4 hi = vqk_pack_bf16x8(v);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            lo[2 * q] = v[2 * q] - __uint_as_float(hi[q] << 16);
-            lo[2 * q + 1] = v[2 * q + 1] - __uint_as_float(hi[q] & 0xffff0000u);
-        }
-        const int64_t frag = (((int64_t)cot * ncc + cc) * taps + tap) * 2 + ks;          // (hi, lo) fragment pair index
-        bf16_raw* dst = out + (frag * 2 * 64 + kg * 32 + co32) * 8;
-        *reinterpret_cast<vqk_u32x4*>(dst) = hi;
-        *reinterpret_cast<vqk_u32x4*>(dst + 64 * 8) = vqk_pack_bf16x8(lo);
-    }
-}
-
-// layout 6 (split-product mode, the 2x2-resampling convs in phase form: conv_x3.hip NTAP = 4): the phase-summed four-tap operand of
-// layout 2 -- same phase / tap algebra, the sums taken in fp32 -- stored as layout 5's (hi | lo) fragment pairs:
-// [phase][cot][chunk of 32 channels][tap 4][ks][hi | lo][kg][co32][8].  Byte size = layout 2's element count x 4.
-__device__ __forceinline__ void pack_x3_phase(const float* __restrict__ w, bf16_raw* __restrict__ out, int cout, int cin, int transpose) {
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-    const int dcout = transpose ? cin : cout, dcin = transpose ? cout : cin;
-    const int cot_tiles = ((dcout + 127) / 128) * 4;
-    const int ncc = dcin / 32;
-    const int64_t per_phase = (int64_t)cot_tiles * ncc * 4 * 2 * 64;
-    for (int64_t o = tid; o < 4 * per_phase; o += nthr) {
-        int64_t r = o;
-        const int co32 = (int)(r & 31); r >>= 5;
-        const int kg = (int)(r & 1); r >>= 1;
-        const int ks = (int)(r & 1); r >>= 1;
-        const int tapd = (int)(r & 3); r >>= 2;
-        const int cc = (int)(r % ncc); r /= ncc;
-        const int cot = (int)(r % cot_tiles);
-        const int ph = (int)(r / cot_tiles), pa = ph >> 1, pb = ph & 1;
-        const int co = cot * 32 + co32;
-        const int ci = ((cc * 2 + ks) * 2 + kg) * 8;
-        const int tap = transpose ? 3 - tapd : tapd;
-        const int tr = tap >> 1, ts = tap & 1;
-        const int ky0 = pa == 0 ? (tr == 0 ? 0 : 1) : (tr == 0 ? 0 : 2), ky1 = pa == 0 ? (tr == 0 ? 0 : 2) : (tr == 0 ? 1 : 2);
-        const int kx0 = pb == 0 ? (ts == 0 ? 0 : 1) : (ts == 0 ? 0 : 2), kx1 = pb == 0 ? (ts == 0 ? 0 : 2) : (ts == 0 ? 1 : 2);
-        float v[8], lo[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.0f;
-        if (co < dcout) {
-            for (int ky = ky0; ky <= ky1; ++ky)
-                for (int kx = kx0; kx <= kx1; ++kx) {
-                    if (!transpose) {
-                        const float* src = w + ((int64_t)co * 9 + ky * 3 + kx) * cin + ci;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += src[e];
-                    } else {
-                        const float* src = w + ((int64_t)ci * 9 + ky * 3 + kx) * cin + co;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += src[(int64_t)e * 9 * cin];
-                    }
-                }
-        }
-        const vqk_u32x4 hi = vqk_pack_bf16x8(v);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            lo[2 * q] = v[2 * q] - __uint_as_float(hi[q] << 16);
-            lo[2 * q + 1] = v[2 * q + 1] - __uint_as_float(hi[q] & 0xffff0000u);
-        }
-        const int64_t frag = ((((int64_t)ph * cot_tiles + cot) * ncc + cc) * 4 + tapd) * 2 + ks;       // (hi, lo) fragment pair index
-        bf16_raw* dst = out + (frag * 2 * 64 + kg * 32 + co32) * 8;
-        *reinterpret_cast<vqk_u32x4*>(dst) = hi;
-        *reinterpret_cast<vqk_u32x4*>(dst + 64 * 8) = vqk_pack_bf16x8(lo);
-    }
-}
-
-__global__ __launch_bounds__(256) void pack_multi_kernel(const int64_t* __restrict__ descs) {
-    const int64_t* d = descs + (int64_t)blockIdx.y * 8;
-    const float* src = reinterpret_cast<const float*>(d[0]);
-    const int dtype = (int)d[2], cout = (int)d[3], cin = (int)d[4], ks = (int)d[5], tr = (int)d[6], lay = (int)d[7];
-    if (lay == 5) pack_x3(src, reinterpret_cast<bf16_raw*>(d[1]), cout, cin, ks * ks, tr);
-    else if (lay == 6) pack_x3_phase(src, reinterpret_cast<bf16_raw*>(d[1]), cout, cin, tr);
-    else if (dtype == VQK_F32) pack_any<float>(src, reinterpret_cast<float*>(d[1]), cout, cin, ks * ks, tr, lay);
-    else pack_any<bf16_raw>(src, reinterpret_cast<bf16_raw*>(d[1]), cout, cin, ks * ks, tr, lay);
-}
-
-// the same packing for ONE operand, descriptor by value (no device table: usable under stream capture)
-__global__ __launch_bounds__(256) void pack_one_kernel(const float* __restrict__ src, void* __restrict__ dst, int dtype, int cout,
-                                                       int cin, int ks, int tr, int lay) {
-    if (lay == 5) pack_x3(src, reinterpret_cast<bf16_raw*>(dst), cout, cin, ks * ks, tr);
-    else if (lay == 6) pack_x3_phase(src, reinterpret_cast<bf16_raw*>(dst), cout, cin, tr);
-    else if (dtype == VQK_F32) pack_any<float>(src, reinterpret_cast<float*>(dst), cout, cin, ks * ks, tr, lay);
-    else pack_any<bf16_raw>(src, reinterpret_cast<bf16_raw*>(dst), cout, cin, ks * ks, tr, lay);
-}
-
-// out[c] += sum_rows x[row][c].  c*sizeof(T) a multiple of 16 (VEC): a thread owns one 16-byte channel slot and strides
-// over rows (the GroupNorm kernels' mapping); otherwise one column per thread.
-template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, int64_t rows, int c, int64_t rows_per_block,
-                                                     float* __restrict__ out, int c_out, float scale) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sh = reinterpret_cast<float*>(smem);            // [c]
-    for (int i = threadIdx.x; i < c; i += 256) sh[i] = 0.f;
-    __syncthreads();
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
-    if (VEC) {
-        constexpr int V = Vec16<T>::N;
-        const int vpp = c / V;                              // slots per row
-        if (vpp <= 256) {
-            const int slot = threadIdx.x % vpp, rlane = threadIdx.x / vpp, rstep = 256 / vpp;
-            if (rlane < rstep) {
-                float a[V];
-#pragma unroll
-                for (int i = 0; i < V; ++i) a[i] = 0.f;
-#pragma unroll 4
-                for (int64_t r = r0 + rlane; r < r1; r += rstep) {
-                    float v[V];
-                    Vec16<T>::load(x + r * c + slot * V, v);
-#pragma unroll
-                    for (int i = 0; i < V; ++i) a[i] += v[i];
-                }
-#pragma unroll
-                for (int i = 0; i < V; ++i) atomicAdd(&sh[slot * V + i], a[i]);
-            }
-        } else {                                            // wide rows (the [N, K] matrices of the quantizers)
-            for (int slot = threadIdx.x; slot < vpp; slot += 256) {
-                float a[V];
-#pragma unroll
-                for (int i = 0; i < V; ++i) a[i] = 0.f;
-#pragma unroll 4
-                for (int64_t r = r0; r < r1; ++r) {
-                    float v[V];
-                    Vec16<T>::load(x + r * c + slot * V, v);
-#pragma unroll
-                    for (int i = 0; i < V; ++i) a[i] += v[i];
-                }
-#pragma unroll
-                for (int i = 0; i < V; ++i) sh[slot * V + i] = a[i];
-            }
-        }
-    } else {
-        for (int col = threadIdx.x & 63; col < c; col += 64) {
-            float a = 0.f;
-            for (int64_t r = r0 + (threadIdx.x >> 6); r < r1; r += 4) a += Elem<T>::ld(x + r * c + col);
-            atomicAdd(&sh[col], a);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < c_out; i += 256) atomicAdd(out + i, sh[i] * scale);     // c_out <= c: the columns `out` has room for
-}
-
-// deterministic column sums, round 4 (the first form -- one thread per column, 2-byte loads, one reducing block -- took 1.47 ms
-// per step for the seven bias gradients: 190 + 80 us for the 537-MB gradient at 128 ch @256^2).  Stage 1: a thread owns one
-// 16-byte channel slot and walks rows r0 + rlane, + rstep, ... of its block (coalesced 16-byte loads, a FIXED set of rows in
-// a fixed order), the row lanes of a slot are added in lane order through LDS; block partials go to the workspace.  Stage 2:
-// a block owns 8 columns, 32 lanes add partial rows lane, lane + 32, ..., thread `col` adds the 32 lane sums in lane order.
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_det_kernel(const T* __restrict__ x, int64_t rows, int c, int64_t rows_per_block,
-                                                         float* __restrict__ part) {
-    constexpr int V = Vec16<T>::N;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sh = reinterpret_cast<float*>(smem);                  // [rstep][c]
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
-    const int vpp = c / V;                                       // slots per row (<= 256: the caller checks)
-    const int slot = threadIdx.x % vpp, rlane = threadIdx.x / vpp, rstep = 256 / vpp;
-    if (rlane < rstep) {
-        float a[V];
-#pragma unroll
-        for (int i = 0; i < V; ++i) a[i] = 0.f;
-#pragma unroll 4
-        for (int64_t r = r0 + rlane; r < r1; r += rstep) {
-            float v[V];
-            Vec16<T>::load(x + r * c + slot * V, v);
-#pragma unroll
-            for (int i = 0; i < V; ++i) a[i] += v[i];
-        }
-#pragma unroll
-        for (int i = 0; i < V; ++i) sh[rlane * c + slot * V + i] = a[i];
-    }
-    __syncthreads();
-    for (int col = threadIdx.x; col < c; col += 256) {
-        float t = 0.f;
-        for (int k = 0; k < rstep; ++k) t += sh[k * c + col];
-        part[(int64_t)blockIdx.x * c + col] = t;
-    }
-}
-// (scalar fallback: channel counts that are no whole 16-byte slots, or more than 256 slots per row)
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_det_scalar_kernel(const T* __restrict__ x, int64_t rows, int c, int64_t rows_per_block,
-                                                                float* __restrict__ part) {
-    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
-    for (int col = threadIdx.x; col < c; col += 256) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        int64_t r = r0;
-        for (; r + 4 <= r1; r += 4) {
-            a0 += Elem<T>::ld(x + r * c + col); a1 += Elem<T>::ld(x + (r + 1) * c + col);
-            a2 += Elem<T>::ld(x + (r + 2) * c + col); a3 += Elem<T>::ld(x + (r + 3) * c + col);
-        }
-        for (; r < r1; ++r) a0 += Elem<T>::ld(x + r * c + col);
-        part[(int64_t)blockIdx.x * c + col] = (a0 + a1) + (a2 + a3);
-    }
-}
-__global__ __launch_bounds__(256) void colsum_det_reduce_kernel(const float* __restrict__ part, int blocks, int c, float* __restrict__ out,
-                                                                int c_out, float scale) {
-    __shared__ float lane_sum[32][8];
-    const int col = (int)blockIdx.x * 8 + (threadIdx.x & 7), rl = threadIdx.x >> 3;
-    float s = 0.f;
-    if (col < c)
-        for (int b = rl; b < blocks; b += 32) s += part[(int64_t)b * c + col];
-    lane_sum[rl][threadIdx.x & 7] = s;
-    __syncthreads();
-    if (threadIdx.x < 8 && col < c_out) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 32; ++k) t += lane_sum[k][threadIdx.x];
-        out[col] += t * scale;
-    }
-}
-
 static thread_local int g_force_variant = -1;   // test hook (per host thread: the library keeps no process-global mutable state): -1 auto, 0 im2col kernel only, 1 halo kernels when eligible,
                                    // 5 never the matrix/auxiliary-wave kernel, 6 that kernel whenever it is eligible
 // deterministic mode (vqk_set_deterministic; the reference trains with deterministic=True, vqvae/train.py:130): split-K partials
@@ -2177,137 +1750,6 @@ int vqk_conv_weight_layout(int dtype, int n, int h_in, int w_in, int cin, int co
     if (dtype == VQK_F32 && cout == 4 && ksize == 3 && !ups && (cin % 16) == 0 && (g.h % 8) == 0 && (g.w % 32) == 0 && g_force_variant != 0)
         return 0;                                                // the 3-channel head in the fp32 modes: conv_thin_f32.hip (plain weights)
     return (halo_twlog(g) && g_force_variant != 2) ? 1 : 0;
-}
-
-int64_t vqk_conv_packed_elems(int cout, int cin, int ksize, int layout) {
-    if (layout == 0) return (int64_t)cout * cin * ksize * ksize;
-    if (layout == 2 || layout == 6) return (int64_t)4 * ((cout + 127) / 128) * 128 * cin * 4;      // four phases x four taps (6: fp32-sized (hi, lo) pairs)
-    if (layout == 3) return (int64_t)((cout + 127) / 128) * 128 * cin * 9;          // four phases, 4 + 2 + 2 + 1 taps
-    return (int64_t)((cout + 127) / 128) * 128 * cin * ksize * ksize;
-}
-
-int vqk_conv_pack_weights(const float* w, void* out, int dtype, int cout, int cin, int ksize, int transpose, int layout,
-                          void* stream) {
-    VQK_REQUIRE(w && out, VQK_ERR_ARG);
-    VQK_REQUIRE(cout > 0 && cin > 0 && (ksize == 1 || ksize == 3), VQK_ERR_SHAPE);
-    VQK_REQUIRE(dtype == VQK_F32 || dtype == VQK_BF16, VQK_ERR_DTYPE);
-    const int taps = ksize * ksize;
-    hipStream_t st = vqk_stream(stream);
-    if (layout == 0) {
-        const int64_t total = (int64_t)cout * cin * taps;
-        const dim3 grid(vqk_grid_1d(total, 256));
-        if (transpose) {
-            if (dtype == VQK_F32) hipLaunchKernelGGL(pack_dgrad_kernel<float>, grid, dim3(256), 0, st, w, (float*)out, cout, cin, taps);
-            else hipLaunchKernelGGL(pack_dgrad_kernel<bf16_raw>, grid, dim3(256), 0, st, w, (bf16_raw*)out, cout, cin, taps);
-        } else {
-            if (dtype == VQK_F32) hipLaunchKernelGGL(cast_kernel<float>, grid, dim3(256), 0, st, w, (float*)out, total);
-            else hipLaunchKernelGGL(cast_kernel<bf16_raw>, grid, dim3(256), 0, st, w, (bf16_raw*)out, total);
-        }
-    } else if (layout == 1) {
-        const int dcout = transpose ? cin : cout, dcin = transpose ? cout : cin;
-        const int e = dtype == VQK_F32 ? 4 : 8;
-        VQK_REQUIRE(dcin % (8 * e) == 0, VQK_ERR_SHAPE);
-        const int cot_tiles = ((dcout + 127) / 128) * 4;
-        const int64_t total = (int64_t)cot_tiles * 32 * taps * dcin;
-        const dim3 grid(vqk_grid_1d(total, 256));
-        if (dtype == VQK_F32) hipLaunchKernelGGL(pack_frag_kernel<float>, grid, dim3(256), 0, st, w, (float*)out, cout, cin, taps, transpose, cot_tiles);
-        else hipLaunchKernelGGL(pack_frag_kernel<bf16_raw>, grid, dim3(256), 0, st, w, (bf16_raw*)out, cout, cin, taps, transpose, cot_tiles);
-    } else if (layout == 5) {
-        const int dcin = transpose ? cout : cin;
-        VQK_REQUIRE((ksize == 3 || ksize == 1) && dtype == VQK_F32 && dcin % 32 == 0, VQK_ERR_SHAPE);
-        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, out, dtype, cout, cin, ksize, transpose, layout);
-    } else if (layout == 6) {
-        const int dcin = transpose ? cout : cin;
-        VQK_REQUIRE(ksize == 3 && dtype == VQK_F32 && dcin % 32 == 0, VQK_ERR_SHAPE);
-        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, out, dtype, cout, cin, ksize, transpose, layout);
-    } else if (layout == 2 || layout == 3) {
-        const int dcin = transpose ? cout : cin;
-        VQK_REQUIRE(ksize == 3 && dtype == VQK_BF16 && dcin % 64 == 0 && (layout == 2 || transpose), VQK_ERR_SHAPE);
-        hipLaunchKernelGGL(pack_one_kernel, dim3(64), dim3(256), 0, st, w, out, dtype, cout, cin, ksize, transpose, layout);
-    } else return VQK_ERR_ARG;
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
-}
-
-int vqk_conv_pack_multi(const int64_t* descs_dev, int ndesc, int blocks_per_desc, void* stream) {
-    VQK_REQUIRE(descs_dev && ndesc >= 0 && blocks_per_desc > 0 && blocks_per_desc <= 4096 && ndesc <= 65535, VQK_ERR_ARG);
-    if (ndesc == 0) return VQK_OK;
-    hipLaunchKernelGGL(pack_multi_kernel, dim3((unsigned)blocks_per_desc, (unsigned)ndesc), dim3(256), 0, vqk_stream(stream),
-                       descs_dev);
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
-}
-
-int vqk_conv_pack_dgrad(const float* w, void* wt, int dtype, int cout, int cin, int ksize, void* stream) {
-    VQK_REQUIRE(w && wt, VQK_ERR_ARG);
-    VQK_REQUIRE(cout > 0 && cin > 0 && (ksize == 1 || ksize == 3), VQK_ERR_SHAPE);
-    const int64_t total = (int64_t)cout * cin * ksize * ksize;
-    const dim3 grid(vqk_grid_1d(total, 256));
-    if (dtype == VQK_F32) hipLaunchKernelGGL(pack_dgrad_kernel<float>, grid, dim3(256), 0, vqk_stream(stream), w, (float*)wt, cout, cin, ksize * ksize);
-    else if (dtype == VQK_BF16) hipLaunchKernelGGL(pack_dgrad_kernel<bf16_raw>, grid, dim3(256), 0, vqk_stream(stream), w, (bf16_raw*)wt, cout, cin, ksize * ksize);
-    else return VQK_ERR_DTYPE;
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
-}
-
-int vqk_colsum(int dtype, const void* x, int64_t rows, int c, float* out, void* stream) {
-    return vqk_colsum_lead(dtype, x, rows, c, c, 1.0f, out, stream);
-}
-
-int vqk_colsum_lead(int dtype, const void* x, int64_t rows, int c, int c_out, float scale, float* out, void* stream) {
-    VQK_REQUIRE(x && out, VQK_ERR_ARG);
-    VQK_REQUIRE(rows >= 0 && c > 0 && c <= 8192 && c_out > 0 && c_out <= c, VQK_ERR_SHAPE);
-    VQK_REQUIRE(dtype == VQK_F32 || dtype == VQK_BF16, VQK_ERR_DTYPE);
-    if (rows == 0) return VQK_OK;
-    if (g_det) {
-        int64_t nb = (rows + 63) / 64; if (nb > 512) nb = 512;
-        while (nb > 1 && nb * c * 4 > g_det_ws_bytes) nb >>= 1;
-        VQK_REQUIRE(g_det_ws && nb * c * 4 <= g_det_ws_bytes, VQK_ERR_ARG);
-        const int64_t rb = (rows + nb - 1) / nb;
-        nb = (rows + rb - 1) / rb;
-        hipStream_t sd = vqk_stream(stream);
-        const int vd = dtype == VQK_F32 ? 4 : 8;
-        const bool vecd = (c % vd) == 0 && c / vd <= 256 && (256 % (c / vd)) == 0 && vqk_aligned16(x);
-        if (vecd) {
-            const size_t ldsd = (size_t)(256 / (c / vd)) * c * 4;
-            if (dtype == VQK_F32) hipLaunchKernelGGL(colsum_det_kernel<float>, dim3((unsigned)nb), dim3(256), ldsd, sd, (const float*)x, rows, c, rb, g_det_ws);
-            else hipLaunchKernelGGL(colsum_det_kernel<bf16_raw>, dim3((unsigned)nb), dim3(256), ldsd, sd, (const bf16_raw*)x, rows, c, rb, g_det_ws);
-        } else {
-            if (dtype == VQK_F32) hipLaunchKernelGGL(colsum_det_scalar_kernel<float>, dim3((unsigned)nb), dim3(256), 0, sd, (const float*)x, rows, c, rb, g_det_ws);
-            else hipLaunchKernelGGL(colsum_det_scalar_kernel<bf16_raw>, dim3((unsigned)nb), dim3(256), 0, sd, (const bf16_raw*)x, rows, c, rb, g_det_ws);
-        }
-        hipLaunchKernelGGL(colsum_det_reduce_kernel, dim3((unsigned)((c + 7) / 8)), dim3(256), 0, sd, (const float*)g_det_ws, (int)nb, c, out, c_out, scale);
-        VQK_CHECK_LAUNCH();
-        return VQK_OK;
-    }
-    const int v = dtype == VQK_F32 ? 4 : 8;
-    const bool vec = (c % v) == 0 && vqk_aligned16(x);
-    int64_t blocks = (rows + 63) / 64; if (blocks > 1024) blocks = 1024;
-    const int64_t rpb = (rows + blocks - 1) / blocks;
-    blocks = (rows + rpb - 1) / rpb;
-    const dim3 grid((unsigned)blocks);
-    const size_t lds = (size_t)c * 4;
-    hipStream_t st = vqk_stream(stream);
-    if (dtype == VQK_F32) {
-        if (vec) hipLaunchKernelGGL((colsum_kernel<float, true>), grid, dim3(256), lds, st, (const float*)x, rows, c, rpb, out, c_out, scale);
-        else hipLaunchKernelGGL((colsum_kernel<float, false>), grid, dim3(256), lds, st, (const float*)x, rows, c, rpb, out, c_out, scale);
-    } else {
-        if (vec) hipLaunchKernelGGL((colsum_kernel<bf16_raw, true>), grid, dim3(256), lds, st, (const bf16_raw*)x, rows, c, rpb, out, c_out, scale);
-        else hipLaunchKernelGGL((colsum_kernel<bf16_raw, false>), grid, dim3(256), lds, st, (const bf16_raw*)x, rows, c, rpb, out, c_out, scale);
-    }
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
-}
-
-int vqk_cast(const float* src, void* dst, int dtype, int64_t n, void* stream) {
-    VQK_REQUIRE(src && dst, VQK_ERR_ARG);
-    if (n <= 0) return VQK_OK;
-    const dim3 grid(vqk_grid_1d(n, 256));
-    if (dtype == VQK_F32) hipLaunchKernelGGL(cast_kernel<float>, grid, dim3(256), 0, vqk_stream(stream), src, (float*)dst, n);
-    else if (dtype == VQK_BF16) hipLaunchKernelGGL(cast_kernel<bf16_raw>, grid, dim3(256), 0, vqk_stream(stream), src, (bf16_raw*)dst, n);
-    else return VQK_ERR_DTYPE;
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
 }
 
 }  // extern "C"
