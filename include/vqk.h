@@ -173,6 +173,38 @@ int64_t vqk_fsq_backward_ws_bytes(int64_t n, int dm, int d);
 int vqk_fsq_backward(const float* z, const float* u, const void* dq, int dq_dtype, const float* w_in, const float* w_out, int64_t n,
                      int dm, int d, const int32_t* levels, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out,
                      int accumulate, void* ws, int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- residual quantizer ---------
+ * Lee et al. 2022 (RQ-VAE) / SoundStream (csrc/rvq.hip).  z[N][D] fp32 rows, ONE codebook e[K][D] shared by the `depth` stages:
+ * r_0 = z; k_q = argmin_k (|r_{q-1}|^2 + |e_k|^2) - 2 r_{q-1}.e_k (the arithmetic of vqk_vq_forward_f32 with assoc 0, first minimum
+ * wins); r_q = r_{q-1} - e[k_q] (one fp32 subtraction per element); zhat = ((e[k_1] + e[k_2]) + ...) + e[k_Q], added in stage order
+ * (NOT z - r_Q: decoding the tokens alone gives the same bits).  Tokens are idx[N][depth] int64, stage fastest.
+ * loss = (1 + beta) / (N D) sum_q sse[q], sse[q] = sum_rows |r_q|^2;  dz = dq + s cz sum_q r_q;  de[k] += -s ce sum_{(row, q): k_q = k} r_q
+ * (cz = 2 beta / (N D), ce = 2 / (N D), s = *gscale_dev).  1 <= depth <= 8.  No call allocates or synchronises.
+ * forward: ONE launch, a block keeps its 32 residual rows in LDS for all stages; equal to `depth` calls of vqk_vq_forward_f32 on the
+ * materialised residuals, bit for bit.  ws = what vqk_vq_prepare_f32 built from THIS codebook (shared by the stages, not rebuilt here).
+ * q as fp32 (q) and / or bf16 (q_lo), sse[depth] and hist[depth][K] (int32) are optional; sse and hist are pre-zeroed by the caller.
+ * sse: one fp32 atomic per block and stage (arrival order); in deterministic mode the blocks' partials go through the workspace of
+ * vqk_set_deterministic (>= ceil(n / 32) * depth * 4 bytes: VQK_ERR_WORKSPACE) and a second one-wave launch adds them in block order.
+ * Served: d == 256, k % 32 == 0 (VQK_ERR_SHAPE otherwise, nothing launched); z, e, ws, q, q_lo 16-byte aligned (VQK_ERR_ALIGN);
+ * ws_bytes >= vqk_vq_filter_ws_bytes(k, d) (VQK_ERR_WORKSPACE). */
+int vqk_rvq_forward_f32(const float* z, const float* e, const void* ws, int64_t ws_bytes, int64_t n, int k, int d, int depth,
+                        int64_t* idx, float* q /* optional */, void* q_lo /* optional */, float* sse /* optional */,
+                        int32_t* hist /* optional */, void* stream);
+/* idx[N][depth] -> zhat as fp32 (q) and / or bf16 (q_lo; at least one) through the forward's own accumulation function: the same bits
+ * for the same tokens.  An index outside [0, K) reads nothing and contributes nothing.  Any d % 4 == 0; e and q 16-byte, q_lo 8-byte aligned. */
+int vqk_rvq_decode_f32(const int64_t* idx, const float* e, int64_t n, int k, int d, int depth, float* q /* optional */,
+                       void* q_lo /* optional */, void* stream);
+/* The residuals are RECOMPUTED from z, e and idx by the forward's running subtraction (the same bits; the forward saves none).  dq:
+ * optional (NULL = 0), fp32 or bf16 (dq_dtype); de: optional, pre-zeroed by the caller (or holding what it is added to).  d == 256.
+ * Default: per stage the rows of a 32-row block that share a code are summed in LDS, one coalesced fp32 atomic row per distinct
+ * (code, block) (arrival order).  Deterministic mode (vqk_set_deterministic) with de: the residual stack R[N][depth][256] goes to ws
+ * (>= vqk_rvq_backward_ws_bytes(n, d, depth) bytes, 16-byte aligned: VQK_ERR_WORKSPACE / VQK_ERR_ALIGN) and one block per code adds its
+ * rows of R in (row, stage) order: no atomics, the same bits every run.  ws is not read otherwise (NULL allowed).
+ * vqk_rvq_backward_ws_bytes returns VQK_ERR_SHAPE for an unserved (d, depth). */
+int64_t vqk_rvq_backward_ws_bytes(int64_t n, int d, int depth);
+int vqk_rvq_backward_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
+                         int depth, float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws,
+                         int64_t ws_bytes, void* stream);
 /* EMA statistics (vector_quantizers.py:159-169): counts[k] += 1, dw[idx] += z (both pre-zeroed) ...  fp32 atomics in arrival order;
  * in deterministic mode (this entry and the fused one): one block per code adds its rows in row order, no atomics -- the same bits every run. */
 int vqk_ema_stats_f32(const float* z, const int64_t* idx, int64_t n, int k, int d,

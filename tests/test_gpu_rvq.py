@@ -1,0 +1,363 @@
+"""The residual quantizer on the GPU (csrc/rvq.hip, _ops_rvq.py, ResidualVectorQuantizer).
+
+1. The fused multi-stage kernel equals the staged formulation (ops.rvq_staged: the single-stage forward kernel per stage + fp32 torch
+   subtraction / addition) BIT FOR BIT -- indices, zhat as fp32 and bf16, hist[q][k] -- on every case and row: both evaluate the same
+   fp32 expression sequence, any difference is a bug (tile write-back, barrier, accumulation order).
+2. Teacher-forced float64 acceptance (tests/rvq_reference.py::check_acceptance) on every (row, stage): within 2 eta of the float64
+   minimum, equal to the float64 argmin where the runner-up is more than 2 eta away; eta = the evaluation bound of the exact fp32 path
+   (csrc/vq_filter.hip).  tests/test_rvq_cpu.py shows that >= 99 % of the scale-1 pairs are separated, so the equality branch carries it.
+3. sse[q], loss, dz, de against the float64 closed forms on the kernel's indices at the tolerances of
+   tests/test_gpu_ops.py::test_vq_standard_module_golden (loss rtol 1e-5; dz rtol 1e-5 / atol 1e-7; de rtol 1e-4 / atol 1e-7).
+The inputs (tests/rvq_reference.py) are shared with the CPU tests; every figure that is asserted with a tolerance is printed first
+(``RVQMEASURE``)."""
+import importlib
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import rvq_reference as R
+
+pytestmark = pytest.mark.gpu
+
+PKG = 'vqvae-vqgan-pytorch-lightning_amd'
+ops = importlib.import_module(PKG + '.ops')
+model_mod = importlib.import_module(PKG + '.model')
+trainer_mod = importlib.import_module(PKG + '.trainer')
+vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEV = 'cuda:0'
+BETA = 0.25
+IDS = lambda c: f'N{c[0]}-K{c[1]}-Q{c[2]}-{c[3]}'
+_FWD: dict = {}
+
+
+def dev_case(case):
+    z, e = R.make_case(*case)
+    return z.to(DEV), e.to(DEV)
+
+
+def fused(case):
+    """the fused forward of one case (fp32 and bf16 output), computed once and shared read-only"""
+    if case not in _FWD:
+        n, k, depth, _ = case
+        z, e = dev_case(case)
+        assert ops.rvq_fused_serves(e)
+        with torch.no_grad():
+            img = z.view(1, n, 1, R.D).permute(0, 3, 1, 2)
+            q32, idx, loss, hist, dh, sse = ops.RVQLookupFn.apply(img, e, BETA, depth, torch.float32)
+            qlo, idx2, _, _, dh2, _ = ops.RVQLookupFn.apply(img, e, BETA, depth, torch.bfloat16)
+        rows = lambda t: t.permute(0, 2, 3, 1).reshape(n, R.D)
+        assert torch.equal(idx, idx2) and torch.equal(dh, dh2)
+        _FWD[case] = dict(idx=idx.view(n, depth), q32=rows(q32), qlo=rows(qlo), loss=loss, hist=hist, depth_hist=dh, sse=sse)
+    return _FWD[case]
+
+
+def close(name, got, want, rtol, atol=0.0):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    err = np.abs(got - want)
+    print(f'RVQMEASURE {name}: max abs {err.max():.3e}, max |want| {np.abs(want).max():.3e}, worst err / (atol + rtol |want|) '
+          f'{(err / (atol + rtol * np.abs(want) + 1e-300)).max():.3g}')
+    np.testing.assert_allclose(got, want, rtol=rtol, atol=atol, err_msg=name)
+
+
+# ---------------------------------------------------------------------------------------------- 1. fused == staged, bit for bit
+@pytest.mark.parametrize('case', R.cases(), ids=IDS)
+def test_fused_equals_staged_bit_for_bit(case):
+    n, k, depth, kind = case
+    z, e = dev_case(case)
+    f = fused(case)
+    idx_s, q_s, qlo_s, sse_s, hist_s = ops.rvq_staged(z, e, depth, want_lo=True)
+    assert torch.equal(f['idx'], idx_s)
+    assert torch.equal(f['q32'], q_s) and f['q32'].dtype == torch.float32
+    assert torch.equal(f['qlo'], qlo_s) and f['qlo'].dtype == torch.bfloat16
+    assert torch.equal(f['depth_hist'], hist_s) and f['depth_hist'].dtype == torch.int32
+    assert torch.equal(f['hist'], hist_s.sum(0).to(torch.int32)) and int(f['hist'].sum()) == n * depth
+    assert [int(v) for v in f['depth_hist'].sum(1)] == [n] * depth
+    assert torch.equal(ops.rvq_assign(z, e, depth), idx_s)
+    if kind == 'collapsed':
+        assert int(f['idx'].max()) < 4                            # exact ties: the smallest index wins (and the list overflows)
+    # the per-stage sums are added in another order by the two paths (block partials, arrival order of the blocks)
+    close('sse fused vs staged', f['sse'].cpu(), sse_s.cpu(), rtol=1e-5)
+
+
+# ---------------------------------------------------------------------------------------------- 2. teacher-forced acceptance
+@pytest.mark.parametrize('case', R.cases(), ids=IDS)
+def test_teacher_forced_float64_acceptance(case):
+    z, e = R.make_case(*case)
+    idx = fused(case)['idx'].cpu()
+    assert int(idx.min()) >= 0 and int(idx.max()) < case[1]
+    separated = R.check_acceptance(z, e, idx)                     # every pair
+    print(f'RVQMEASURE {IDS(case)}: separated pairs {separated:.4f}')
+    if case[3] == 'scale1':
+        assert separated >= 0.99
+    if case[3] == 'zero':
+        print(f'RVQMEASURE {IDS(case)}: zero code chosen {int((idx == 3).sum())} times')
+
+
+# ---------------------------------------------------------------------------------------------- 3. sse, loss, dz, de
+def _grads(case, dq_name, deterministic=False):
+    n, k, depth, _ = case
+    z, e = dev_case(case)
+    img = z.view(1, n, 1, R.D).permute(0, 3, 1, 2).detach().requires_grad_(True)
+    cb = e.detach().clone().requires_grad_(True)
+    dq = None
+    if dq_name != 'none':
+        dq = torch.randn(n, R.D, generator=torch.Generator().manual_seed(11)).to(DEV)
+        dq = dq.to(torch.bfloat16) if dq_name == 'bf16' else dq
+    ops.set_deterministic(deterministic)
+    try:
+        q, idx, loss, _, _, sse = ops.RVQLookupFn.apply(img, cb, BETA, depth, torch.bfloat16 if dq_name == 'bf16' else torch.float32)
+        outs, gouts = [loss], [torch.ones((), device=DEV)]
+        if dq is not None:
+            outs.append(q), gouts.append(dq.view(1, n, 1, R.D).permute(0, 3, 1, 2))
+        dz, de = torch.autograd.grad(outs, [img, cb], gouts)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_deterministic(False)
+    return dict(idx=idx.view(n, depth), loss=loss, sse=sse, dz=dz.permute(0, 2, 3, 1).reshape(n, R.D), de=de,
+                dq=None if dq is None else dq.float().cpu())
+
+
+@pytest.mark.parametrize('dq_name', ['fp32', 'bf16', 'none'])
+@pytest.mark.parametrize('case', R.cases(), ids=IDS)
+def test_loss_and_gradients_against_float64(case, dq_name):
+    z, e = R.make_case(*case)
+    g = _grads(case, dq_name)
+    assert torch.equal(g['idx'], fused(case)['idx'])
+    loss, sse, dz, de = R.gradients(z, e, g['idx'].cpu(), g['dq'], BETA)
+    tag = f'{IDS(case)} dq {dq_name}'
+    close(f'{tag} sse', g['sse'].cpu(), sse, rtol=1e-5)
+    close(f'{tag} loss', g['loss'].item(), loss.item(), rtol=1e-5)
+    close(f'{tag} dz', g['dz'].cpu(), dz, rtol=1e-5, atol=1e-7)
+    close(f'{tag} de', g['de'].cpu(), de, rtol=1e-4, atol=1e-7)
+
+
+# ---------------------------------------------------------------------------------------------- 4. depth 1 == VectorQuantizer
+@pytest.mark.parametrize('case', [c for c in R.cases() if c[:3] in ((67, 64, 4), (2051, 1024, 4))], ids=IDS)
+def test_depth_one_is_the_standard_quantizer(case):
+    n, k, _, _ = case
+    z, e = dev_case(case)
+    res = {}
+    for name, quant in (('std', vqm.VectorQuantizer(k, R.D, BETA)), ('rvq', vqm.ResidualVectorQuantizer(k, R.D, BETA, 1))):
+        quant = quant.to(DEV)
+        with torch.no_grad():
+            quant.codebook.weight.copy_(e)
+        img = z.view(1, n, 1, R.D).permute(0, 3, 1, 2).detach().requires_grad_(True)
+        q, idx, loss = quant(img)
+        dq = torch.randn(n, R.D, generator=torch.Generator().manual_seed(5)).to(DEV).view(1, n, 1, R.D).permute(0, 3, 1, 2)
+        dz, de = torch.autograd.grad([q, loss], [img, quant.codebook.weight], [dq, torch.ones((), device=DEV)])
+        res[name] = (q, idx.reshape(n), loss, dz, de, quant.last_hist)
+    assert torch.equal(res['rvq'][1], res['std'][1]) and torch.equal(res['rvq'][0], res['std'][0])
+    assert torch.equal(res['rvq'][5], res['std'][5])
+    close('depth 1 loss', res['rvq'][2].item(), res['std'][2].item(), rtol=1e-5)
+    close('depth 1 dz', res['rvq'][3].cpu(), res['std'][3].cpu(), rtol=1e-5, atol=1e-7)
+    close('depth 1 de', res['rvq'][4].cpu(), res['std'][4].cpu(), rtol=1e-4, atol=1e-7)
+
+
+# ---------------------------------------------------------------------------------------------- 5. decode
+@pytest.mark.parametrize('case', [c for c in R.cases() if c[:3] in ((67, 64, 4), (2051, 1024, 8))], ids=IDS)
+def test_decode_has_the_forwards_bits(case):
+    n, k, depth, _ = case
+    _, e = dev_case(case)
+    f = fused(case)
+    for dtype, key in ((torch.float32, 'q32'), (torch.bfloat16, 'qlo')):
+        dec = ops.rvq_decode(f['idx'].view(1, n, depth), e, dtype)
+        assert dec.dtype == dtype and tuple(dec.shape) == (1, n, R.D) and torch.equal(dec[0], f[key])
+    # an index outside [0, K) reads nothing: that stage contributes zero, the other stages their codes
+    row, stage = n // 2, depth - 1
+    for bad in (-1, k, 2 ** 40 + 3, -2 ** 62):
+        wild = f['idx'].clone()
+        wild[row, stage] = bad
+        out = ops.rvq_decode(wild, e)
+        assert bool(torch.isfinite(out).all())
+        want = ops.rvq_decode(f['idx'][:, :stage].contiguous(), e) if stage else torch.zeros_like(out)
+        assert torch.equal(out[row], want[row])
+        keep = torch.arange(n, device=DEV) != row
+        assert torch.equal(out[keep], f['q32'][keep])
+    all_bad = torch.full((3, depth), k + 7, dtype=torch.int64, device=DEV)
+    assert float(ops.rvq_decode(all_bad, e).abs().max()) == 0.0
+    # the module over the same codebook
+    quant = vqm.ResidualVectorQuantizer(k, R.D, BETA, depth).to(DEV)
+    with torch.no_grad():
+        quant.codebook.weight.copy_(e)
+        z = dev_case(case)[0].view(1, n, 1, R.D).permute(0, 3, 1, 2)
+        codes = quant.vec_to_codes(z)
+        assert tuple(codes.shape) == (1, n, depth) and torch.equal(codes[0], f['idx'])
+        assert torch.equal(quant.codes_to_vec(codes)[0], f['q32'])
+
+
+# ---------------------------------------------------------------------------------------------- 6. deterministic mode
+@pytest.mark.parametrize('kind', ['scale1', 'collapsed'])
+def test_deterministic_backward_is_reproducible(kind):
+    case = (2051, 1024, 4, kind)
+    a, b = _grads(case, 'fp32', deterministic=True), _grads(case, 'fp32', deterministic=True)
+    assert torch.equal(a['dz'], b['dz']) and torch.equal(a['de'], b['de']) and torch.equal(a['idx'], b['idx'])
+    assert torch.equal(a['sse'], b['sse']) and torch.equal(a['loss'], b['loss'])      # the stage sums are added in block order too
+    d = _grads(case, 'fp32')
+    assert torch.equal(a['idx'], d['idx']) and torch.equal(a['dz'], d['dz'])
+    z, e = R.make_case(*case)
+    _, _, dz, de = R.gradients(z, e, a['idx'].cpu(), a['dq'], BETA)
+    close(f'{kind} deterministic de vs float64', a['de'].cpu(), de, rtol=1e-4, atol=1e-7)
+    close(f'{kind} deterministic de vs default', a['de'].cpu(), d['de'].cpu(), rtol=1e-4, atol=1e-7)
+    close(f'{kind} deterministic dz vs float64', a['dz'].cpu(), dz, rtol=1e-5, atol=1e-7)
+
+
+# ---------------------------------------------------------------------------------------------- 7. model level
+AE = dict(channels=32, num_res_blocks=1, channel_multipliers=(1, 2))
+TC = dict(lr=1e-3, betas=(0.0, 0.99), eps=1e-8, weight_decay=1e-4, warmup_epochs=None, decay_epochs=None)
+
+
+def _qc(dim):
+    return dict(num_embeddings=64, embedding_dim=dim, reinit_every_n_epochs=None, type='residual',
+                params=dict(commitment_cost=0.25, depth=3))
+
+
+def _images(seed=3, b=4):
+    return torch.rand(b, 3, 32, 32, generator=torch.Generator().manual_seed(seed)).to(DEV)
+
+
+# embedding_dim 64 as the FSQ model test sizes it (the staged product path: D != 256), 256 the fused kernels
+@pytest.mark.parametrize('dtype,dim', [(torch.float32, 64), (torch.bfloat16, 64), (torch.float32, 256), (torch.bfloat16, 256)],
+                         ids=['fp32-D64', 'bf16-D64', 'fp32-D256', 'bf16-D256'])
+def test_model_step_tokens_roundtrip_and_checkpoint(dtype, dim, tmp_path):
+    torch.manual_seed(0)
+    m = model_mod.VQVAE(32, AE, _qc(dim), None, TC, compute_dtype=dtype).to(DEV).train()
+    assert ops.rvq_fused_serves(m.quantizer.codebook.weight) == (dim == 256)
+    tr = trainer_mod.MiniTrainer(num_training_batches=10)
+    tr.attach(m)
+    m.on_train_start()
+    images = _images()
+    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    loss = tr.train_batch(m, images, 0)
+    torch.cuda.synchronize()
+    assert np.isfinite(loss.item()) and float(m.logged['train/quant_loss']) > 0.0
+    qz = m.quantizer
+    assert qz.last_hist.numel() == 64 and int(qz.last_hist.sum()) == 4 * 64 * 3
+    assert tuple(qz.last_depth_hist.shape) == (3, 64) and [int(v) for v in qz.last_depth_hist.sum(1)] == [4 * 64] * 3
+    assert tuple(qz.last_stage_sse.shape) == (3,) and bool((qz.last_stage_sse > 0).all())
+    assert int(m.train_epoch_usage_count.sum()) == 4 * 64 * 3
+    after = m.state_dict()
+    changed = {k for k in before if not torch.equal(before[k], after[k])}
+    assert {'quantizer.codebook.weight', 'encoder.conv_in.weight', 'decoder.conv_out.weight'} <= changed
+
+    m.eval()
+    with torch.no_grad():
+        tokens = m.get_tokens(images)
+        assert tokens.dtype == torch.int64 and tuple(tokens.shape) == (4, 64, 3)
+        assert tuple(m.quantize(images).shape) == (4, 64, dim)
+        # (the autoencoder's GroupNorm sums are combined in arrival order by default: bits are compared in deterministic mode)
+        ops.set_deterministic(True)
+        try:
+            tokens_det = m.get_tokens(images)
+            assert torch.equal(m.reconstruct_from_tokens(tokens_det), m.reconstruct(images))
+        finally:
+            ops.set_deterministic(False)
+        # dead codes are re-initialised from the usage pooled over the stages
+        usage = qz.get_codebook_usage(m.train_epoch_usage_count.float())[0]
+        dead = usage == 0
+        book = qz.codebook.weight.detach().clone()
+        qz.reinit_unused_codes(usage)
+        assert torch.equal(qz.codebook.weight[~dead], book[~dead])
+        if bool(dead.any()):
+            live = book[~dead]
+            assert all(bool((live == row).all(1).any()) for row in qz.codebook.weight[dead])
+        ops.refresh_vq_prepared()
+        tokens = m.get_tokens(images)
+    path = str(tmp_path / 'rvq.ckpt')
+    tr.save_checkpoint(m, path)
+    torch.manual_seed(1)
+    m2 = model_mod.VQVAE(32, AE, _qc(dim), None, TC, compute_dtype=dtype).to(DEV)
+    t2 = trainer_mod.MiniTrainer(num_training_batches=10)
+    t2.attach(m2)
+    t2.load_checkpoint(m2, path)
+    m2.eval()
+    assert torch.equal(m2.quantizer.codebook.weight, m.quantizer.codebook.weight)
+    assert torch.equal(m2.get_tokens(images), tokens)
+
+
+# ---------------------------------------------------------------------------------------------- 8. graph replay
+@pytest.mark.parametrize('deterministic', [True, False], ids=['deterministic', 'default'])
+def test_captured_forward_backward_replays(deterministic):
+    n, k, depth = 2051, 1024, 4
+    z0, e0 = dev_case((n, k, depth, 'scale1'))
+    gen = torch.Generator().manual_seed(23)
+    dq0 = torch.randn(n, R.D, generator=gen).to(DEV)
+    step = (torch.randn(k, R.D, generator=gen) * 0.05).to(DEV)           # what an optimizer step does to the codebook
+    img = lambda t: t.view(1, n, 1, R.D).permute(0, 3, 1, 2)
+
+    def run(z, cb, dq):
+        q, idx, loss, hist, _, _ = ops.RVQLookupFn.apply(img(z), cb, BETA, depth, torch.float32)
+        dz, de = torch.autograd.grad([q, loss], [z, cb], [img(dq), torch.ones((), device=DEV)])
+        return q, idx, loss, hist, dz, de
+
+    ops.set_deterministic(deterministic)
+    try:
+        cb = torch.nn.Parameter(e0.clone())
+        z = z0.clone().requires_grad_(True)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            run(z, cb, dq0)                                               # first launches, workspaces and the prepared codebook: outside
+            torch.cuda.synchronize()
+            graph, update = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                got = run(z, cb, dq0)
+            with torch.cuda.graph(update, stream=side):
+                with torch.no_grad():
+                    cb.add_(step)
+        torch.cuda.current_stream().wait_stream(side)
+        for round_ in range(2):
+            graph.replay()
+            torch.cuda.synchronize()
+            replayed = [t.detach().clone() for t in got]
+            want = run(z, cb, dq0)
+            torch.cuda.synchronize()
+            for name, a, b in zip(('q', 'idx', 'loss', 'hist', 'dz', 'de'), replayed, want):
+                if deterministic or name in ('q', 'idx', 'hist', 'dz'):
+                    assert torch.equal(a, b), (round_, name)
+                else:
+                    close(f'replay {round_} {name}', a.cpu(), b.detach().cpu(), rtol=1e-5 if name == 'loss' else 1e-4,
+                          atol=0.0 if name == 'loss' else 1e-7)
+            if round_ == 0:
+                first_idx = replayed[1]
+                update.replay()                                           # the codebook changes under the captured step ...
+                ops.refresh_vq_prepared(data_ptr=cb.data_ptr())           # ... and the prepared workspace follows, as after an optimizer step
+        assert not torch.equal(first_idx, replayed[1])                    # the second replay ranked against the NEW codebook
+    finally:
+        ops.set_deterministic(False)
+
+
+# ---------------------------------------------------------------------------------------------- 9. entry points
+SMALL = ['--set', 'image_size=32', '--set', 'autoencoder.channels=32', '--set', 'autoencoder.num_res_blocks=1',
+         '--set', 'autoencoder.channel_multipliers=[1, 2]', '--set', 'quantizer.num_embeddings=64', '--set', 'quantizer.params.depth=3',
+         '--set', 'training.cumulative_bs=4']
+
+
+def test_entry_points(tmp_path, capsys):
+    train = importlib.import_module(PKG + '.train')
+    ev = importlib.import_module(PKG + '.evaluate')
+    conf = os.path.join(ROOT, 'example_confs', 'residual_vqvae.yaml')
+    common = ['--params_file', conf] + SMALL + ['--max_epochs', '1', '--batches_per_epoch', '2', '--seed', '0', '--dtype', 'f32']
+    capsys.readouterr()
+    loss = train.main(common + ['--save_path', str(tmp_path), '--run_name', 'rvq'])
+    out = capsys.readouterr().out
+    assert loss is not None and np.isfinite(loss)
+    assert 'eager launches' not in out                                                  # the graph was captured, not given up
+    ckpt = str(tmp_path / 'rvq' / 'epoch=00.ckpt')
+    assert os.path.exists(ckpt)
+    small = tmp_path / 'conf.yaml'
+    small.write_text('image_size: 32\nautoencoder:\n  channels: 32\n  num_res_blocks: 1\n  channel_multipliers: [1, 2]\n'
+                     'quantizer:\n  num_embeddings: 64\n  embedding_dim: 256\n  type: residual\n  params:\n'
+                     '    commitment_cost: 0.25\n    depth: 3\n  reinit_every_n_epochs:\n')
+    pt = str(tmp_path / 'test.pt')
+    torch.save(torch.rand(8, 3, 32, 32, generator=torch.Generator().manual_seed(5)), pt)
+    capsys.readouterr()
+    res = ev.main(['--params_file', str(small), '--batch_size', '4', '--seed', '0', '--loading_path', ckpt, '--dtype', 'f32',
+                   '--dataset_path', pt])
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    assert json.loads(lines[-1]) == res
+    assert {'mse', 'psnr', 'ssim', 'used_codebook', 'perplexity'} <= set(res)
+    assert 0.0 < res['used_codebook'] <= 100.0 and 1.0 <= res['perplexity'] <= 64.0     # pooled usage of the 64 codes

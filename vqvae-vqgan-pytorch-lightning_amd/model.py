@@ -27,7 +27,7 @@ from torch import nn
 from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
-from .modules.vector_quantizers import (EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer,
+from .modules.vector_quantizers import (EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer, ResidualVectorQuantizer,
                                         VectorQuantizer)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
@@ -124,6 +124,11 @@ class VQVAE(BaseVQVAE, _LightningBase):
             if self.reinit_every_n_epochs is not None:
                 raise ValueError('fsq has no learned codebook: reinit_every_n_epochs must be empty')
             self.quantizer = FSQuantizer(self.cb_size, self.latent_dim, qp['levels'])
+        elif qt == 'residual':
+            depth = int(qp.get('depth', 4))
+            if not 1 <= depth <= 8:
+                raise ValueError(f'residual quantizer: depth must be between 1 and 8, got {depth}')
+            self.quantizer = ResidualVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']), depth)
         else:
             raise ValueError(f'unrecognized quantizer: {qt}')
 
@@ -529,7 +534,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
 
     @torch.no_grad()
     def reconstruct_from_tokens(self, tokens: torch.Tensor) -> torch.Tensor:
-        b, s = tokens.shape
+        b, s = tokens.shape[:2]                            # (B, S), or (B, S, depth) token stacks of the residual quantizer
         side = int(round(s ** 0.5))
         q = self.quantizer.codes_to_vec(tokens).view(b, side, side, self.latent_dim).permute(0, 3, 1, 2)
         return self.preprocess_visualization(self.decoder(q).float())

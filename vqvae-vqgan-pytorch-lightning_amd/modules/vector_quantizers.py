@@ -1,7 +1,7 @@
 """Quantizers on the vqk kernels; same classes / ctor signatures / return conventions as the reference's
 ``vqvae/modules/vector_quantizers.py`` (VectorQuantizer :8-84, EMAVectorQuantizer :87-203,
 EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274); ``FSQuantizer`` (finite scalar quantization, no counterpart in
-the reference) is the fifth member of the family.
+the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (residual quantization, no counterpart either) the sixth.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -246,3 +246,43 @@ class FSQuantizer(BaseVectorQuantizer):
 
     def reinit_unused_codes(self, codebook_usage: torch.Tensor):
         raise RuntimeError('fsq: there is no learned codebook to re-initialise')
+
+
+class ResidualVectorQuantizer(BaseVectorQuantizer):
+    """Residual quantization (Lee et al. 2022, RQ-VAE; SoundStream): every latent vector is approximated by the sum of ``depth`` codes
+    of ONE shared codebook, stage q quantizing what the stages before it left over -- K^depth effective codes per position from the
+    codebook memory of the standard quantizer, and a coarse-to-fine token stack (B, H*W, depth).  Every stage carries the standard
+    quantizer's codebook + commitment loss on its own input residual.  One fused forward kernel for all stages and one backward kernel
+    (csrc/rvq.hip).  Depth 1 is the standard quantizer.  The codebook (``codebook.weight``), its initialisation, usage statistics and
+    dead-code re-initialisation are the base class's: ``last_hist`` is the usage POOLED over the stages (total N * depth),
+    ``last_depth_hist`` [depth, K] the per-stage table (later stages collapse first), ``last_stage_sse`` [depth] the residual energy
+    sum |r_q|^2 left after each stage."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25, depth: int = 4):
+        depth = int(depth)
+        if not 1 <= depth <= ops.RVQ_MAX_DEPTH:
+            raise ValueError(f'residual quantizer: depth must be between 1 and {ops.RVQ_MAX_DEPTH}, got {depth}')
+        super().__init__(num_embeddings, embedding_dim)
+        self.commitment_cost = commitment_cost
+        self.depth = depth
+        self.last_depth_hist = None
+        self.last_stage_sse = None
+
+    def forward(self, x: torch.Tensor):
+        q, idx, loss, hist, depth_hist, stage_sse = ops.RVQLookupFn.apply(x, self.codebook.weight, self.commitment_cost, self.depth,
+                                                                          self.compute_dtype)
+        self.last_hist, self.last_depth_hist, self.last_stage_sse = hist, depth_hist, stage_sse
+        return q, idx, loss
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        """x (B,D,H,W) -> codes (B,H*W,depth) int64"""
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.rvq_assign(_flat_view(z), self.codebook.weight, self.depth).view(x.shape[0], -1, self.depth)
+
+    @torch.no_grad()
+    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes (B,N,depth) -> (B,N,D): the stage-order sum of the codes, the bits the forward hands to the decoder"""
+        if codes.dim() != 3 or not 1 <= codes.shape[-1] <= ops.RVQ_MAX_DEPTH:
+            raise ValueError(f'residual quantizer: codes must be (B, N, depth), got {tuple(codes.shape)}')
+        return ops.rvq_decode(codes, self.codebook.weight)
