@@ -205,6 +205,31 @@ int64_t vqk_rvq_backward_ws_bytes(int64_t n, int d, int depth);
 int vqk_rvq_backward_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
                          int depth, float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws,
                          int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- k-means codebook initialisation ---------
+ * k-means++ seeding and the centroid update of a Lloyd iteration (csrc/kmeans.hip); the assignment and the per-cluster sums of an
+ * iteration are vqk_vq_assign*_f32 and vqk_ema_stats*_f32.  No call allocates, synchronises or reads anything back to the host: a
+ * caller loops j = 0 .. k - 1 on one stream.
+ * vqk_kmeans_seed_step_f32 = pick j of k.  x[N][D] fp32 rows, D % 4 == 0, 4 <= D <= 1024, 1 <= N <= 2^36, 0 <= j < k (VQK_ERR_SHAPE);
+ * device arrays picks[k] int64, u[k] FLOAT64 draws in [0, 1), mind[N] fp32, total[k] float64 (optional); ws: >= vqk_kmeans_seed_ws_bytes(N)
+ * bytes (VQK_ERR_WORKSPACE; one float64 per block of 64 rows), x and ws 16-byte aligned (VQK_ERR_ALIGN).
+ *   j == 0 (one launch): picks[0] = min(floor(u[0] N), N - 1); mind[i] = +inf for every i -- the caller need not initialise it;
+ *           total[0] = +inf.
+ *   j >= 1 (two launches): c = x[picks[j-1]], read on the device;  mind[i] = min(mind[i], sum_d (x[i,d] - c[d])^2) -- the difference
+ *           form, never |x|^2 + |c|^2 - 2 x.c: a row bit-equal to c gets exactly 0 and near rows do not cancel (one fp32 fma chain per
+ *           lane, an xor tree over the lanes of the row: relative error <= (D + 3) 2^-24);  total[j] = S = sum_i mind[i] in float64;
+ *           with P the float64 running sums of mind in row order and t = u[j] S:  picks[j] = the smallest i with P[i] > t;  where
+ *           rounding leaves none, the largest i with mind[i] > 0;  S == 0 (fewer distinct rows than centres): min(floor(u[j] N), N - 1).
+ *           A pick always has mind > 0 while S > 0, so picks are pairwise distinct rows until the distinct rows run out.
+ * Every sum is added in an order fixed by (N, D): the same bits of mind, total and the same picks on every run.  P is the running sum
+ * of a fixed three-level tree over the 64-row blocks (csrc/kmeans.hip), within N 2^-52 S of any other float64 prefix sum. */
+int64_t vqk_kmeans_seed_ws_bytes(int64_t n);
+int vqk_kmeans_seed_step_f32(const float* x, int64_t n, int d, int k, int j, const double* u, int64_t* picks, float* mind,
+                             double* total /* optional */, void* ws, int64_t ws_bytes, void* stream);
+/* Centroid update, ONE launch: centres[c] = sums[c] / counts[c] (correctly rounded fp32 division) where counts[c] > 0, an empty cluster
+ * keeps its centre bit for bit; moved[c] = |c_new - c_old|^2 (float64 sum rounded once; 0 for an empty cluster; optional).  counts[k] and
+ * sums[k][D] are what vqk_ema_stats*_f32 wrote (sums at any 4-byte alignment: the packed buffer puts it k floats in); centres[k][D]
+ * 16-byte aligned (VQK_ERR_ALIGN), D % 4 == 0 (VQK_ERR_SHAPE). */
+int vqk_kmeans_update_f32(const float* counts, const float* sums, int k, int d, float* centres, float* moved /* optional */, void* stream);
 /* EMA statistics (vector_quantizers.py:159-169): counts[k] += 1, dw[idx] += z (both pre-zeroed) ...  fp32 atomics in arrival order;
  * in deterministic mode (this entry and the fused one): one block per code adds its rows in row order, no atomics -- the same bits every run. */
 int vqk_ema_stats_f32(const float* z, const int64_t* idx, int64_t n, int k, int d,

@@ -19,6 +19,7 @@ from __future__ import annotations
 from typing import Any
 
 import os
+import time
 
 import torch
 import torch.distributed as dist
@@ -28,7 +29,7 @@ from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
 from .modules.vector_quantizers import (EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer, ResidualVectorQuantizer,
-                                        VectorQuantizer)
+                                        VectorQuantizer, _flat_view, gather_latent_sample)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
 from .optim import FlatAdamW
@@ -105,6 +106,9 @@ class VQVAE(BaseVQVAE, _LightningBase):
         self.scalar_log = None
 
         qt, qp = q_conf['type'], q_conf['params']
+        # optional `codebook_init` block of the quantizer config: a k-means start from encoder latents (init_codebook_from_batches);
+        # absent or empty: the uniform start
+        self.codebook_init = self._parse_codebook_init(q_conf.get('codebook_init'), qt, self.cb_size)
         if qt == 'standard':
             self.quantizer = VectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']))
         elif qt == 'ema':
@@ -157,6 +161,62 @@ class VQVAE(BaseVQVAE, _LightningBase):
             for m in self.criterion.modules():
                 if hasattr(m, 'conv_products'):
                     m.conv_products = 'fp32'
+
+    @staticmethod
+    def _parse_codebook_init(block, qt: str, cb_size: int):
+        """{'method': 'kmeans', 'samples': latent rows collected (>= num_embeddings), 'iters': Lloyd iterations after the k-means++
+        seeding (0 = the seeds)} -> the same with defaults filled in; None for an absent / empty block"""
+        if not block:
+            return None
+        if qt in ('gumbel', 'fsq'):
+            raise ValueError(f'quantizer.codebook_init: the {qt} quantizer has no codebook a k-means start would serve '
+                             f'({"no distance lookup" if qt == "gumbel" else "no learned codebook"})')
+        unknown = set(block) - {'method', 'samples', 'iters'}
+        if unknown:
+            raise ValueError(f'quantizer.codebook_init: unknown keys {sorted(unknown)}')
+        method = block.get('method', 'kmeans')
+        if method != 'kmeans':
+            raise ValueError(f"quantizer.codebook_init.method: 'kmeans' is the one method, got {method!r}")
+        samples, iters = int(block.get('samples', 65536)), int(block.get('iters', 10))
+        if samples < cb_size:
+            raise ValueError(f'quantizer.codebook_init.samples = {samples} is fewer than num_embeddings = {cb_size}')
+        if iters < 0:
+            raise ValueError(f'quantizer.codebook_init.iters must be >= 0, got {iters}')
+        return dict(method=method, samples=samples, iters=iters)
+
+    @torch.no_grad()
+    def init_codebook_from_batches(self, batches, seed: int) -> dict:
+        """The data-dependent codebook start the config's ``quantizer.codebook_init`` block asks for: the encoder runs (no gradient,
+        no augmentation) over as many of ``batches`` as it takes to hold ``samples`` latent rows -- fp32, flattened as the quantizer
+        flattens them; data parallel: samples // world per rank, one all-gather forms the common sample -- and the quantizer's
+        ``init_codebook_from_data`` fits k-means to them with the draws ``torch.rand(K, generator=manual_seed(seed), float64)``.
+        Call it after the optimizer is attached (the codebook is written in place) and BEFORE a hipGraph capture.
+        Returns dict(samples, iters, inertia, used, seconds)."""
+        conf = self.codebook_init
+        if conf is None:
+            raise RuntimeError('init_codebook_from_batches: the quantizer config holds no codebook_init block')
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        want = conf['samples'] // world
+        t0 = time.perf_counter()
+        rows, have, rows_per_batch = [], 0, None
+        for batch in batches:
+            images = batch[0] if isinstance(batch, (tuple, list)) else batch
+            x_pad, _ = self._preprocess_train(images, False)
+            flat = _flat_view(ops.nhwc(self.encoder(x_pad).to(torch.float32))).clone()
+            rows_per_batch = rows_per_batch or flat.shape[0]
+            rows.append(flat)
+            have += flat.shape[0]
+            if have >= want:
+                break
+        if have < want:
+            raise ValueError(f'init_codebook_from_batches: the batches hold {have} latent rows per rank, codebook_init.samples asks for {want}')
+        sample = gather_latent_sample(torch.cat(rows)[:want].contiguous())
+        if sample.shape[0] < self.cb_size:
+            raise ValueError(f'init_codebook_from_batches: {sample.shape[0]} latent rows over {world} ranks are fewer than num_embeddings = {self.cb_size}')
+        u = torch.rand(self.cb_size, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+        fit = self.quantizer.init_codebook_from_data(sample, conf['iters'], u, rows_per_step=rows_per_batch * world)
+        inertia, used = float(fit['inertia']), float(fit['used'])       # the one host read: the fit is over
+        return dict(samples=int(sample.shape[0]), iters=conf['iters'], inertia=inertia, used=used, seconds=time.perf_counter() - t0)
 
     # ------------------------------------------------------------------ forward (model.py:151-161)
     def forward(self, x: torch.Tensor):

@@ -24,6 +24,28 @@ class BaseVectorQuantizer(ABC, nn.Module):
     def init_codebook(self) -> None:
         nn.init.uniform_(self.codebook.weight, -1 / self.num_embeddings, 1 / self.num_embeddings)
 
+    @torch.no_grad()
+    def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
+        """Data-dependent start: the codebook becomes the k-means centres of ``flat_z`` [N, D] (encoder latents as the quantizer
+        flattens them, fp32, on the GPU; N >= K) -- k-means++ seeding from the float64 draws ``u`` [K], then ``iters`` Lloyd
+        iterations (``ops.kmeans_fit``).  Written IN PLACE (the parameter may live in the optimizer's flat arena) and followed by a
+        refresh of the cached lookup workspace.  Data parallel: every rank fits the same gathered sample, then the codebook (and the
+        cluster sizes) are broadcast from rank 0 so that the replicas are bit-identical.  ``rows_per_step``: latent rows of one
+        training step over all ranks, for quantizers that keep running statistics.  Returns the fit (``ops.kmeans_fit``)."""
+        from ... import ops
+        w = self.codebook.weight
+        if flat_z.dim() != 2 or flat_z.shape[1] != w.shape[1]:
+            raise ValueError(f'init_codebook_from_data: latents must be [N, {w.shape[1]}], got {tuple(flat_z.shape)}')
+        fit = ops.kmeans_fit(flat_z.detach().to(torch.float32).contiguous(), self.num_embeddings, iters, u)
+        w.data.copy_(fit['centres'])
+        fit['counts'] = fit['counts'].to(torch.float32)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            from ...optim import broadcast_
+            broadcast_(w.data, src=0)
+            broadcast_(fit['counts'], src=0)
+        ops.refresh_vq_prepared(data_ptr=w.data_ptr())       # written in place: the cached filter workspace must follow
+        return fit
+
     @abstractmethod
     def forward(self, x: torch.Tensor):
         """x (B,D,H,W) -> (quantized (B,D,H,W), codes (B,H*W) int64 detached, latent loss 0-dim)"""

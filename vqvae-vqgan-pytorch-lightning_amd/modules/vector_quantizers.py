@@ -36,6 +36,22 @@ def reduce_ema_stats(stats: torch.Tensor, local_batch: int, force_collective: bo
     return float(local_batch * world)
 
 
+def gather_latent_sample(rows: torch.Tensor) -> torch.Tensor:
+    """The common sample of the data-dependent codebook start (``VQVAE.init_codebook_from_batches``): every data-parallel rank hands
+    in the SAME number of latent rows [n, D]; ONE all-gather returns the rank-ordered concatenation [world * n, D] on every rank (the
+    rows themselves without a process group).  Host logic only (no kernel): callable on CPU tensors under gloo."""
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    if world == 1:
+        return rows
+    from ..optim import _track
+    rows = rows.contiguous()
+    out = torch.empty((world * rows.shape[0],) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    work = _track(dist.all_gather(list(out.chunk(world, 0)), rows, async_op=True))      # async + wait: see optim.all_reduce_sum
+    if work is not None:
+        work.wait()
+    return out
+
+
 def _flat_view(z: torch.Tensor):
     b, d, h, w = z.shape
     return z.permute(0, 2, 3, 1).reshape(b * h * w, d)
@@ -94,6 +110,17 @@ class EMAVectorQuantizer(BaseVectorQuantizer):
                     ops.ema_apply(stats, self.ema_count, self.ema_weight, self.codebook.weight.data, self.decay,
                                   self.epsilon, batch)
         return q, idx, loss
+
+    @torch.no_grad()
+    def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
+        """the base class's k-means start, plus the running statistics a long run of such batches converges to: ema_count = the
+        cluster sizes scaled from the sample to one training step (``rows_per_step`` latent rows over all ranks; default: the sample
+        itself), ema_weight = ema_count[:, None] * centres -- so that ema_weight / ema_count reproduces the codebook"""
+        fit = super().init_codebook_from_data(flat_z, iters, u, rows_per_step)
+        rows = float(flat_z.shape[0] if rows_per_step is None else rows_per_step)
+        self.ema_count.copy_(fit['counts'] * (rows / float(flat_z.shape[0])))
+        self.ema_weight.copy_(self.ema_count[:, None] * self.codebook.weight.data)
+        return fit
 
     @torch.no_grad()
     def finish_update(self, force_collective: bool = False) -> None:
@@ -160,6 +187,9 @@ class GumbelVectorQuantizer(BaseVectorQuantizer):
                                                 self.sched_dev if self.training else None)
         self.last_hist = hist
         return q, idx, kl
+
+    def init_codebook_from_data(self, *args, **kwargs):
+        raise ValueError('gumbel: the quantizer does no distance lookup, there is nothing a k-means start of the codebook would serve')
 
     def get_consts(self):
         return self.temp, self.kl_cost
@@ -247,6 +277,9 @@ class FSQuantizer(BaseVectorQuantizer):
     def reinit_unused_codes(self, codebook_usage: torch.Tensor):
         raise RuntimeError('fsq: there is no learned codebook to re-initialise')
 
+    def init_codebook_from_data(self, *args, **kwargs):
+        raise ValueError('fsq: there is no learned codebook to initialise from data')
+
 
 class ResidualVectorQuantizer(BaseVectorQuantizer):
     """Residual quantization (Lee et al. 2022, RQ-VAE; SoundStream): every latent vector is approximated by the sum of ``depth`` codes
@@ -254,7 +287,8 @@ class ResidualVectorQuantizer(BaseVectorQuantizer):
     codebook memory of the standard quantizer, and a coarse-to-fine token stack (B, H*W, depth).  Every stage carries the standard
     quantizer's codebook + commitment loss on its own input residual.  One fused forward kernel for all stages and one backward kernel
     (csrc/rvq.hip).  Depth 1 is the standard quantizer.  The codebook (``codebook.weight``), its initialisation, usage statistics and
-    dead-code re-initialisation are the base class's: ``last_hist`` is the usage POOLED over the stages (total N * depth),
+    dead-code re-initialisation are the base class's; ``init_codebook_from_data`` is inherited as it is: the shared codebook is fitted
+    to z, the FIRST stage's input (the later stages' residuals only exist once there is a codebook): ``last_hist`` is the usage POOLED over the stages (total N * depth),
     ``last_depth_hist`` [depth, K] the per-stage table (later stages collapse first), ``last_stage_sse`` [depth] the residual energy
     sum |r_q|^2 left after each stage."""
 

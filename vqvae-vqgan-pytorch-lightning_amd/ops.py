@@ -2248,4 +2248,5 @@ if TRACE:
 from ._ops_vq import *        # noqa: E402,F401,F403  quantizers
 from ._ops_fsq import *       # noqa: E402,F401,F403  finite scalar quantizer
 from ._ops_rvq import *       # noqa: E402,F401,F403  residual quantizer
+from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins

@@ -15,7 +15,9 @@ Out of scope: the ffcv data module and wandb.  Batches come from ``--
 layout (``train/``, optionally ``validation/``) is read through ``data.get_datamodule`` (host threads decode, one HIP kernel
 resizes: data.py); a ``.pt`` / ``.npy`` tensor file holds images [M,3,S,S] in [0,1], resident on the device; omitted: synthetic
 U(0,1) batches (the benchmark's input).  ``--image_log_dir`` writes the reference's reconstruction panels (model.py:442-456) as PNG
-files instead of ``wandb.Image``s (imagelog.py), under hipGraph replay too.
+files instead of ``wandb.Image``s (imagelog.py), under hipGraph replay too.  A ``quantizer.codebook_init`` block in the config starts
+the codebook from k-means over encoder latents of the first training batches (``VQVAE.init_codebook_from_batches``) unless the run
+resumes from ``--loading_path``.
 """
 from __future__ import annotations
 
@@ -42,13 +44,15 @@ def derive_run_config(conf: dict, world_size: int, overrides: dict | None = None
     """Everything ``train.py:55-103,139-140`` derives from a config file and the device count, as one dict:
     image_size, ae_conf, q_conf, l_conf, t_conf, batch_size_per_device, cumulative_batch_size, learning_rate, max_epochs,
     use_adversarial.  ``overrides``: optional ``{'quantizer.num_embeddings': 8192, 'loss.adversarial_params.start_epoch': 0,
-    'training.cumulative_bs': 512, ...}`` applied to the loaded YAML first (BASELINE.json quotes some configs with a
+    'training.cumulative_bs': 512, 'quantizer.codebook_init.method': 'kmeans', ...}`` applied to the loaded YAML first (BASELINE.json quotes some configs with a
     different codebook size than the YAML carries)."""
     conf = _deep_copy(conf)
     for dotted, value in (overrides or {}).items():
         node = conf
         *path, leaf = dotted.split('.')
         for key in path:
+            if key == 'codebook_init' and not node.get(key):         # the one optional block: an override may bring it along
+                node[key] = {}
             node = node[key]
         node[leaf] = value
     if world_size < 1:
@@ -228,6 +232,11 @@ def main(argv=None):
         print(f'[INFO] batch size per device: {run["batch_size_per_device"]}')
         print(f'[INFO] cumulative batch size (all devices): {run["cumulative_batch_size"]}')
         print(f'[INFO] final learning rate: {run["learning_rate"]}')
+    if model.codebook_init is not None and args.loading_path is None:    # a resumed run keeps its checkpointed codebook (init_cb=False)
+        info = model.init_codebook_from_batches(batches, args.seed)       # in place, before the capture below
+        if rank == 0:
+            print(f'[INFO] codebook init: k-means on {info["samples"]} latent rows, {info["iters"]} Lloyd iterations, inertia '
+                  f'{info["inertia"]:.6g}, {100.0 * info["used"]:.1f}% of the codes non-empty, {info["seconds"]:.2f} s', flush=True)
     model.on_train_start()
     graphed = False
     if not args.no_graph:
