@@ -766,9 +766,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_stream_kernel(const bf16_raw* 
         const bool has_next = u + 1 < units;
         if (!has_next) { ntj = tj; nc = c; }                     // clamp: loads stay unconditional
         const TilePos nxt = (ntj == tj) ? cur : tile_pos(ntj);
-#ifndef VQK_ABL_NOHALO
         load_halo(nxt, nc);                                      // in flight during this unit's MFMAs
-#endif
         const char* wnxt[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) wnxt[j] = unit_w(nxt.nt, nc, j);
@@ -832,11 +830,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_stream_kernel(const bf16_raw* 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifdef VQK_ABL_NOEPI
-        if (c == nch - 1 && g.n < 0) {                             // timing-only ablation: the epilogue is never executed
-#else
         if (c == nch - 1) {                                        // tile finished: epilogue, accumulators reset
-#endif
             const int n0 = cur.nt * COT;
             // Straight-line fast paths (no activation, unit gains, full cout tile): the epilogue runs on the same
             // SIMD as the MFMAs, so every branch / select per element is stolen from the matrix pipe.
@@ -973,9 +967,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_stream_kernel(const bf16_raw* 
             }
             }
         }
-#ifndef VQK_ABL_NOHALO
         if (has_next) store_halo(smem + ((u + 1) & 1) * BUF);
-#endif
         __syncthreads();
         cur = nxt; tj = ntj; c = nc;
 #pragma unroll

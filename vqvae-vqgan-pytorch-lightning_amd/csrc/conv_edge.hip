@@ -45,9 +45,6 @@ __device__ __forceinline__ bf16x8_t tr_frag(const char* tile, int k0, int cbase,
     return __builtin_bit_cast(bf16x8_t, v);
 }
 
-#ifndef VQK_EDGE_ABL
-#define VQK_EDGE_ABL 0       // timing-only ablation bits (tools/ab_build.sh): 1 im2col pieces from the zero page, 2 no wide pieces, 4 no MFMA loop
-#endif
 constexpr int EDGE_CW = 128;                                     // wide channels
 constexpr int EDGE_PIX = 128;                                    // pixels per patch
 constexpr int EDGE_WIDE_B = EDGE_PIX * EDGE_CW * 2;              // 32768
@@ -96,8 +93,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_thin_kernel(const bf16_r
             const int q = wave * 8 + t;
             const int row = 4 * q + (lane >> 4), pc = lane & 15;
             const int lc = pc ^ ((row & 3) << 2);
-            if (!((VQK_EDGE_ABL & 2) && n > 0)) glds16(wide + (p0 + row) * EDGE_CW + lc * 8, st + q * 1024);
-            else glds16(zeros, st + q * 1024);
+            glds16(wide + (p0 + row) * EDGE_CW + lc * 8, st + q * 1024);
         }
         const bf16_raw* timg = thin + (int64_t)img * hw * 8;
 #pragma unroll
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_thin_kernel(const bf16_r
             if (q < 18) {
                 const int yy = y0 + s_ry[t] + s_ty[t], xx = x0 + s_rx[t] + s_tx[t];
                 const void* src = zeros;
-                if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w && !((VQK_EDGE_ABL & 1) && n > 0))
+                if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w)
                     src = timg + ((int64_t)yy * w + xx) * 8;
                 glds16(src, st + EDGE_WIDE_B + q * 1024);
             } else {
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_thin_kernel(const bf16_r
         if (i + 2 < cnt) issue(b + (i + 2) * G, (i + 2) % 3);
         const char* st = smem + (i % 3) * EDGE_STAGE;
 #pragma unroll
-        for (int k0 = 0; k0 < (((VQK_EDGE_ABL & 4) && n > 0) ? 0 : EDGE_PIX); k0 += 16) {
+        for (int k0 = 0; k0 < EDGE_PIX; k0 += 16) {
             const bf16x8_t a = tr_frag<EDGE_CW * 2, true>(st, k0, 32 * wave, lane);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {

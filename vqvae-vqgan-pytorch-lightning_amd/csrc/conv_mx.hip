@@ -41,9 +41,6 @@ using vqkd::ConvGeom;
 using vqkd::pack_bf16x2;
 using vqkd::xcd_remap;
 
-#ifndef VQK_MXABL
-#define VQK_MXABL 0          // timing-only ablation bits (tools/ab_build.sh): never set in the shipped build (32: half the weight stream)
-#endif
 #ifndef VQK_MX_RD
 #define VQK_MX_RD 6          // weight ring depth in phases ((tap, k-substep) pairs; divides 18)
 #endif
@@ -151,10 +148,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
         return tp;
     };
     auto unit_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-    // VQK_MXABL & 64 (instrumented build, tools/mx_phase_probe.py): g.gn_ws is NOT a statistics workspace but a debug buffer -- every
-    // matrix wave leaves {cycles in its unit loop, cycles parked in the unit barrier, cycles parking tiles, units} there (s_memtime)
-    double* const gnws = (VQK_MXABL & 64) ? nullptr : g.gn_ws;
-    unsigned long long* const dbg = (VQK_MXABL & 64) ? reinterpret_cast<unsigned long long*>(g.gn_ws) : nullptr;
+    double* const gnws = g.gn_ws;                                // GroupNorm statistics workspace of the stored output (null: no sums)
 
     if (wave < 4) {
         // ================================================================= M waves: MFMA only
@@ -211,10 +205,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
         unit_barrier();                                          // the halo of unit 0 has landed
 
         int tj = 0, c = 0, bi = 0, t_next = 0;
-        unsigned long long t_bar = 0, t_park = 0, n_units = 0, t_c0 = 0, t_cl = 0, t_top = 0;     // (t_c0 / t_cl: MFMA sections of a tile's first / last unit)
-        const unsigned long long t_begin = (VQK_MXABL & 64) ? __builtin_amdgcn_s_memtime() : 0;
         for (;;) {
-            if (VQK_MXABL & 64) t_top = __builtin_amdgcn_s_memtime();
             // the id of the next tile is read one unit before it is needed (published two units earlier by the first X wave)
             if (c == nun - 2) t_next = next_id(tj + 1);
             const bool last_c = c == nun - 1, more = last_c && t_next < total_tiles;
@@ -272,12 +263,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
                         const int soff = (ph + RD >= NPH) ? wnxt[j] + (ph + RD - NPH) * 1024 : wcur[j] + (ph + RD) * 1024;
-                        // VQK_MXABL & 32 (timing only, round 4): the two pixel-half waves of a cout half load the SAME weight
-                        // fragments -- here the second wave keeps its stale ring instead: the kernel's L2 -> VGPR weight stream is
-                        // halved (L2 side) at NO cost for whatever would share it, i.e. an upper bound on what a shared stream can win
-                        // (same instruction stream: the second wave re-reads ONE fragment -- an L1 hit -- instead of skipping the load;
-                        // skipping it put a branch into the pinned phase and cost 7-10 %)
-                        bw[ph % RD][j] = wload(((VQK_MXABL & 32) && g.n > 0 && wm == 1) ? (soff & 1023) : soff);
+                        bw[ph % RD][j] = wload(soff);
                     }
                     if (VQK_MX_PIN) {
                         if (reads) {
@@ -292,9 +278,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            const unsigned long long t_a = (VQK_MXABL & 64) ? __builtin_amdgcn_s_memtime() : 0;
-            if (VQK_MXABL & 64) { if (c == 0) t_c0 += t_a - t_top; if (c == nun - 1) t_cl += t_a - t_top; }
-            if (c == nun - 1 && !((VQK_MXABL & 4) && g.n > 0)) {
+            if (c == nun - 1) {
                 // park the tile: lane (pixel p, half kg) holds couts j*32 + 8*rq + 4*kg + e of its wave's 64 -> 8-byte pieces
 #pragma unroll
                 for (int i = 0; i < NI; ++i)
@@ -307,24 +291,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
                             *reinterpret_cast<u32x2*>(smem + sbase[i] + (j * 32 + 8 * rq) * 2) = o;
                         }
             }
-            if (VQK_MXABL & 64) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the park's ds_writes are issued, not retired: count them as park)
-                const unsigned long long t_b = __builtin_amdgcn_s_memtime();
-                unit_barrier();
-                const unsigned long long t_c = __builtin_amdgcn_s_memtime();
-                t_park += t_b - t_a; t_bar += t_c - t_b; ++n_units;
-            } else
             unit_barrier();
             if (last_c) { if (!more) break; ++tj; }
             cur_nt = nxt_nt; c = nc;
             bi = bi == NBUF - 1 ? 0 : bi + 1;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) wcur[j] = wnxt[j];
-        }
-        if ((VQK_MXABL & 64) && dbg && lane == 0) {
-            unsigned long long* o = dbg + ((int64_t)blockIdx.x * 4 + wave) * 8;
-            o[0] = __builtin_amdgcn_s_memtime() - t_begin; o[1] = t_bar; o[2] = t_park; o[3] = n_units;
-            o[4] = t_c0; o[5] = t_cl; o[6] = (unsigned long long)nun; o[7] = 0;
         }
         return;
     }
@@ -370,7 +342,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
                 const int off = (flg[sl] & tb) ? OOB : base + rel[sl];
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     xsrd, (VQK_LDS void*)(smem + bufi * BUF + (xw + 4 * sl) * 1024), 16,
-                    (VQK_MXABL & 8) ? (off & 0x8003fff0) : off, 0, 0, VQK_MX_HALO_AUX);
+                    off, 0, 0, VQK_MX_HALO_AUX);
             }
         }
     };
@@ -426,7 +398,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
         }
     };
     // k0 .. k1: the output pieces of this call (round 6: a tile's drain is PACED over the next tile's units -- measured with the
-    // instrumented build, tools/mx_phase_probe.py: the matrix waves' unit beside a whole-tile drain took 6993 cycles against 5222 for a
+    // s_memtime build of profiles/round6_mx_phase_attribution.txt: the matrix waves' unit beside a whole-tile drain took 6993 cycles against 5222 for a
     // unit with quiet auxiliary waves, 128 -> 128 @256^2); `first` clears the statistics accumulators, `last` folds them
     float ga = 0.f, qa = 0.f, gb = 0.f, qb = 0.f;                // GroupNorm sums of the tile being drained: channels 0-3 / 4-7 of the thread's eight
     auto drain = [&](const OutPos& o, const u32x4 (&rv)[NR], int k0, int k1, bool first, bool last) {
@@ -483,29 +455,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
                 }
             } else {
                 const bool general = g.act != 0 || g.acc_scale != 1.0f || g.out_gain != 1.0f;     // wave-uniform
-                float abl_b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, abl_g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int k = 0; k < NP; ++k) {
                     if (k < k0 || k >= k1) continue;
                     float f[8], r[8];
                     unpack8(t[k], f);
                     unpack8(rv[k], r);
-                    if ((VQK_MXABL & 16) && g.n > 0) {
-                        // TIMING-ONLY experiment (profiles/round3_gn_bwd_fusion_ab.txt): the arithmetic a fused GroupNorm+SiLU
-                        // BACKWARD reduction would add to a data-gradient drain -- the residual operand stands in for the
-                        // GroupNorm input x (same bytes), per element: x_hat, u = gamma x_hat + beta, sigmoid, SiLU', t = dy SiLU',
-                        // two per-channel sums (d beta, d gamma).  Constants instead of per-group statistics; sums folded into
-                        // the statistics accumulators so that nothing is dead code.
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float xh = __fmaf_rn(r[e], 1.3f, -0.13f);
-                            const float u = __fmaf_rn(xh, 1.1f, 0.05f);
-                            const float sg = __frcp_rn(1.0f + __expf(-u));
-                            const float t = f[e] * (sg * (1.0f + u * (1.0f - sg)));
-                            abl_b[e] += t;
-                            abl_g[e] = __fmaf_rn(t, xh, abl_g[e]);
-                        }
-                    }
                     if (general) {                               // y = out_gain * act(acc * acc_scale + bias) + residual
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
@@ -520,10 +475,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
                     const u32x4 ov = pack8(f);
                     __builtin_amdgcn_raw_buffer_store_b128(ov, ysrd, res_off(o, k), 0, VQK_MX_NT);
                     if (want_stats) tally(ov);
-                }
-                if ((VQK_MXABL & 16) && g.n > 0) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { ga += abl_b[e]; qa += abl_g[e]; }
                 }
             }
         } else {
@@ -656,7 +607,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
             bump();
         }
         if (flush) { flush_stats(); flush = false; }
-        if (pending && !((VQK_MXABL & 2) && g.n > 0)) {          // a tile parked during unit u-1 (or earlier: paced) waits in the staging tile
+        if (pending) {                                           // a tile parked during unit u-1 (or earlier: paced) waits in the staging tile
             // paced: ceil(NP / (nun - 1)) pieces per interval over the next tile's units 0 .. nun-2 -- it has to be gone before that
             // tile is parked at the end of its unit nun-1 (the residual registers are reloaded in that interval, too)
             const int per = (VQK_MX_PACE && nun > 2) ? (NP + nun - 2) / (nun - 1) : NP;
@@ -675,7 +626,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
         }
         if constexpr (NBUF == 3) {
             look();
-            if (lvalid && !((VQK_MXABL & 1) && g.n > 0)) issue_halo(ltp, lc, lbuf);      // unit u+2
+            if (lvalid) issue_halo(ltp, lc, lbuf);      // unit u+2
             bump();
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

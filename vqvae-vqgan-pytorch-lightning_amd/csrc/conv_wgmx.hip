@@ -30,9 +30,6 @@ namespace {
 using vqkd::ConvGeom;
 using vqkd::xcd_remap;
 
-#ifndef VQK_WGMX_ABL
-#define VQK_WGMX_ABL 0       // timing-only ablation bits: 1 no pieces, 2 no atomic pass over dW
-#endif
 #ifndef VQK_WGMX_NST
 #define VQK_WGMX_NST 3       // LDS stages (3: 120 KiB, 4: all 160 KiB)
 #endif
@@ -173,7 +170,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw
             si = si == NST - 1 ? 0 : si + 1;
         }
         const int ci = ci0 + wj * 32 + (lane & 31);
-        if ((VQK_WGMX_ABL & 2) && g.n > 0 && acc[0][0] != 12345.678f) return;      // timing-only: no atomic pass
         if constexpr (NT == 4) {
             // G[ty][tx] of phase (a, b) stands for the taps ky in {ty ? (a ? 2 : 1) : 0 .. ty ? 2 : (a ? 1 : 0)}, kx likewise
 #pragma unroll
@@ -277,11 +273,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw
         }
     };
     auto issue = [&](int patch, int stage) {
-        if ((VQK_WGMX_ABL & 1) && g.n > 0) {                     // timing-only: ten harmless loads keep the wait counts valid
-#pragma unroll
-            for (int sl = 0; sl < NDY + NX; ++sl) glds16(zeros, smem + NST * STAGE - 1024 * 4 + xw * 1024);
-            return;
-        }
         const PatchPos pp = decode(patch);
         char* st = smem + stage * STAGE;
         if (pp.interior) {

@@ -9,9 +9,6 @@
 
 namespace {
 
-#ifndef VQK_VQF_ABL
-#define VQK_VQF_ABL 0        // timing-only ablation bits (tools/ab_build.sh): 1 no re-rank, 2 no pass 2, 4 no pass 1, 8 no z loads, 16 no epilogue
-#endif
 constexpr int FD = 256;                                          // embedding_dim of every reference config
 constexpr int FCAP = 2048;                                       // candidate list capacity per block (64 per row on average)
 constexpr float F_DELTA = 0.0160f;
@@ -111,7 +108,7 @@ __device__ __forceinline__ void vqf_load_rows(const float* __restrict__ z, int64
     for (int it = 0; it < 8; ++it) {
         const int v = it * 256 + tid, r = v >> 6, c = v & 63;
         int64_t src = n0 + r; if (src >= n) src = n - 1;
-        st[it] = ((VQK_VQF_ABL & 8) && n > 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(z + src * FD + 4 * c);
+        st[it] = *reinterpret_cast<const f32x4*>(z + src * FD + 4 * c);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -247,12 +244,11 @@ __device__ __forceinline__ void vqf_rank(const float* __restrict__ z, const floa
     // (the NEXT tile's sixteen loads are issued before this tile's MFMAs: a whole tile of matrix work covers the L2 latency)
     float u = INFINITY;
     float lo_reg[CT][16];
-    const int cnt1 = (VQK_VQF_ABL & 4) ? (int)(n == 0) : cnt;
 #pragma unroll
     for (int tt = 0; tt < CT; ++tt) {
-        if (tt < cnt1) {
+        if (tt < cnt) {
             float hi[16];
-            tile_scores(tile_of(tt), fa[tt % 3], lo_reg[tt], hi, [&]() { if (tt + 2 < cnt1) load_tile(tile_of(tt + 2), fa[(tt + 2) % 3]); });
+            tile_scores(tile_of(tt), fa[tt % 3], lo_reg[tt], hi, [&]() { if (tt + 2 < cnt) load_tile(tile_of(tt + 2), fa[(tt + 2) % 3]); });
 #pragma unroll
             for (int r = 0; r < 16; ++r) u = fminf(u, hi[r]);
         } else {
@@ -262,13 +258,13 @@ __device__ __forceinline__ void vqf_rank(const float* __restrict__ z, const floa
     }
     // tiles beyond the register cache (K > 1024): same ring, three tiles per trip (ring slot = tile % 3; CT % 3 == CT_R)
     constexpr int CT_R = CT % 3;
-    for (int tt = CT; tt < cnt1; tt += 3) {
+    for (int tt = CT; tt < cnt; tt += 3) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            if (tt + q < cnt1) {
+            if (tt + q < cnt) {
                 float lo[16], hi[16];
                 tile_scores(tile_of(tt + q), fa[(CT_R + q) % 3], lo, hi,
-                            [&]() { if (tt + q + 2 < cnt1) load_tile(tile_of(tt + q + 2), fa[(CT_R + q + 2) % 3]); });
+                            [&]() { if (tt + q + 2 < cnt) load_tile(tile_of(tt + q + 2), fa[(CT_R + q + 2) % 3]); });
 #pragma unroll
                 for (int r = 0; r < 16; ++r) u = fminf(u, hi[r]);
             }
@@ -297,13 +293,12 @@ __device__ __forceinline__ void vqf_rank(const float* __restrict__ z, const floa
             ++pos;
         }
     };
-    const int cnt2 = (VQK_VQF_ABL & 2) ? (int)(n == 0) : cnt;
     {
         unsigned masks[CT];
         int total = 0;
 #pragma unroll
         for (int tt = 0; tt < CT; ++tt) {
-            masks[tt] = tt < cnt2 ? tile_mask(lo_reg[tt]) : 0u;
+            masks[tt] = tt < cnt ? tile_mask(lo_reg[tt]) : 0u;
             total += __builtin_popcount(masks[tt]);
         }
         if (total) {
@@ -313,16 +308,16 @@ __device__ __forceinline__ void vqf_rank(const float* __restrict__ z, const floa
                 if (masks[tt]) append(tile_of(tt), masks[tt], pos);
         }
     }
-    if (CT < cnt2) {
+    if (CT < cnt) {
         load_tile(tile_of(CT), fa[0]);
-        if (CT + 1 < cnt2) load_tile(tile_of(CT + 1), fa[1]);
+        if (CT + 1 < cnt) load_tile(tile_of(CT + 1), fa[1]);
     }
-    for (int tt = CT; tt < cnt2; tt += 3) {
+    for (int tt = CT; tt < cnt; tt += 3) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            if (tt + q < cnt2) {
+            if (tt + q < cnt) {
                 float lo[16], hi[16];
-                tile_scores(tile_of(tt + q), fa[q], lo, hi, [&]() { if (tt + q + 2 < cnt2) load_tile(tile_of(tt + q + 2), fa[(q + 2) % 3]); });
+                tile_scores(tile_of(tt + q), fa[q], lo, hi, [&]() { if (tt + q + 2 < cnt) load_tile(tile_of(tt + q + 2), fa[(q + 2) % 3]); });
                 const unsigned mask = tile_mask(lo);
                 if (mask) {
                     int pos = atomicAdd(&ncand, __builtin_popcount(mask));
@@ -339,7 +334,7 @@ __device__ __forceinline__ void vqf_rank(const float* __restrict__ z, const floa
         // The 256-term fma chain is sequential by definition; what can be hidden is its operand traffic: the z rows come from
         // the LDS tile, a candidate's code row arrives in two batches of 32 independent 16-byte loads (two L2 round trips
         // instead of sixteen).
-        const int nc = (VQK_VQF_ABL & 1) ? (int)(n == 0) : ncand;
+        const int nc = ncand;
         for (int c = tid; c < nc; c += 256) {
             const unsigned pk = cand[c];
             const int row = (int)(pk >> 26), code = (int)(pk & 0x03ffffffu);

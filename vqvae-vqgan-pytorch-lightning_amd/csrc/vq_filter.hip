@@ -40,10 +40,6 @@
 
 namespace {
 
-#ifndef VQK_VQB_ABL
-#define VQK_VQB_ABL 0        // timing-only ablation bits of the fused backward: 1 plain stores instead of atomics, 2 no LDS adds
-#endif
-
 // codebook -> bf16 (RNE), FRAGMENT-MAJOR: [tile of 32 codes][k-step s 0..15][lane 0..63][8 bf16], lane = 32 * half + (code % 32)
 // holds columns 16 s + 8 half .. + 7 of its code -- every MFMA A operand of the filter is ONE coalesced 1-KiB load (the
 // row-major form made each load touch 32 different lines).  + delta factors eps_e[k] = F_DELTA * sqrt(E2_k).
@@ -112,7 +108,7 @@ __global__ __launch_bounds__(256, 1) void vq_assign_filter_kernel(const float* _
     const int* fin = s.fin;
     float* red_m = s.red_m;
     if (tid < 32 && n0 + tid < n) idx[n0 + tid] = (int64_t)fin[tid];
-    if (!(q32 || q_lo || sse || hist) || ((VQK_VQF_ABL & 16) && n > 0)) return;      // kernel-uniform
+    if (!(q32 || q_lo || sse || hist)) return;      // kernel-uniform
 
     // ---------------------------------------------------------------- fused epilogue (vector_quantizers.py:44-56)
     // thread (row = tid / 8, sub = tid % 8): columns 4 sub + 32 jj .. + 3, jj = 0..7 -- all 32 rows of the block in flight at
@@ -242,10 +238,7 @@ __global__ __launch_bounds__(256) void vq_backward_fused_kernel(const float* __r
         }
         float* drow = de + (int64_t)code_s[r] * FD;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if ((VQK_VQB_ABL & 1) && n > 0) drow[t * 64 + lane] = ce * a[t];
-            else atomicAdd(drow + t * 64 + lane, ce * a[t]);
-        }
+        for (int t = 0; t < 4; ++t) atomicAdd(drow + t * 64 + lane, ce * a[t]);
     }
 }
 

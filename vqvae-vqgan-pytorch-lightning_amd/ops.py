@@ -899,9 +899,6 @@ def raw_split_pair(t) -> torch.Tensor:
     return out
 
 
-_ABL_SKIP_SMALL_WGRAD = int(_native.switch('VQK_ABL_SKIP_SMALL_WGRAD', '0'))      # TIMING-ONLY ablation (tools/ab_env_multi.sh): 3x3 weight gradients on maps of <= this many pixels are not launched -- is their time hidden under the GroupNorm backward?
-
-
 def raw_conv_wgrad(x, dy, ksize: int, ups: bool, out=None, thin_true: int = 8, x3: bool = False) -> torch.Tensor:
     """dw as fp32 with memory [Cout][k][k][Cin] (logical [Cout,Cin,k,k] channels_last); ``out``: accumulate
     into this (pre-existing) buffer instead of a fresh zeroed one.  ``thin_true`` < 8 (edge convs only, with ``out``): ``out`` is
@@ -911,8 +908,6 @@ def raw_conv_wgrad(x, dy, ksize: int, ups: bool, out=None, thin_true: int = 8, x
     dw = out if out is not None else \
         torch.zeros((cout, ksize, ksize, cin), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
     flops = 2.0 * n * dy.shape[2] * dy.shape[3] * cout * cin * ksize * ksize
-    if _ABL_SKIP_SMALL_WGRAD and ksize == 3 and out is not None and dy.shape[2] * dy.shape[3] <= _ABL_SKIP_SMALL_WGRAD:
-        return dw                                                # (wrong gradients: a timing experiment, never a training run)
     if edge_wgrad_served(x, dy, ksize, ups):
         # the two edge convs (padded 3-channel image / reconstruction): K = 72 GEMM, HBM-bound, workspace split-K
         ws = _edge_ws(x.device)
@@ -1735,19 +1730,7 @@ class Conv2dFn(torch.autograd.Function):
                 # the TRUE gradient to the arena -- no zero-filled padded temporary, no slice, no AccumulateGrad pass
                 tgt = direct_grad(ctx.weight_ref)
                 thin = (i if cin != i else o) if tgt is not None else 8
-            if (tgt is not None and CONV_WGRAD_SIDE and OVERLAP_WGRAD and k == 3 and dt == torch.bfloat16 and thin == 8
-                    and dyc.shape[2] * dyc.shape[3] >= CONV_WGRAD_SIDE_MIN_HW and not DETERMINISTIC):
-                # a conv outside a ResBlock (the decoder's Upsample convs: 0.9 ms of weight gradients per step): the gradient goes
-                # to the arena and only the optimizer reads it -- issued on the side stream behind the data gradient; the next
-                # ResBlock's backward (or join_side_streams at the end of the backward) joins it
-                main, side = torch.cuda.current_stream(), _side_stream(x.device)
-                _side_after(side, _fork_point(main))
-                with torch.cuda.stream(side):
-                    raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3)
-                _SIDE_PENDING.add(x.device)
-                x.record_stream(side); dyc.record_stream(side)
-            else:
-                dw = raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3)
+            dw = raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3)
             if tgt is not None:
                 dw = None                                        # already accumulated in the flat arena
             elif padded:
@@ -1797,10 +1780,6 @@ class GroupNormSiLUFn(torch.autograd.Function):
 
 POOLED_BWD = _native.switch('VQK_POOLED_BWD', '1') != '0'      # ResBlock + fused avg-pool: the backward keeps the gradient pooled
 OVERLAP_WGRAD = _native.switch('VQK_OVERLAP_WGRAD', '1') == '1'
-SHORTCUT_WGRAD_SIDE = _native.switch('VQK_SHORTCUT_WGRAD_SIDE', '0') == '1'   # ResBlock shortcut: weight gradient on the side stream (measured +-0: 28.26 / 28.18 against 28.17 / 28.19 ms -- off)
-OVERLAP_MODE = int(_native.switch('VQK_OVERLAP_MODE', '3'))
-WGRAD_NOJOIN_HW = int(_native.switch('VQK_WGRAD_NOJOIN_HW', '0'))      # ResBlocks on maps of <= this many pixels: weight gradients joined at the END of the backward
-OVERLAP_WAIT_MIN_HW = int(_native.switch('VQK_OVERLAP_WAIT_MIN_HW', '0'))   # maps below this many pixels: dgrad1 does not wait for wgrad2
 OVERLAP_STREAM_BLOCKS = int(_native.switch('VQK_OVERLAP_STREAM_BLOCKS', '512'))
 OVERLAP_WGRAD_BLOCKS = int(_native.switch('VQK_OVERLAP_WGRAD_BLOCKS', '320'))
 OVERLAP_WGRAD_BLOCKS_HI = int(_native.switch('VQK_OVERLAP_WGRAD_BLOCKS_HI', '256'))   # the 256x256 levels: GroupNorm-bound in the backward -- the weight gradient on half the CUs (swept 192 / 224 / 256 / 288 / 320 / 448: -0.15 ms at 256)
@@ -1824,40 +1803,17 @@ def aux_stream(device, tag: str) -> torch.cuda.Stream:
     return st
 
 
-# hipGraph replay maps the captured nodes to hardware queues by a depth-first walk in which the FIRST successor of a node
-# (in capture order) inherits its queue and every further successor gets another one.  The weight-gradient launch is
-# captured right behind the data-gradient conv it forks from, so the replay runs conv -> wgrad -> conv on one queue and the
-# GroupNorm-backward chain on the other: every conv -> GroupNorm -> conv hop crosses queues (84 gaps of ~10 us,
-# profiles/round3_step_timeline.txt).  CHAIN_FIRST = 1 captures the chain's next kernel first (the side stream then waits on
-# an event recorded at the fork point): the replay does put the whole chain on one queue (profiles/round4_chain_first_ab.txt:
-# 311 + 40 kernels instead of 275 + 76) -- and the step is SLOWER, 29.8-30.2 against 29.1-29.3 ms same box, with every cap /
-# join variant tried: the kernel that reaches the chip first takes the CUs, the GroupNorm pass floods all 256 and the
-# weight gradient (one 512-thread, 120-KiB block per CU) only gets in as its blocks retire (wgrad 11.3 instead of 9.9 ms,
-# main queue waits 2.0 ms on it).  The weight gradient has to be launched first; the 10-us hops are the price.
-CHAIN_FIRST = _native.switch('VQK_CHAIN_FIRST', '0') == '1'
-
-
-CONV_WGRAD_SIDE = _native.switch('VQK_CONV_WGRAD_SIDE', '0') == '1'
-CONV_WGRAD_SIDE_MIN_HW = int(_native.switch('VQK_CONV_WGRAD_SIDE_MIN_HW', '1024'))
-_SIDE_PENDING: set = set()      # devices whose side stream carries work no ResBlock backward has joined yet
-
-
-def join_side_streams() -> None:
-    """the current stream waits for side-stream work that was issued outside a ResBlock's backward (Conv2dFn's weight gradient):
-    called at the end of a backward, before the gradients are reduced / the optimizer steps"""
-    for dev in list(_SIDE_PENDING):
-        torch.cuda.current_stream(dev).wait_stream(_side_stream(dev))
-    _SIDE_PENDING.clear()
-
-
-def _fork_point(main):
-    ev = torch.cuda.Event()
-    ev.record(main)
-    return ev
-
-
-def _side_after(side, fork) -> None:
+def _on_side(main, side, launch) -> None:
+    """fork: ``launch()`` on the side stream, behind everything issued on ``main`` so far.
+    Called BEFORE the next kernel of the main chain is launched: the weight gradient has to reach the chip first.  Launched (or
+    captured) second it only gets CUs as the GroupNorm blocks retire and the step is slower, 29.8-30.2 against 29.1-29.3 ms
+    (profiles/round4_chain_first_ab.txt) -- although a hipGraph replay then keeps the conv -> GroupNorm -> conv chain on one
+    hardware queue.  The ~10-us queue hops of this order (profiles/round3_step_timeline.txt) are the price."""
+    fork = torch.cuda.Event()
+    fork.record(main)
     side.wait_event(fork)
+    with torch.cuda.stream(side):
+        launch()
 
 
 def _wgrad_cap(hw: int) -> int:
@@ -1954,32 +1910,17 @@ class ResBlockFn(torch.autograd.Function):
                 d_a2 = raw_conv_pooled_dgrad_phase(dout, c2w, 0.25) if POOLED_DGRAD_PHASE else None
                 if d_a2 is None:
                     d_a2 = _conv_general_raw(dout, wt2, None, None, cout, 3, 1, 1, 1, h, w, 0, 0.25, 1.0, dt, lay)
-                fork = _fork_point(main)
-                if not CHAIN_FIRST:
-                    _side_after(side, fork)
-                    with torch.cuda.stream(side):
-                        if not raw_conv_wgrad_pooled_dy(a2, dout, 0.25, t2):
-                            raise RuntimeError('vqk: pooled weight gradient not served for an eligible shape')
+
+                def wgrad2_pooled():
+                    if not raw_conv_wgrad_pooled_dy(a2, dout, 0.25, t2):
+                        raise RuntimeError('vqk: pooled weight gradient not served for an eligible shape')
+                _on_side(main, side, wgrad2_pooled)
                 d_r1, _, _ = raw_gn_backward(r1, st2, w2, b2, d_a2, groups, True, tw2, tb2, cluster_ok=ctx.cluster_ok)
-                if CHAIN_FIRST:
-                    _side_after(side, fork)
-                    with torch.cuda.stream(side):
-                        if not raw_conv_wgrad_pooled_dy(a2, dout, 0.25, t2):
-                            raise RuntimeError('vqk: pooled weight gradient not served for an eligible shape')
-                if OVERLAP_MODE == 3:
-                    main.wait_stream(side)
+                main.wait_stream(side)                   # dgrad1 alone on the chip
                 lay1 = weight_layout(dt, n, h, w, cout, cin, 3, False)
                 d_a1 = raw_conv_fprop(d_r1, packed_weight(c1w, cin, cout, dt, 3, True, lay1), None, None, 3, False, 0, dt, cin, lay1)
-                fork = _fork_point(main)
-                if not CHAIN_FIRST:
-                    _side_after(side, fork)
-                    with torch.cuda.stream(side):
-                        raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3)
+                _on_side(main, side, lambda: raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3))
                 dx = raw_gn_backward_pooled_add(x, st1, w1, b1, d_a1, groups, True, tw1, tb1, dout, 0.25, cluster_ok=ctx.cluster_ok)
-                if CHAIN_FIRST:
-                    _side_after(side, fork)
-                    with torch.cuda.stream(side):
-                        raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3)
                 main.wait_stream(side)
             finally:
                 lib.vqk_conv_set_block_caps(0, 0)
@@ -2031,66 +1972,17 @@ class ResBlockFn(torch.autograd.Function):
             lib = _native.lib()
             lib.vqk_conv_set_block_caps(OVERLAP_STREAM_BLOCKS, _wgrad_cap(h * w))
             try:
-                if OVERLAP_MODE == 1:
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        wgrad_c2(t2)
-                    d_a2 = d_a2_pre if d_a2_pre is not None else conv_bwd(a2, dout, c2w, 3, cout, cout, need_dw=False)[0]
-                else:                                    # wgrad starts behind the dgrad: it overlaps GroupNorm only
-                    d_a2 = d_a2_pre if d_a2_pre is not None else conv_bwd(a2, dout, c2w, 3, cout, cout, need_dw=False)[0]
-                    fork = _fork_point(main)
-                    if not CHAIN_FIRST:
-                        _side_after(side, fork)
-                        with torch.cuda.stream(side):
-                            wgrad_c2(t2)
+                d_a2 = d_a2_pre if d_a2_pre is not None else conv_bwd(a2, dout, c2w, 3, cout, cout, need_dw=False)[0]
+                _on_side(main, side, lambda: wgrad_c2(t2))           # behind the data gradient: it overlaps the GroupNorm pass only
                 d_r1, dn2w, dn2b = gn_bwd(r1, st2, w2, b2, d_a2, n2w, n2b)
-                if OVERLAP_MODE != 1 and CHAIN_FIRST:
-                    _side_after(side, fork)
-                    with torch.cuda.stream(side):
-                        wgrad_c2(t2)
-                if OVERLAP_MODE == 1:
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3)
-                    d_a1, _ = conv_bwd(a1, d_r1, c1w, 3, cin, cout, need_dw=False)
-                else:
-                    if OVERLAP_MODE == 3 and h * w >= OVERLAP_WAIT_MIN_HW:
-                        main.wait_stream(side)           # dgrad1 alone on the chip
-                    d_a1, _ = conv_bwd(a1, d_r1, c1w, 3, cin, cout, need_dw=False)
-                    fork = _fork_point(main)
-                    if not CHAIN_FIRST:
-                        _side_after(side, fork)
-                        with torch.cuda.stream(side):
-                            raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3)
+                main.wait_stream(side)                   # dgrad1 alone on the chip
+                d_a1, _ = conv_bwd(a1, d_r1, c1w, 3, cin, cout, need_dw=False)
+                _on_side(main, side, lambda: raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3))
                 dskip, dwsc = dout, None
-                if scw is not None:
-                    tsc = direct_grad(scw) if SHORTCUT_WGRAD_SIDE else None
-                    if tsc is not None:
-                        # the 1x1 shortcut: its data gradient (the skip addend of the GroupNorm pass below) on the main stream, its
-                        # WEIGHT gradient -- needed by the optimizer only -- behind conv1's on the side stream, next to that pass
-                        # (it ran on the main stream before: 0.42 ms per step on the critical path, profiles/round4_step_timeline.txt)
-                        dskip, _ = conv_bwd(x, dout, scw, 1, cin, cout, need_dw=False)
-                        fork_sc = _fork_point(main)
-                        _side_after(side, fork_sc)
-                        with torch.cuda.stream(side):
-                            raw_conv_wgrad(x, dout, 1, False, out=tsc, x3=x3)
-                    else:
-                        dskip, dwsc = conv_bwd(x, dout, scw, 1, cin, cout)
+                if scw is not None:                      # the 1x1 shortcut stays on the main stream (its weight gradient forked as well: measured +-0)
+                    dskip, dwsc = conv_bwd(x, dout, scw, 1, cin, cout)
                 dx, dn1w, dn1b = gn_bwd(x, st1, w1, b1, d_a1, n1w, n1b, add=dskip, colsum_of=ctx.db_param)
-                if OVERLAP_MODE != 1 and CHAIN_FIRST:
-                    _side_after(side, fork)
-                    with torch.cuda.stream(side):
-                        raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3)
-                if h * w <= WGRAD_NOJOIN_HW:
-                    # small maps: the block's GroupNorm backward is ONE short kernel, the weight gradients outlast it (measured: not
-                    # launching them at all on <= 32^2 maps saves 1.23 ms of a 27.8-ms step, profiles/round6_small_wgrad_ab.txt) --
-                    # they are joined at the end of the backward (join_side_streams) instead of at the end of the block and run
-                    # beside the next blocks' kernels, which leave CUs free on these maps
-                    _SIDE_PENDING.add(x.device)
-                    for t in (a1, a2, dout, d_r1) + ((dout_p,) if dout_p is not None else ()):
-                        t.record_stream(side)
-                else:
-                    main.wait_stream(side)
+                main.wait_stream(side)
             finally:
                 lib.vqk_conv_set_block_caps(0, 0)
             return dx, dn1w, dn1b, None, dn2w, dn2b, None, dwsc, None, None, None, None
