@@ -60,6 +60,8 @@ const char* vqk_arch(void);
 
 /* ---------------------------------------------------------------- vector quantizer ---------
  * vector_quantizers.py:33-44 / :337-343.  z[N][D], e[K][D] fp32 row-major, D % 8 == 0.
+ * (The cosine quantizer further down applies this arithmetic, assoc 0, to l2-normalised rows: fused for D in {8, 16, 32, 64} and
+ * K % 32 == 0, staged on these functions for every other shape.)
  * assoc 0: d = (|z|^2 + |e|^2) - 2 z.e (Standard/EMA); assoc 1: d = (|z|^2 - 2 z.e) + |e|^2 (Entropy).
  * Products are exact fp32 (v_mfma_f32_32x32x2_f32), first minimum wins. */
 int vqk_row_sqnorm_f32(const float* x, int64_t rows, int d, float* out, void* stream);
@@ -205,6 +207,48 @@ int64_t vqk_rvq_backward_ws_bytes(int64_t n, int d, int depth);
 int vqk_rvq_backward_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
                          int depth, float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws,
                          int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- cosine quantizer ---------
+ * Yu et al. 2022 (ViT-VQGAN), the factorised l2-normalised codebook (csrc/vq_cos.hip).  z[N][D], e[K][D] fp32 rows, eps = 1e-12.
+ * nrm(x): ss = |x|^2 with the bits of vqk_row_sqnorm_f32; inv = 1 / max(sqrt(ss), eps), correctly rounded; xn_j = x_j * inv -- ONE
+ * device function (csrc/vq_cos.h) behind every entry point below: the same row gives the same bits everywhere.
+ * zn = nrm(z), en = nrm(e); idx = vqk_vq_assign_f32(zn, en, assoc 0) with |zn|^2, |en|^2 from vqk_row_sqnorm_f32, first minimum
+ * wins; q = en[idx]; sse = sum |q - zn|^2; loss = (1 + beta) / (N D) sse; hist[idx] += 1.  Backward (the straight-through
+ * estimator is taken at zn): g = dq + s cz (zn - q); dz = (g - zn (zn.g)) inv_z; de[k] += s ce inv_e[k] sum_{rows: idx = k}
+ * (en_k (en_k.zn) - zn), cz = 2 beta / (N D), ce = 2 / (N D), s = *gscale_dev.  A clamped row (|x| < eps) has the Jacobian I / eps.
+ * No call allocates, synchronises or reads the environment.
+ * vqk_l2norm_rows_f32: xn = nrm(x) row-wise, inv[rows] optional; any d % 4 == 0. */
+int vqk_l2norm_rows_f32(const float* x, int64_t rows, int d, float* xn, float* inv /* optional */, void* stream);
+/* The per-codebook workspace en[K][D] | |en|^2[K] | inv_e[K] (each part 16-byte aligned; vqk_cos_ws_bytes(k, d) bytes, VQK_ERR_SHAPE
+ * for d % 4 != 0): built when the codebook CHANGES, not per step.  ws 16-byte aligned. */
+int64_t vqk_cos_ws_bytes(int k, int d);
+int vqk_cos_prepare_f32(const float* e, int k, int d, void* ws, int64_t ws_bytes, void* stream);
+/* forward: ONE launch -- a block stages 32 rows in LDS, normalises them there, ranks them against en streamed from L2 with the MFMA
+ * sequence and comparisons of vqk_vq_assign_f32, gathers and reduces; equal to vqk_l2norm_rows_f32 + vqk_row_sqnorm_f32 +
+ * vqk_vq_assign_f32 + vqk_vq_gather_f32 on the materialised rows, bit for bit.  q as fp32 (q) and / or bf16 (q_lo), sse[1] and
+ * hist[K] (int32) are optional; sse and hist are pre-zeroed by the caller.  sse: one fp32 atomic per block (arrival order); in
+ * deterministic mode the blocks' partials go through the workspace of vqk_set_deterministic (>= ceil(n / 32) * 4 bytes:
+ * VQK_ERR_WORKSPACE) and a second launch adds them in block order.  Served: d in {8, 16, 32, 64}, k % 32 == 0 (VQK_ERR_SHAPE
+ * otherwise, nothing launched); z, ws, q 16-byte, q_lo 8-byte aligned; ws_bytes >= vqk_cos_ws_bytes(k, d). */
+int vqk_cos_forward_f32(const float* z, const void* ws, int64_t ws_bytes, int64_t n, int k, int d, int64_t* idx,
+                        float* q /* optional */, void* q_lo /* optional */, float* sse /* optional */, int32_t* hist /* optional */,
+                        void* stream);
+/* sse[0] += sum |q - zn|^2 over materialised rows with the forward's block partials and thread mapping: the staged formulation's
+ * sum with the forward's bits in deterministic mode (same workspace rule).  Any d % 4 == 0; zn and q 16-byte aligned. */
+int vqk_cos_sse_f32(const float* zn, const float* q, int64_t n, int d, float* sse, void* stream);
+/* q = en[idx] from the prepared workspace as fp32 and / or bf16 (at least one): the forward's bits for the same tokens.  A token
+ * outside [0, K) reads nothing and gives a zero row.  Any d % 4 == 0. */
+int vqk_cos_decode_f32(const int64_t* idx, const void* ws, int64_t ws_bytes, int64_t n, int k, int d, float* q /* optional */,
+                       void* q_lo /* optional */, void* stream);
+/* backward: ONE launch in default mode -- z is re-normalised with the forward's bits, dz written once, the rows of a 32-row block
+ * that share a code are summed in LDS and ONE projected, coalesced fp32 atomic row per distinct (code, block) goes to de (which may
+ * be a view of the optimizer's gradient arena).  dq: optional (NULL = 0), fp32 or bf16 (dq_dtype); de: optional, pre-zeroed by the
+ * caller (or holding what it is added to).  Deterministic mode with de: the per-row terms go to ws2 (>= vqk_cos_backward_ws_bytes(n,
+ * d) bytes: VQK_ERR_WORKSPACE) and a second launch, one block per code, adds them in row order: no atomics, the same bits every run.
+ * ws2 is not read otherwise (NULL allowed).  Served: d in {8, 16, 32, 64} (VQK_ERR_SHAPE otherwise, also from the size query). */
+int64_t vqk_cos_backward_ws_bytes(int64_t n, int d);
+int vqk_cos_backward_f32(const float* z, const void* ws, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
+                         float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws2,
+                         int64_t ws2_bytes, void* stream);
 /* ---------------------------------------------------------------- k-means codebook initialisation ---------
  * k-means++ seeding and the centroid update of a Lloyd iteration (csrc/kmeans.hip); the assignment and the per-cluster sums of an
  * iteration are vqk_vq_assign*_f32 and vqk_ema_stats*_f32.  No call allocates, synchronises or reads anything back to the host: a

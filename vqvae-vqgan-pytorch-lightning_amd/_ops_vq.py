@@ -31,11 +31,17 @@ class _VQPrep:
 
 
 _VQ_PREP: dict = {}             # data_ptr of the codebook -> _VQPrep: what vqk_vq_prepare_f32 derived from it
+# every table of prepared workspaces refresh_vq_prepared keeps current: (data_ptr -> _VQPrep, prepare(ent, codebook)); the
+# cosine quantizer's (_ops_cos.py) registers itself here
+_PREP_TABLES: list = []
 
 
 def _vq_prepare_now(ent, cb) -> None:
     _native.check(_native.lib().vqk_vq_prepare_f32(cb.data_ptr(), ent.k, ent.d, ent.ws.data_ptr(), ent.ws.numel(), core._stream()),
                   'vq_prepare')
+
+
+_PREP_TABLES.append((_VQ_PREP, _vq_prepare_now))
 
 
 def vq_prepared(codebook) -> torch.Tensor | None:
@@ -67,21 +73,22 @@ def refresh_vq_prepared(owner=None, data_ptr: int | None = None) -> int:
     """re-derive the prepared workspaces whose codebook belongs to ``owner`` (a FlatAdamW that just stepped), lives at
     ``data_ptr`` (the EMA update wrote it through the C-ABI: no version bump), or -- both None -- is stale"""
     n = 0
-    for ptr, ent in list(_VQ_PREP.items()):
-        cbp = ent.wref()
-        if cbp is None or cbp.data_ptr() != ptr:
-            del _VQ_PREP[ptr]
-            continue
-        if data_ptr is not None:
-            hit = ptr == data_ptr
-        elif owner is not None:
-            hit = getattr(cbp, '_vqk_owner', None) is owner
-        else:
-            hit = ent.stamp != core._pack_stamp(cbp)
-        if hit:
-            _vq_prepare_now(ent, cbp.detach())
-            ent.stamp = core._pack_stamp(cbp)
-            n += 1
+    for table, prepare in _PREP_TABLES:
+        for ptr, ent in list(table.items()):
+            cbp = ent.wref()
+            if cbp is None or cbp.data_ptr() != ptr:
+                del table[ptr]
+                continue
+            if data_ptr is not None:
+                hit = ptr == data_ptr
+            elif owner is not None:
+                hit = getattr(cbp, '_vqk_owner', None) is owner
+            else:
+                hit = ent.stamp != core._pack_stamp(cbp)
+            if hit:
+                prepare(ent, cbp.detach())
+                ent.stamp = core._pack_stamp(cbp)
+                n += 1
     return n
 
 

@@ -28,8 +28,8 @@ from torch import nn
 from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
-from .modules.vector_quantizers import (EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer, ResidualVectorQuantizer,
-                                        VectorQuantizer, _flat_view, gather_latent_sample)
+from .modules.vector_quantizers import (CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer,
+                                        ResidualVectorQuantizer, VectorQuantizer, _flat_view, gather_latent_sample)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
 from .optim import FlatAdamW
@@ -133,6 +133,10 @@ class VQVAE(BaseVQVAE, _LightningBase):
             if not 1 <= depth <= 8:
                 raise ValueError(f'residual quantizer: depth must be between 1 and 8, got {depth}')
             self.quantizer = ResidualVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']), depth)
+        elif qt == 'cosine':
+            # the l2-normalised low-dimensional codebook (embedding_dim 8 to 64); a codebook_init block fits k-means to the
+            # l2-normalised latent sample (CosineVectorQuantizer.init_codebook_from_data)
+            self.quantizer = CosineVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']))
         else:
             raise ValueError(f'unrecognized quantizer: {qt}')
 
@@ -190,6 +194,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         no augmentation) over as many of ``batches`` as it takes to hold ``samples`` latent rows -- fp32, flattened as the quantizer
         flattens them; data parallel: samples // world per rank, one all-gather forms the common sample -- and the quantizer's
         ``init_codebook_from_data`` fits k-means to them with the draws ``torch.rand(K, generator=manual_seed(seed), float64)``.
+        The cosine quantizer l2-normalises the sample first (vqk_l2norm_rows_f32): its k-means runs on the unit sphere.
         Call it after the optimizer is attached (the codebook is written in place) and BEFORE a hipGraph capture.
         Returns dict(samples, iters, inertia, used, seconds)."""
         conf = self.codebook_init

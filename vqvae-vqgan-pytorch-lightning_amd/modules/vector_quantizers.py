@@ -1,7 +1,8 @@
 """Quantizers on the vqk kernels; same classes / ctor signatures / return conventions as the reference's
 ``vqvae/modules/vector_quantizers.py`` (VectorQuantizer :8-84, EMAVectorQuantizer :87-203,
 EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274); ``FSQuantizer`` (finite scalar quantization, no counterpart in
-the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (residual quantization, no counterpart either) the sixth.
+the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (residual quantization, no counterpart either) the sixth,
+``CosineVectorQuantizer`` (the l2-normalised low-dimensional codebook of ViT-VQGAN, no counterpart either) the seventh.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -320,3 +321,44 @@ class ResidualVectorQuantizer(BaseVectorQuantizer):
         if codes.dim() != 3 or not 1 <= codes.shape[-1] <= ops.RVQ_MAX_DEPTH:
             raise ValueError(f'residual quantizer: codes must be (B, N, depth), got {tuple(codes.shape)}')
         return ops.rvq_decode(codes, self.codebook.weight)
+
+
+class CosineVectorQuantizer(BaseVectorQuantizer):
+    """The factorised, l2-normalised codebook of ViT-VQGAN (Yu et al. 2022): the encoder projects to a LOW-dimensional latent
+    (``embedding_dim`` 8 to 64 instead of 256), latents and codes are both l2-normalised before the lookup -- the Euclidean ranking is
+    then the cosine ranking -- and the decoder sees the normalised code.  loss = codebook term |sg(zn) - en|^2 + ``commitment_cost`` *
+    commitment term |zn - sg(en)|^2; the straight-through estimator is taken at the normalised latent.  One fused forward and one
+    backward kernel (csrc/vq_cos.hip) for D in {8, 16, 32, 64} and K % 32 == 0, the staged formulation (``ops.cos_staged``) otherwise.
+    The state dict is the standard quantizer's: ``codebook.weight`` only, stored UN-normalised, so checkpoints move both ways between
+    ``standard`` and ``cosine``.  Usage statistics and dead-code re-initialisation are the base class's.  ``init_codebook_from_data``
+    fits k-means to the l2-NORMALISED latent sample (``vqk_l2norm_rows_f32``): Euclidean k-means on the unit sphere, whose centres the
+    lookup normalises again (spherical k-means proper is not implemented)."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25):
+        if int(embedding_dim) % 8 != 0:
+            raise ValueError(f'cosine quantizer: embedding_dim must be a multiple of 8, got {embedding_dim}')
+        super().__init__(num_embeddings, embedding_dim)
+        self.commitment_cost = commitment_cost
+
+    def forward(self, x: torch.Tensor):
+        q, idx, loss, hist = ops.CosLookupFn.apply(x, self.codebook.weight, self.commitment_cost, self.compute_dtype)
+        self.last_hist = hist
+        return q, idx, loss
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.cos_assign(_flat_view(z), self.codebook.weight).view(x.shape[0], -1)
+
+    @torch.no_grad()
+    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes (B,N) -> (B,N,D): the NORMALISED code rows, the bits the forward hands to the decoder"""
+        return ops.cos_decode(codes, self.codebook.weight)
+
+    @torch.no_grad()
+    def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
+        """the base class's k-means start on the l2-normalised sample (see the class docstring)"""
+        w = self.codebook.weight
+        if flat_z.dim() != 2 or flat_z.shape[1] != w.shape[1]:
+            raise ValueError(f'init_codebook_from_data: latents must be [N, {w.shape[1]}], got {tuple(flat_z.shape)}')
+        return super().init_codebook_from_data(ops.l2norm_rows(flat_z), iters, u, rows_per_step)

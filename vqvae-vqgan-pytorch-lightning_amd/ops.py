@@ -2066,6 +2066,7 @@ class _MSE(torch.autograd.Function):
 VQ_FILTER = _native.switch('VQK_VQ_FILTER', '1') != '0'
 VQ_FUSED = _native.switch('VQK_VQ_FUSED', '1') != '0'      # one forward kernel + one backward kernel (0: the round-3 launch sequence)
 RVQ_FUSED = _native.switch('VQK_RVQ_FUSED', '1') != '0'    # residual quantizer: the one-launch multi-stage forward (0: the staged formulation, _ops_rvq.rvq_staged)
+COS_FUSED = _native.switch('VQK_COS_FUSED', '1') != '0'    # cosine quantizer: the one-launch normalise + rank + gather forward (0: the staged formulation, _ops_cos.cos_staged)
 ENTROPY_FUSED_ROWS = _native.switch('VQK_ENTROPY_FUSED_ROWS', '1') != '0'
 ENTROPY_SPLIT_GEMM = _native.switch('VQK_ENTROPY_SPLIT_GEMM', '1') != '0'     # bf16 compute mode: the entropy cotangent's two GEMMs as bf16 split products
 ACT_CODE = {'linear': 0, 'tanh': 1, 'relu': 2, 'lrelu': 3}
@@ -2140,5 +2141,6 @@ if TRACE:
 from ._ops_vq import *        # noqa: E402,F401,F403  quantizers
 from ._ops_fsq import *       # noqa: E402,F401,F403  finite scalar quantizer
 from ._ops_rvq import *       # noqa: E402,F401,F403  residual quantizer
+from ._ops_cos import *       # noqa: E402,F401,F403  cosine quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins
