@@ -175,6 +175,37 @@ int64_t vqk_fsq_backward_ws_bytes(int64_t n, int dm, int d);
 int vqk_fsq_backward(const float* z, const float* u, const void* dq, int dq_dtype, const float* w_in, const float* w_out, int64_t n,
                      int dm, int d, const int32_t* levels, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out,
                      int accumulate, void* ws, int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- lookup-free quantizer ---------
+ * Yu et al. 2023 (MAGVIT-v2) / Open-MAGVIT2 (csrc/lfq.hip).  z[N][D] fp32 rows, w_in[d][D], b_in[d], w_out[D][d], b_out[D] fp32, d = bits.
+ * u = W_in z + b_in; c_j = +1 if u_j > 0 else -1 (a zero or a NaN gives -1); idx = sum_j [u_j > 0] 2^j; q = W_out c + b_out.
+ * commit = sum (u - c)^2 / (N d); p_nj = sigmoid(a u_nj), a = 4 / tau; H_sample = sum_nj h(p_nj) / N (h = binary entropy: exactly the
+ * entropy of softmax(2 u.c_k / tau) over the 2^d sign codes); the bits are split into ceil(d / g) groups of g consecutive bits (the last
+ * may be shorter), P_n^s(m) = prod_i (bit_i(m) ? p : 1 - p) over the bits of group s, Pbar^s = mean_n P_n^s, H_batch = sum_s -sum_m
+ * Pbar^s(m) log(Pbar^s(m) + 1e-10); loss = beta commit + ratio (H_sample - gamma H_batch).
+ * Served: 4 <= D <= 512, D % 4 == 0, 1 <= d <= 18, 1 <= g <= 10 (VQK_ERR_SHAPE otherwise, nothing launched); tau > 0 (VQK_ERR_ARG); z, q,
+ * q_lo, dq, dz and ws 16-byte aligned, the parameters need no alignment.  No call allocates or synchronises; every sum over rows is
+ * ordered (per-block slabs in ws + a second launch that adds them in an order fixed by their count): the same bits every run.
+ * ws: >= vqk_lfq_ws_bytes(n, D, d, g) bytes, a function of the shape only, serves forward and backward (VQK_ERR_WORKSPACE).
+ * forward: idx[N]; u[N][d] (optional: what the backward needs); q as fp32 (q) and / or bf16 (q_lo), both optional; hist[idx] += 1 (int32
+ * [2^d], optional, pre-zeroed by the caller).  The loss is asked for with out, ltab and ws together (all three or none): out[4] = loss,
+ * commit, H_sample, H_batch; ltab[ceil(d / g) << g] = log(Pbar + 1e-10) + Pbar / (Pbar + 1e-10), what the backward reads.  Without them:
+ * assignment only, ONE launch, no workspace. */
+int64_t vqk_lfq_ws_bytes(int64_t n, int dm, int d, int g);
+int vqk_lfq_forward(const float* z, const float* w_in, const float* b_in, const float* w_out, const float* b_out, int64_t n, int dm,
+                    int d, int g, float tau, float beta, float ratio, float gamma, int64_t* idx, float* u /* optional */,
+                    float* q /* optional */, void* q_lo /* optional */, int32_t* hist /* optional */, float* out /* optional */,
+                    float* ltab /* optional */, void* ws /* optional */, int64_t ws_bytes, void* stream);
+/* idx[N] -> q (fp32 and / or bf16): c_j from bit j of the index -- no table, any int64 reads nothing out of bounds -- through the
+ * forward's own device function: the same bits of q for the same index. */
+int vqk_lfq_decode(const int64_t* idx, const float* w_out, const float* b_out, int64_t n, int dm, int d, float* q /* optional */,
+                   void* q_lo /* optional */, void* stream);
+/* du = W_out^T dq (straight-through at u, no tanh) + s dloss/du, s = *gscale_dev (a device scalar: the upstream gradient of the loss; NULL
+ * = 1), p recomputed from the forward's u, the H_batch term from the forward's ltab; dz = du W_in and the four parameter gradients
+ * (accumulate = 1: added to what the targets hold).  dq fp32 or bf16 (dq_dtype). */
+int vqk_lfq_backward(const float* z, const float* u, const void* dq, int dq_dtype, const float* w_in, const float* w_out,
+                     const float* ltab, const float* gscale_dev, int64_t n, int dm, int d, int g, float tau, float beta, float ratio,
+                     float gamma, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out, int accumulate, void* ws,
+                     int64_t ws_bytes, void* stream);
 /* ---------------------------------------------------------------- residual quantizer ---------
  * Lee et al. 2022 (RQ-VAE) / SoundStream (csrc/rvq.hip).  z[N][D] fp32 rows, ONE codebook e[K][D] shared by the `depth` stages:
  * r_0 = z; k_q = argmin_k (|r_{q-1}|^2 + |e_k|^2) - 2 r_{q-1}.e_k (the arithmetic of vqk_vq_forward_f32 with assoc 0, first minimum

@@ -1,0 +1,273 @@
+"""The lookup-free quantizer without a GPU: the float64 reference (tests/lfq_reference.py) against torch.autograd on a float64
+transcription of the specification (sign straight-through, per-bit sigmoids, factorised group products), the factorisation of the
+per-position entropy against the explicit softmax over all 2^d codes, the token arithmetic, the input generator, ``LFQuantizer`` /
+``VQVAE`` construction on the CPU, the shipped config, and the argument validation of the entry points.
+
+Bound of the reference check: both sides are float64 (unit roundoff 1.1e-16); the sums run over at most 64 rows of O(1) terms and the
+two formulations differ in association and in how H_batch is formed (explicit softmax in the reference, products of sigmoids in the
+transcription; at tau = 0.01 the logits reach 400 |u| and both lose the digits exp() loses) -- below 1e-12 relative to the largest
+element.  1e-10 on the max-abs metric of the GPU tests leaves two decades and is five below anything a float32 slip or a wrong term
+would show.  Measured (every figure is printed as ``LFQMEASURE cpu`` before it is asserted), the worst distances over the ten cases:
+H_sample 2.7e-14 (bits 13, g 9, tau 0.01), the isolated H_batch gradient 7.2e-15 (dz, bits 13, g 9, tau 1), every other quantity
+below 5e-15 -- against the bound of 1e-10."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import lfq_reference as R
+
+PKG = 'vqvae-vqgan-pytorch-lightning_amd'
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+AE = dict(channels=32, num_res_blocks=1, channel_multipliers=(1, 2))
+TC = dict(lr=1e-4, betas=(0.0, 0.99), eps=1e-8, weight_decay=1e-4, warmup_epochs=None, decay_epochs=None)
+KEYS = ('z', 'w_in', 'b_in', 'w_out', 'b_out')
+
+
+def q_conf(bits=10, k=1024, dim=64, reinit=None, **params):
+    return dict(num_embeddings=k, embedding_dim=dim, reinit_every_n_epochs=reinit, type='lfq', params=dict(bits=bits, **params))
+
+
+# ---------------------------------------------------------------------------------------------- reference vs torch.autograd
+class _SignSTE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return torch.where(x > 0, torch.ones_like(x), -torch.ones_like(x))
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+def torch_loss(u, g, tau, beta, ratio, gamma):
+    """the specification in torch float64, H_batch in the FACTORISED form (products of per-bit sigmoids)"""
+    n, d = u.shape
+    a = 4.0 / tau
+    c = _SignSTE.apply(u).detach()
+    commit = ((u - c) ** 2).sum() / (n * d)
+    x = a * u
+    p, pm = torch.sigmoid(x), torch.sigmoid(-x)
+    h_sample = (torch.nn.functional.softplus(-x.abs()) + x.abs() * torch.sigmoid(-x.abs())).sum() / n
+    h_batch = 0.0
+    for s, gs in R.groups(d, g):
+        bit = torch.tensor(R.codes(gs) > 0)                                 # [2^gs, gs]
+        pn = torch.where(bit[None], p[:, None, s:s + gs], pm[:, None, s:s + gs]).prod(-1)      # [N, 2^gs]
+        pbar = pn.mean(0)
+        h_batch = h_batch - (pbar * torch.log(pbar + R.EPS)).sum()
+    return beta * commit + ratio * (h_sample - gamma * h_batch), commit, h_sample, h_batch
+
+
+@pytest.mark.parametrize('tau', [1.0, 0.01])
+@pytest.mark.parametrize('bits,g,d_model', [(1, 9, 8), (4, 9, 32), (4, 3, 20), (13, 9, 64), (13, 5, 32)])
+def test_reference_matches_autograd(bits, g, d_model, tau):
+    beta, ratio, gamma, gloss = 0.25, 0.1, 1.3, 1.7
+    inp = R.make_inputs(5, 64, d_model, bits)
+    t = {k: torch.tensor(inp[k], dtype=torch.float64, requires_grad=k != 'dq') for k in KEYS + ('dq',)}
+    u = t['z'] @ t['w_in'].T + t['b_in']
+    q = _SignSTE.apply(u) @ t['w_out'].T + t['b_out']
+    loss, commit, h_sample, h_batch = torch_loss(u, g, tau, beta, ratio, gamma)
+    torch.autograd.backward([q, loss], [t['dq'], torch.tensor(gloss, dtype=torch.float64)])
+    args = tuple(inp[k] for k in KEYS)
+    fwd = R.forward(*args, g, tau, beta, ratio, gamma)
+    figures = {'q': R.distance(fwd['q'], q.detach().numpy())}
+    commit, h_sample, h_batch = (float(v.detach()) for v in (commit, h_sample, h_batch))
+    scale = max(abs(beta * commit), abs(ratio * h_sample), abs(ratio * gamma * h_batch))
+    for name, want in (('commit', commit), ('h_sample', h_sample), ('h_batch', h_batch)):
+        figures[name] = abs(float(fwd[name]) - float(want)) / max(abs(float(want)), 1e-300)
+    figures['loss'] = abs(float(fwd['loss']) - float(loss.detach())) / scale
+    ref = R.backward(*args, inp['dq'], gloss, g, tau, beta, ratio, gamma)
+    for name, key in (('dz', 'z'), ('dw_in', 'w_in'), ('db_in', 'b_in'), ('dw_out', 'w_out'), ('db_out', 'b_out')):
+        figures[name] = R.distance(ref[name], t[key].grad.numpy())
+    # the loss terms alone (dq = 0), each isolated: a wrong term cannot hide behind the 1e3 times larger quantization path.  At tau = 1
+    # only: with saturated sigmoids (tau = 0.01) the isolated H_batch gradient is ~1e-47, the difference of cancelling terms, and
+    # carries no digits to compare at 1e-10 (the combined check above covers that temperature)
+    for b_, r_, g_ in () if tau != 1.0 else ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 1.0, 1e6)):
+        tz = {k: torch.tensor(inp[k], dtype=torch.float64, requires_grad=True) for k in KEYS}
+        uu = tz['z'] @ tz['w_in'].T + tz['b_in']
+        torch_loss(uu, g, tau, b_, r_, g_)[0].backward(torch.tensor(gloss, dtype=torch.float64))
+        ref = R.backward(*args, np.zeros_like(inp['dq']), gloss, g, tau, b_, r_, g_)
+        for name, key in (('dz', 'z'), ('dw_in', 'w_in'), ('db_in', 'b_in')):
+            figures[f'{name} alone ({b_}, {r_}, {g_})'] = R.distance(ref[name], tz[key].grad.numpy())
+    for name, dist in figures.items():
+        print(f'LFQMEASURE cpu {name} bits={bits} g={g} tau={tau}: {dist:.3e} (bound 1e-10)')
+    for name, dist in figures.items():
+        assert dist <= 1e-10, name
+
+
+@pytest.mark.parametrize('tau', [1.0, 0.3, 0.01])
+@pytest.mark.parametrize('bits', [1, 4, 10])
+def test_sample_entropy_is_the_explicit_softmax_entropy(bits, tau):
+    inp = R.make_inputs(2, 48, 32, bits)
+    f = R.forward(*(inp[k] for k in KEYS), 9, tau)
+    want = R.h_sample_explicit(f['u'], tau)
+    assert abs(float(f['h_sample']) - want) <= 1e-10 * max(abs(want), 1e-30) + 1e-13
+    # and with g >= d the group table IS the full softmax: its row sums are 1, p factorises it
+    if bits <= 9:
+        ps = f['soft'][0]
+        np.testing.assert_allclose(ps.sum(-1), 1.0, rtol=0, atol=1e-12)
+        bit = R.codes(bits) > 0
+        fact = np.where(bit[None], f['p'][:, None, :], f['pm'][:, None, :]).prod(-1)
+        np.testing.assert_allclose(fact, ps, rtol=1e-9, atol=1e-300)
+
+
+# ---------------------------------------------------------------------------------------------- tokens
+@pytest.mark.parametrize('bits', [1, 4, 10, 13])
+def test_tokens_and_bits_are_a_bijection(bits):
+    k = 1 << bits
+    idx = np.arange(k)
+    c = R.indices_to_codes(idx, bits)
+    assert c.shape == (k, bits) and set(np.unique(c)) == {-1.0, 1.0}
+    assert len({tuple(row) for row in c.tolist()}) == k
+    np.testing.assert_array_equal(R.codes_to_indices(c), idx)
+    np.testing.assert_array_equal(R.codes(bits), c)
+    assert R.codes_to_indices(np.array([[1.0] + [-1.0] * (bits - 1)]))[0] == 1          # the first channel is bit 0
+
+
+@pytest.mark.parametrize('bits,d_model', [(1, 20), (10, 64), (18, 256), (16, 64)])
+def test_generator_is_off_the_boundaries_and_float32_gives_the_same_tokens(bits, d_model):
+    inp = R.make_inputs(1, 512, d_model, bits)
+    args = tuple(inp[k] for k in KEYS)
+    f64 = R.forward(*args, 9, 1.0)
+    assert f64['idx'].min() >= 0 and f64['idx'].max() < (1 << bits)
+    assert np.abs(f64['u']).min() >= 1e-3
+    print(f'LFQMEASURE resampled bits={bits} D={d_model}: {inp["resampled"]:.4f}')
+    assert inp['resampled'] <= 0.1
+    np.testing.assert_array_equal(R.indices_to_codes(f64['idx'], bits), f64['c'])
+    f32 = R.forward(*args, 9, 1.0, dtype=np.float32)
+    assert np.abs(f32['u'] - f64['u']).max() <= 1e-4
+    np.testing.assert_array_equal(f32['idx'], f64['idx'])
+
+
+# ---------------------------------------------------------------------------------------------- module and model on the CPU
+def test_constructor_validation():
+    vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
+    with pytest.raises(ValueError, match=r'2\*\*bits'):
+        vqm.LFQuantizer(1000, 64, 10)
+    with pytest.raises(ValueError, match='bits must be between 1 and 18'):
+        vqm.LFQuantizer(1 << 19, 64, 19)
+    with pytest.raises(ValueError, match='bits must be between 1 and 18'):
+        vqm.LFQuantizer(1, 64, 0)
+    with pytest.raises(ValueError, match='ent_group_bits'):
+        vqm.LFQuantizer(1024, 64, 10, ent_group_bits=11)
+    with pytest.raises(ValueError, match='ent_group_bits'):
+        vqm.LFQuantizer(1024, 64, 10, ent_group_bits=0)
+    with pytest.raises(ValueError, match='ent_temperature'):
+        vqm.LFQuantizer(1024, 64, 10, ent_temperature=0.0)
+    q = vqm.LFQuantizer(1024, 64, 10)
+    assert (q.commitment_cost, q.ent_loss_ratio, q.ent_temperature, q.diversity_gamma, q.ent_group_bits) == (0.25, 0.1, 0.01, 1.0, 9)
+
+
+def test_module_state_and_implicit_codebook():
+    vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
+    ae = importlib.import_module(PKG + '.modules.autoencoder')
+    q = vqm.LFQuantizer(1024, 64, 10)
+    assert set(q.state_dict()) == {'codebook.weight', 'project_in.weight', 'project_in.bias', 'project_out.weight', 'project_out.bias'}
+    assert isinstance(q.project_in, ae.Conv2d) and isinstance(q.project_out, ae.Conv2d)
+    assert tuple(q.project_in.weight.shape) == (10, 64, 1, 1) and tuple(q.project_out.weight.shape) == (64, 10, 1, 1)
+    assert tuple(q.codebook.weight.shape) == (1024, 10) and not q.codebook.weight.requires_grad
+    np.testing.assert_array_equal(q.codebook.weight.numpy(), R.codes(10, np.float32))
+    with torch.no_grad():
+        q.codebook.weight.zero_()
+    q.init_codebook()                                                        # writes the implicit rows, not noise
+    np.testing.assert_array_equal(q.codebook.weight.numpy(), R.codes(10, np.float32))
+    with pytest.raises(RuntimeError, match='no learned codebook'):
+        q.reinit_unused_codes(torch.ones(1024))
+    with pytest.raises(ValueError, match='no learned codebook'):
+        q.init_codebook_from_data(torch.zeros(2048, 64), 1, torch.zeros(1024, dtype=torch.float64))
+    with pytest.raises(RuntimeError, match='GPU only'):
+        q(torch.zeros(1, 64, 2, 2))
+
+
+def test_model_builds_and_groups_parameters():
+    model_mod = importlib.import_module(PKG + '.model')
+    m = model_mod.VQVAE(32, AE, q_conf(ent_group_bits=5, ent_temperature=0.3), None, TC)
+    assert type(m.quantizer).__name__ == 'LFQuantizer' and m.encoder.conv_out.out_channels == 64
+    assert (m.quantizer.bits, m.quantizer.ent_group_bits, m.quantizer.ent_temperature) == (10, 5, 0.3)
+    keys = {k for k in m.state_dict() if k.startswith('quantizer.')}
+    assert keys == {'quantizer.codebook.weight', 'quantizer.project_in.weight', 'quantizer.project_in.bias',
+                    'quantizer.project_out.weight', 'quantizer.project_out.bias'}
+    decay, no_decay = ({n for n, _ in grp} for grp in m.optimizer_groups())
+    assert {'quantizer.project_in.weight', 'quantizer.project_out.weight'} <= decay
+    assert {'quantizer.project_in.bias', 'quantizer.project_out.bias'} <= no_decay
+    assert 'quantizer.codebook.weight' not in decay | no_decay                # frozen: not handed to the optimizer
+    np.testing.assert_array_equal(m.quantizer.codebook.weight.numpy(), R.codes(10, np.float32))
+    with pytest.raises(ValueError, match='reinit_every_n_epochs'):
+        model_mod.VQVAE(32, AE, q_conf(reinit=10), None, TC)
+    with pytest.raises(ValueError, match=r'2\*\*bits'):
+        model_mod.VQVAE(32, AE, q_conf(k=1000), None, TC)
+    conf = q_conf()
+    conf['codebook_init'] = dict(method='kmeans', samples=4096, iters=2)
+    with pytest.raises(ValueError, match='no learned codebook'):
+        model_mod.VQVAE(32, AE, conf, None, TC)
+
+
+def test_shipped_config():
+    train = importlib.import_module(PKG + '.train')
+    model_mod = importlib.import_module(PKG + '.model')
+    conf = train.get_model_conf(os.path.join(ROOT, 'example_confs', 'lfq_vqvae.yaml'))
+    q = conf['quantizer']
+    assert (q['type'], q['num_embeddings'], q['embedding_dim'], q['reinit_every_n_epochs']) == ('lfq', 65536, 256, None)
+    assert q['params']['bits'] == 16 and q['params']['ent_group_bits'] == 8
+    std = train.get_model_conf(os.path.join(ROOT, 'example_confs', 'standard_vqvae.yaml'))
+    assert conf['autoencoder'] == std['autoencoder'] and conf['training'] == std['training'] and conf['image_size'] == std['image_size']
+    run = train.derive_run_config(conf, 8, {'autoencoder.channels': 32, 'quantizer.params.bits': 4, 'quantizer.num_embeddings': 16})
+    assert run['batch_size_per_device'] == 32 and run['l_conf'] is None
+    m = model_mod.VQVAE(run['image_size'], run['ae_conf'], run['q_conf'], run['l_conf'], run['t_conf'])
+    assert m.quantizer.bits == 4 and m.quantizer.ent_group_bits == 8 and type(m.criterion).__name__ == 'MSELoss'
+
+
+# ---------------------------------------------------------------------------------------------- the entry points, no device
+def test_entry_points_validate_without_gpu():
+    native = importlib.import_module(PKG + '._native')
+    native.build()
+    lib = native.lib()
+    for name in ('vqk_lfq_forward', 'vqk_lfq_backward', 'vqk_lfq_decode', 'vqk_lfq_ws_bytes'):
+        assert hasattr(lib, name) and name in native.EXPORTS
+    p = 4096                                                  # a non-NULL, 16-byte aligned address: validation never dereferences it
+
+    def fwd(dm=256, d=16, g=8, tau=0.01, z=p, out=p, ltab=p, ws=p, ws_bytes=1 << 30):
+        return lib.vqk_lfq_forward(z, p, p, p, p, 16, dm, d, g, tau, 0.25, 0.1, 1.0, p, p, p, 0, p, out, ltab, ws, ws_bytes, 0)
+
+    def bwd(dm=256, d=16, g=8, tau=0.01, z=p, dtype=0, ws_bytes=1 << 30):
+        return lib.vqk_lfq_backward(z, p, p, dtype, p, p, p, p, 16, dm, d, g, tau, 0.25, 0.1, 1.0, p, p, p, p, p, 0, p, ws_bytes, 0)
+
+    def dec(dm=256, d=16, idx=p):
+        return lib.vqk_lfq_decode(idx, p, p, 16, dm, d, p, 0, 0)
+
+    for fn in (fwd, bwd, dec):
+        assert fn(dm=6) == -1 and fn(dm=516) == -1 and fn(dm=0) == -1        # D % 4, D > 512
+        assert fn(d=0) == -1 and fn(d=19) == -1
+    for fn in (fwd, bwd):
+        assert fn(g=0) == -1 and fn(g=11) == -1
+        assert fn(tau=0.0) == -5 and fn(tau=-1.0) == -5
+        assert fn(ws_bytes=-1) == -5
+    assert fwd(z=0) == -5 and bwd(z=0) == -5 and dec(idx=0) == -5            # NULL pointers
+    assert fwd(z=p + 4) == -3 and bwd(z=p + 4) == -3                         # alignment
+    assert fwd(ws=p + 8) == -3
+    assert bwd(dtype=7) == -2
+    assert fwd(out=0) == -5 and fwd(ltab=0) == -5 and fwd(ws=0) == -5        # the loss: out, ltab and ws together or not at all
+    assert lib.vqk_lfq_forward(p, p, p, 0, 0, 16, 256, 16, 8, 0.01, 0.25, 0.1, 1.0, p, 0, p, 0, 0, 0, 0, 0, 0, 0) == -5   # q without W_out
+    assert lib.vqk_lfq_decode(p, p, p, 16, 256, 16, 0, 0, 0) == -5           # no output
+    assert lib.vqk_lfq_ws_bytes(16, 6, 16, 8) == -1 and lib.vqk_lfq_ws_bytes(16, 256, 19, 8) == -1
+    assert lib.vqk_lfq_ws_bytes(16, 256, 16, 11) == -1 and lib.vqk_lfq_ws_bytes(-1, 256, 16, 8) == -1
+    need = lib.vqk_lfq_ws_bytes(8192, 256, 16, 8)
+    assert need > 0 and need % 16 == 0
+    assert lib.vqk_lfq_ws_bytes(8192, 256, 16, 8) == need                    # a function of the shape only
+    assert lib.vqk_lfq_ws_bytes(1, 256, 16, 8) < need <= lib.vqk_lfq_ws_bytes(1 << 20, 256, 16, 8)
+    assert lib.vqk_lfq_ws_bytes(8192, 20, 10, 10) >= 256 * (1024 + 2) * 4     # the group tables dominate a narrow latent
+    small = lib.vqk_lfq_ws_bytes(16, 256, 16, 8)
+    assert bwd(ws_bytes=small - 4) == -6 and fwd(ws_bytes=small - 4) == -6
+
+
+def test_launchers_refuse_cpu_tensors():
+    ops = importlib.import_module(PKG + '.ops')
+    w_in, b_in, w_out, b_out = torch.zeros(10, 64), torch.zeros(10), torch.zeros(64, 10), torch.zeros(64)
+    with pytest.raises(RuntimeError, match='GPU only'):
+        ops.LFQFn.apply(torch.zeros(1, 64, 2, 2), w_in, b_in, w_out, b_out, (10, 9, 0.25, 0.1, 1.0, 0.01), torch.float32)
+    with pytest.raises(RuntimeError, match='GPU only'):
+        ops.lfq_assign(torch.zeros(4, 64), w_in, b_in, 10)
+    with pytest.raises(RuntimeError, match='GPU only'):
+        ops.lfq_decode(torch.zeros(4, dtype=torch.int64), w_out, b_out, 10)

@@ -8,6 +8,7 @@
 // (fixed order: every lane ends with the same bits), after which every lane bounds, rounds and forms the token redundantly.
 // The levels and what derives from them travel BY VALUE in the launch arguments (FsqP): nothing about them is read from memory.
 #include "common.h"
+#include "proj_slab.h"
 
 #include <cmath>
 
@@ -192,9 +193,6 @@ template <> __device__ __forceinline__ void fsq_load4<bf16_raw>(const bf16_raw* 
     for (int i = 0; i < 4; ++i) o[i] = bf16_to_f32(v[i]);
 }
 
-// slab of one block (floats): [dW_in d*D][db_in d][dW_out D*d][db_out D], padded to a multiple of 4
-__host__ __device__ inline int64_t fsq_slab_floats(int dm, int d) { return ((int64_t)2 * d * dm + dm + d + 3) & ~(int64_t)3; }
-
 // Backward.  grid = (blocks over rows, 256-channel slices): a block owns ONE chunk per lane (76 accumulators whatever D is); the
 // cotangent g = W_out^T dq of a row needs the whole row of dq, which every slice reads (one slice up to D = 256).  The parameter
 // gradients are sums over rows: per lane in registers over the rows of its wave (fixed by the grid), over the block's waves through
@@ -310,7 +308,7 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* 
         }
     }
     if (wave != 0) return;
-    float* slab = ws + (int64_t)blockIdx.x * fsq_slab_floats(dm, d);
+    float* slab = ws + (int64_t)blockIdx.x * proj_slab_floats(dm, d);
     float* s_bi = slab + d * dm;
     float* s_wo = s_bi + d;
     float* s_bo = s_wo + dm * d;
@@ -331,36 +329,6 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* 
         for (int j = 0; j < kFsqMaxD; ++j)
             if (j < d) s_bi[j] = a_bi[j];
     }
-}
-
-// second launch: the slabs summed in an order fixed by their count, one thread per gradient element; accumulate: add to what the
-// target holds
-__global__ __launch_bounds__(256) void fsq_slab_sum_kernel(const float* __restrict__ ws, int slabs, int dm, int d, int accumulate,
-                                                            float* __restrict__ dw_in, float* __restrict__ db_in,
-                                                            float* __restrict__ dw_out, float* __restrict__ db_out) {
-    const int total = 2 * d * dm + dm + d;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int64_t pitch = fsq_slab_floats(dm, d);
-    // four running sums over the block index (b % 4), combined at the end: a fixed order, and four times the loads in flight
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    const float* src = ws + e;
-    int b = 0;
-#pragma unroll 4
-    for (; b + 4 <= slabs; b += 4) {
-        s0 += src[(b + 0) * pitch];
-        s1 += src[(b + 1) * pitch];
-        s2 += src[(b + 2) * pitch];
-        s3 += src[(b + 3) * pitch];
-    }
-    for (; b < slabs; ++b) s0 += src[b * pitch];
-    const float s = (s0 + s1) + (s2 + s3);
-    float* dst;
-    if (e < d * dm) dst = dw_in + e;
-    else if (e < d * dm + d) dst = db_in + (e - d * dm);
-    else if (e < 2 * d * dm + d) dst = dw_out + (e - d * dm - d);
-    else dst = db_out + (e - 2 * d * dm - d);
-    *dst = accumulate ? *dst + s : s;
 }
 
 // levels (host) -> launch arguments; VQK_ERR_SHAPE for what the kernels do not serve
@@ -426,7 +394,7 @@ int vqk_fsq_decode(const int64_t* idx, const float* w_out, const float* b_out, i
 
 int64_t vqk_fsq_backward_ws_bytes(int64_t n, int dm, int d) {
     if (n < 0 || dm < 4 || dm > 4 * 64 * kFsqMaxChunks || (dm % 4) || d < 1 || d > kFsqMaxD) return VQK_ERR_SHAPE;
-    return (int64_t)fsq_backward_blocks(n) * fsq_slab_floats(dm, d) * (int64_t)sizeof(float);
+    return (int64_t)fsq_backward_blocks(n) * proj_slab_floats(dm, d) * (int64_t)sizeof(float);
 }
 
 int vqk_fsq_backward(const float* z, const float* u, const void* dq, int dq_dtype, const float* w_in, const float* w_out, int64_t n,
@@ -453,7 +421,7 @@ int vqk_fsq_backward(const float* z, const float* u, const void* dq, int dq_dtyp
         VQK_CHECK_LAUNCH();
     }
     const int total = 2 * d * dm + dm + d;
-    hipLaunchKernelGGL(fsq_slab_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, vqk_stream(stream),
+    hipLaunchKernelGGL(proj_slab_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, vqk_stream(stream),
                        reinterpret_cast<const float*>(ws), blocks, dm, d, accumulate, dw_in, db_in, dw_out, db_out);
     VQK_CHECK_LAUNCH();
     return VQK_OK;

@@ -29,7 +29,7 @@ from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
 from .modules.vector_quantizers import (CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer,
-                                        ResidualVectorQuantizer, VectorQuantizer, _flat_view, gather_latent_sample)
+                                        LFQuantizer, ResidualVectorQuantizer, VectorQuantizer, _flat_view, gather_latent_sample)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
 from .optim import FlatAdamW
@@ -128,6 +128,12 @@ class VQVAE(BaseVQVAE, _LightningBase):
             if self.reinit_every_n_epochs is not None:
                 raise ValueError('fsq has no learned codebook: reinit_every_n_epochs must be empty')
             self.quantizer = FSQuantizer(self.cb_size, self.latent_dim, qp['levels'])
+        elif qt == 'lfq':
+            if self.reinit_every_n_epochs is not None:
+                raise ValueError('lfq has no learned codebook: reinit_every_n_epochs must be empty')
+            self.quantizer = LFQuantizer(self.cb_size, self.latent_dim, int(qp['bits']), float(qp.get('commitment_cost', 0.25)),
+                                         float(qp.get('ent_loss_ratio', 0.1)), float(qp.get('ent_temperature', 0.01)),
+                                         float(qp.get('diversity_gamma', 1.0)), int(qp.get('ent_group_bits', 9)))
         elif qt == 'residual':
             depth = int(qp.get('depth', 4))
             if not 1 <= depth <= 8:
@@ -172,7 +178,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         seeding (0 = the seeds)} -> the same with defaults filled in; None for an absent / empty block"""
         if not block:
             return None
-        if qt in ('gumbel', 'fsq'):
+        if qt in ('gumbel', 'fsq', 'lfq'):
             raise ValueError(f'quantizer.codebook_init: the {qt} quantizer has no codebook a k-means start would serve '
                              f'({"no distance lookup" if qt == "gumbel" else "no learned codebook"})')
         unknown = set(block) - {'method', 'samples', 'iters'}

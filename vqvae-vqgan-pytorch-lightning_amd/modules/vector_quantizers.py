@@ -2,7 +2,8 @@
 ``vqvae/modules/vector_quantizers.py`` (VectorQuantizer :8-84, EMAVectorQuantizer :87-203,
 EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274); ``FSQuantizer`` (finite scalar quantization, no counterpart in
 the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (residual quantization, no counterpart either) the sixth,
-``CosineVectorQuantizer`` (the l2-normalised low-dimensional codebook of ViT-VQGAN, no counterpart either) the seventh.
+``CosineVectorQuantizer`` (the l2-normalised low-dimensional codebook of ViT-VQGAN, no counterpart either) the seventh,
+``LFQuantizer`` (lookup-free quantization of MAGVIT-v2: sign bits + an entropy loss, no counterpart either) the eighth.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -280,6 +281,80 @@ class FSQuantizer(BaseVectorQuantizer):
 
     def init_codebook_from_data(self, *args, **kwargs):
         raise ValueError('fsq: there is no learned codebook to initialise from data')
+
+
+class LFQuantizer(BaseVectorQuantizer):
+    """Lookup-free quantization (Yu et al. 2023, MAGVIT-v2; Open-MAGVIT2): the D-channel latent is projected to ``bits`` channels, each
+    is quantized to its sign, the bit pattern is the token (K = 2^bits, first channel = bit 0) and the sign vector is projected back
+    to D channels.  loss = commitment_cost * commit + ent_loss_ratio * (H_sample - diversity_gamma * H_batch): the per-position
+    entropy keeps the bits confident, the entropy of the batch-average distribution -- factorised over groups of ``ent_group_bits``
+    bits -- keeps the vocabulary evenly used.  No learned codebook, no search, no dead codes, no collective (data parallel, the batch
+    average is per rank, as the entropy quantizer's statistics are); training and evaluation behave the same.  One fused kernel each
+    way (csrc/lfq.hip); the two 1x1 projections are ``Conv2d`` modules for their parameters only, as in ``FSQuantizer``.  ``codebook``
+    holds the IMPLICIT codebook, frozen: row i = the +-1 vector of token i.  ``last_parts`` = (commit, H_sample, H_batch) of the last
+    forward, on the device, for logging."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float = 0.25, ent_loss_ratio: float = 0.1,
+                 ent_temperature: float = 0.01, diversity_gamma: float = 1.0, ent_group_bits: int = 9):
+        bits, ent_group_bits = int(bits), int(ent_group_bits)
+        if not 1 <= bits <= ops.LFQ_MAX_BITS:
+            raise ValueError(f'lfq: bits must be between 1 and {ops.LFQ_MAX_BITS}, got {bits}')
+        if num_embeddings != 2 ** bits:
+            raise ValueError(f'lfq: num_embeddings = {num_embeddings} must equal 2**bits = {2 ** bits}')
+        if not 1 <= ent_group_bits <= ops.LFQ_MAX_GROUP_BITS:
+            raise ValueError(f'lfq: ent_group_bits must be between 1 and {ops.LFQ_MAX_GROUP_BITS}, got {ent_group_bits}')
+        if not float(ent_temperature) > 0.0:
+            raise ValueError(f'lfq: ent_temperature must be > 0, got {ent_temperature}')
+        super().__init__(num_embeddings, bits)                # the codebook the base class owns is the implicit one: [K, bits], frozen
+        self.embedding_dim = embedding_dim
+        self.codebook.requires_grad_(False)
+        self.bits, self.ent_group_bits = bits, ent_group_bits
+        self.commitment_cost, self.ent_loss_ratio = float(commitment_cost), float(ent_loss_ratio)
+        self.ent_temperature, self.diversity_gamma = float(ent_temperature), float(diversity_gamma)
+        self.project_in = Conv2d(embedding_dim, bits, 1, bias=True)
+        self.project_out = Conv2d(bits, embedding_dim, 1, bias=True)
+        self.last_parts = None
+        self.init_codebook()
+
+    def implicit_codebook(self) -> torch.Tensor:
+        """[K, bits] fp32: row i, column j = +1 if bit j of i is set, else -1"""
+        tokens = torch.arange(self.num_embeddings, dtype=torch.int64)
+        return (((tokens[:, None] >> torch.arange(self.bits)) & 1) * 2 - 1).to(torch.float32)
+
+    @torch.no_grad()
+    def init_codebook(self) -> None:
+        self.codebook.weight.copy_(self.implicit_codebook())
+
+    def _projections(self):
+        return self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias
+
+    def forward(self, x: torch.Tensor):
+        cfg = (self.bits, self.ent_group_bits, self.commitment_cost, self.ent_loss_ratio, self.diversity_gamma, self.ent_temperature)
+        q, idx, loss, hist, parts = ops.LFQFn.apply(x, *self._projections(), cfg, self.compute_dtype)
+        self.last_hist, self.last_parts = hist, parts
+        return q, idx, loss
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.lfq_assign(_flat_view(z), self.project_in.weight, self.project_in.bias, self.bits).view(x.shape[0], -1)
+
+    @torch.no_grad()
+    def get_codebook(self) -> torch.Tensor:
+        """the [K, D] decoder-side vectors: every token decoded"""
+        tokens = torch.arange(self.num_embeddings, dtype=torch.int64, device=self.project_out.weight.device)
+        return ops.lfq_decode(tokens, self.project_out.weight, self.project_out.bias, self.bits)
+
+    @torch.no_grad()
+    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes (B,N) -> (B,N,D), by bit arithmetic on the token (no [K, D] table is built)"""
+        return ops.lfq_decode(codes, self.project_out.weight, self.project_out.bias, self.bits)
+
+    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
+        raise RuntimeError('lfq: there is no learned codebook to re-initialise')
+
+    def init_codebook_from_data(self, *args, **kwargs):
+        raise ValueError('lfq: there is no learned codebook to initialise from data')
 
 
 class ResidualVectorQuantizer(BaseVectorQuantizer):

@@ -2140,6 +2140,7 @@ if TRACE:
 # ------------------------------------------------------------------------------------------------------
 from ._ops_vq import *        # noqa: E402,F401,F403  quantizers
 from ._ops_fsq import *       # noqa: E402,F401,F403  finite scalar quantizer
+from ._ops_lfq import *       # noqa: E402,F401,F403  lookup-free quantizer
 from ._ops_rvq import *       # noqa: E402,F401,F403  residual quantizer
 from ._ops_cos import *       # noqa: E402,F401,F403  cosine quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
