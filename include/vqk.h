@@ -206,6 +206,21 @@ int vqk_lfq_backward(const float* z, const float* u, const void* dq, int dq_dtyp
                      const float* ltab, const float* gscale_dev, int64_t n, int dm, int d, int g, float tau, float beta, float ratio,
                      float gamma, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out, int accumulate, void* ws,
                      int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- self-attention core ---------
+ * csrc/attn.hip.  o[b][i][h d + c] = sum_j softmax_j(scale <q[b][i][h], k[b][j][h]>) v[b][j][h d + c], lse[b][h][i] = log sum_j
+ * exp(scale <q_i, k_j>) in fp32.  Operands are [B][N][ld] rows of `dtype` (VQK_F32: exact fp32 products; VQK_BF16: bf16 products, fp32
+ * accumulation and statistics, P / dS rounded to bf16 only as matrix operands); every operand has its own row stride in elements
+ * (>= heads * d, a multiple of 16 bytes: VQK_ERR_SHAPE) and starts 16-byte aligned (VQK_ERR_ALIGN), so the slices of one [B][N][3C]
+ * tensor are read in place.  Served: d in {64, 128, 256, 512}, any n >= 1, b and heads <= 65535 (VQK_ERR_SHAPE otherwise, nothing
+ * launched).  Tail keys weigh exactly zero; nothing is read or written past row n.  No call allocates or synchronises.
+ * backward: delta[b][h][i] = sum_c do o (fp32 workspace of B * heads * N floats, written first), P = exp(scale S - lse) recomputed;
+ * dV = P^T dO, dS = P o (dO V^T - delta), dQ = scale dS K, dK = scale dS^T Q.  Every output element is summed by one workgroup in a
+ * fixed order (one pass owns key tiles, one owns query tiles): no atomics, the same bits on every run in every mode. */
+int vqk_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int n, int heads, int d, int64_t ldq,
+                 int64_t ldk, int64_t ldv, int64_t ldo, float scale, void* stream);
+int vqk_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse, const void* dout, void* dq,
+                 void* dk, void* dv, float* delta, int b, int n, int heads, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                 int64_t lddo, int64_t lddq, int64_t lddk, int64_t lddv, float scale, void* stream);
 /* ---------------------------------------------------------------- residual quantizer ---------
  * Lee et al. 2022 (RQ-VAE) / SoundStream (csrc/rvq.hip).  z[N][D] fp32 rows, ONE codebook e[K][D] shared by the `depth` stages:
  * r_0 = z; k_q = argmin_k (|r_{q-1}|^2 + |e_k|^2) - 2 r_{q-1}.e_k (the arithmetic of vqk_vq_forward_f32 with assoc 0, first minimum

@@ -54,6 +54,8 @@ _PROTOS = {
     'vqk_lfq_forward': [P, P, P, P, P, L, I, I, I, F, F, F, F, P, P, P, P, P, P, P, P, L, P],
     'vqk_lfq_decode': [P, P, P, L, I, I, P, P, P],
     'vqk_lfq_backward': [P, P, P, I, P, P, P, P, L, I, I, I, F, F, F, F, P, P, P, P, P, I, P, L, P],
+    'vqk_attn_fwd': [I, P, P, P, P, P, I, I, I, I, L, L, L, L, F, P],
+    'vqk_attn_bwd': [I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, L, L, L, L, L, L, L, L, F, P],
     'vqk_rvq_forward_f32': [P, P, P, L, L, I, I, I, P, P, P, P, P, P],
     'vqk_rvq_decode_f32': [P, P, L, I, I, I, P, P, P],
     'vqk_rvq_backward_f32': [P, P, P, P, I, L, I, I, I, F, F, P, P, P, P, L, P],

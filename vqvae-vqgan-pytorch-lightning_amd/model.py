@@ -147,8 +147,14 @@ class VQVAE(BaseVQVAE, _LightningBase):
             raise ValueError(f'unrecognized quantizer: {qt}')
 
         ch, nrb, mult = ae_conf['channels'], ae_conf['num_res_blocks'], tuple(ae_conf['channel_multipliers'])
-        self.encoder = Encoder(ch, nrb, mult, self.cb_size if qt == 'gumbel' else self.latent_dim)   # model.py:130
-        self.decoder = Decoder(ch, nrb, mult, self.latent_dim)
+        # optional: self-attention blocks behind every ResBlock whose map side is listed (absent / None / []: the pure ResBlock stack).
+        # attn_heads is checked where an AttnBlock is built (it must divide THAT level's channels): without attn_resolutions, or with
+        # sides that never occur, it is not read at all -- intended, a config may carry it while the blocks are switched off
+        attn_heads = ae_conf.get('attn_heads')
+        attn = dict(attn_resolutions=ae_conf.get('attn_resolutions'), attn_heads=1 if attn_heads is None else attn_heads,
+                    image_size=image_size)
+        self.encoder = Encoder(ch, nrb, mult, self.cb_size if qt == 'gumbel' else self.latent_dim, **attn)   # model.py:130
+        self.decoder = Decoder(ch, nrb, mult, self.latent_dim, **attn)
 
         if load_loss:
             if l_conf is None:

@@ -99,6 +99,61 @@ class ResBlock(nn.Module):
                              self.norm1.num_groups, self.norm1.eps, pool, next_gn)
 
 
+class AttnBlock(nn.Module):
+    """Single- or multi-head self-attention over the positions of the map, with the parameter names of the VQ-GAN everybody ports
+    from (``norm``, ``q``, ``k``, ``v``, ``proj_out``: checkpoints map key for key): x + proj_out(attention(q(h), k(h), v(h))),
+    h = norm(x) without SiLU.  NHWC storage is the [B, H*W, C] row matrix the attention kernels read: no layout pass; the residual
+    add rides in proj_out's epilogue."""
+
+    def __init__(self, in_channels: int, heads: int = 1):
+        super().__init__()
+        heads = int(heads)
+        if in_channels % 32:
+            raise ValueError(f'AttnBlock: {in_channels} channels are not a multiple of the 32 GroupNorm groups')
+        if heads < 1 or in_channels % heads:
+            raise ValueError(f'AttnBlock: attn_heads = {heads} does not divide the {in_channels} channels')
+        self.in_channels, self.heads = in_channels, heads
+        self.norm = GroupNorm(32, in_channels, eps=1e-6)
+        self.q = Conv2d(in_channels, in_channels, 1, bias=True)
+        self.k = Conv2d(in_channels, in_channels, 1, bias=True)
+        self.v = Conv2d(in_channels, in_channels, 1, bias=True)
+        self.proj_out = Conv2d(in_channels, in_channels, 1, bias=True)
+
+    def forward(self, x, next_gn: int = 0):
+        # (next_gn: the walks of Encoder / Decoder hand it to every block; a 1x1 conv carries no GroupNorm sums, the next norm
+        # computes its own)
+        h = self.norm(x)
+        a = ops.attention(self.q(h), self.k(h), self.v(h), self.heads)
+        return self.proj_out(a, residual=x)
+
+
+def attn_sides(attn_resolutions, image_size) -> tuple:
+    """the config's ``attn_resolutions`` as a tuple of map sides; absent, None or empty: no attention anywhere"""
+    if attn_resolutions is None:
+        return ()
+    if isinstance(attn_resolutions, (str, bytes)) or not isinstance(attn_resolutions, (list, tuple)):
+        raise ValueError(f'autoencoder.attn_resolutions must be a list of map sides, got {attn_resolutions!r}')
+    sides = []
+    for r in attn_resolutions:
+        if isinstance(r, bool) or not isinstance(r, int) or r < 1:
+            raise ValueError(f'autoencoder.attn_resolutions must hold positive integers, got {r!r}')
+        sides.append(int(r))
+    if sides and image_size is None:
+        raise ValueError('attn_resolutions names map sides: the image size must be given with it')
+    return tuple(sides)
+
+
+def _res_level(ch_in: int, ch_out: int, count: int, side, sides: tuple, heads: int) -> list:
+    """``count`` ResBlocks at one map side, each followed by an AttnBlock when that side is an attention resolution"""
+    out = []
+    for _ in range(count):
+        out.append(ResBlock(ch_in, ch_out))
+        ch_in = ch_out
+        if side in sides:
+            out.append(AttnBlock(ch_out, heads))
+    return out
+
+
 class Downsample(nn.Module):
     def __init__(self, kernel_size: int = 2, stride: int = 2, padding: int = 0):
         super().__init__()
@@ -133,19 +188,22 @@ def _to_internal(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 
 class Encoder(nn.Module):
-    def __init__(self, channels: int, num_res_blocks: int, channel_multipliers: tuple, embedding_dim: int):
+    def __init__(self, channels: int, num_res_blocks: int, channel_multipliers: tuple, embedding_dim: int,
+                 attn_resolutions=None, attn_heads: int = 1, image_size: int = None):
         super().__init__()
         self.compute_dtype = torch.float32
+        sides = attn_sides(attn_resolutions, image_size)
+        side = image_size                                     # (only read when sides is not empty)
         self.conv_in = Conv2d(3, channels, 3, bias=False)
         blocks, ch_in = [], channels
         for mult in channel_multipliers:
             ch_out = channels * mult
-            for _ in range(num_res_blocks):
-                blocks.append(ResBlock(ch_in, ch_out))
-                ch_in = ch_out
+            blocks += _res_level(ch_in, ch_out, num_res_blocks, side, sides, attn_heads)
+            ch_in = ch_out
             blocks.append(Downsample())
+            side = side // 2 if sides else side
         self.blocks = nn.Sequential(*blocks)
-        self.final_residual = nn.Sequential(*[ResBlock(ch_in) for _ in range(num_res_blocks)])
+        self.final_residual = nn.Sequential(*_res_level(ch_in, ch_in, num_res_blocks, side, sides, attn_heads))
         self.norm = GroupNorm(32, ch_in, eps=1e-6)
         self.conv_out = Conv2d(ch_in, embedding_dim, 1, bias=True)
         self.last_cut = None
@@ -201,19 +259,22 @@ class Encoder(nn.Module):
 
 
 class Decoder(nn.Module):
-    def __init__(self, channels: int, num_res_blocks: int, channel_multipliers: tuple, embedding_dim: int):
+    def __init__(self, channels: int, num_res_blocks: int, channel_multipliers: tuple, embedding_dim: int,
+                 attn_resolutions=None, attn_heads: int = 1, image_size: int = None):
         super().__init__()
         self.compute_dtype = torch.float32
+        sides = attn_sides(attn_resolutions, image_size)
+        side = image_size // (2 ** len(channel_multipliers)) if sides else None
         ch_in = channels * channel_multipliers[-1]
         self.conv_in = Conv2d(embedding_dim, ch_in, 3, bias=True)
-        self.initial_residual = nn.Sequential(*[ResBlock(ch_in) for _ in range(num_res_blocks)])
+        self.initial_residual = nn.Sequential(*_res_level(ch_in, ch_in, num_res_blocks, side, sides, attn_heads))
         blocks = []
         for i in reversed(range(len(channel_multipliers))):
             ch_out = channels * channel_multipliers[i - 1] if i > 0 else channels
-            for _ in range(num_res_blocks):
-                blocks.append(ResBlock(ch_in, ch_out))
-                ch_in = ch_out
+            blocks += _res_level(ch_in, ch_out, num_res_blocks, side, sides, attn_heads)
+            ch_in = ch_out
             blocks.append(Upsample(ch_out))
+            side = side * 2 if sides else side
         self.blocks = nn.Sequential(*blocks)
         self.norm = GroupNorm(32, channels, eps=1e-6)
         self.conv_out = Conv2d(channels, 3, 3, bias=True)

@@ -2067,6 +2067,7 @@ VQ_FILTER = _native.switch('VQK_VQ_FILTER', '1') != '0'
 VQ_FUSED = _native.switch('VQK_VQ_FUSED', '1') != '0'      # one forward kernel + one backward kernel (0: the round-3 launch sequence)
 RVQ_FUSED = _native.switch('VQK_RVQ_FUSED', '1') != '0'    # residual quantizer: the one-launch multi-stage forward (0: the staged formulation, _ops_rvq.rvq_staged)
 COS_FUSED = _native.switch('VQK_COS_FUSED', '1') != '0'    # cosine quantizer: the one-launch normalise + rank + gather forward (0: the staged formulation, _ops_cos.cos_staged)
+ATTN_FUSED = _native.switch('VQK_ATTN_FUSED', '1') != '0'   # self-attention: the fused forward / backward kernels (0: the staged formulation, _ops_attn.attention_staged)
 ENTROPY_FUSED_ROWS = _native.switch('VQK_ENTROPY_FUSED_ROWS', '1') != '0'
 ENTROPY_SPLIT_GEMM = _native.switch('VQK_ENTROPY_SPLIT_GEMM', '1') != '0'     # bf16 compute mode: the entropy cotangent's two GEMMs as bf16 split products
 ACT_CODE = {'linear': 0, 'tanh': 1, 'relu': 2, 'lrelu': 3}
@@ -2144,4 +2145,5 @@ from ._ops_lfq import *       # noqa: E402,F401,F403  lookup-free quantizer
 from ._ops_rvq import *       # noqa: E402,F401,F403  residual quantizer
 from ._ops_cos import *       # noqa: E402,F401,F403  cosine quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
+from ._ops_attn import *      # noqa: E402,F401,F403  self-attention core
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins
