@@ -102,6 +102,9 @@ def test_module_state_and_implicit_codebook():
     ae = importlib.import_module(PKG + '.modules.autoencoder')
     q = vqm.FSQuantizer(1000, 64, [8, 5, 5, 5])
     assert set(q.state_dict()) == {'codebook.weight', 'project_in.weight', 'project_in.bias', 'project_out.weight', 'project_out.bias'}
+    # registration order fixes the optimizer's arena layout, and with it the bits of a training step
+    assert [n for n, _ in q.named_parameters()] == ['codebook.weight', 'project_in.weight', 'project_in.bias', 'project_out.weight',
+                                                    'project_out.bias']
     assert isinstance(q.project_in, ae.Conv2d) and isinstance(q.project_out, ae.Conv2d)
     assert tuple(q.project_in.weight.shape) == (4, 64, 1, 1) and tuple(q.project_out.weight.shape) == (64, 4, 1, 1)
     assert tuple(q.codebook.weight.shape) == (1000, 4) and not q.codebook.weight.requires_grad

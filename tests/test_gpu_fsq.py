@@ -1,4 +1,4 @@
-"""The finite scalar quantizer on the GPU (csrc/fsq.hip, _ops_fsq.py, FSQuantizer) against the float64 reference of
+"""The finite scalar quantizer on the GPU (csrc/fsq.hip, csrc/proj_quant.h, _ops_proj.py, FSQuantizer) against the float64 reference of
 tests/fsq_reference.py.
 
 Tokens are integers: the device must return the reference's token on EVERY row -- the generator removed the rows within 1e-3 of a

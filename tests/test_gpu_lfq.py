@@ -1,4 +1,4 @@
-"""The lookup-free quantizer on the GPU (csrc/lfq.hip, _ops_lfq.py, LFQuantizer) against the float64 reference of
+"""The lookup-free quantizer on the GPU (csrc/lfq.hip, csrc/proj_quant.h, _ops_proj.py, LFQuantizer) against the float64 reference of
 tests/lfq_reference.py.
 
 Tokens are integers: the device must return the reference's token on EVERY row -- the generator removed the rows with some |u_j| <

@@ -18,7 +18,7 @@ from ._ops_vq import _PREP_TABLES, _VQPrep, vq_assign
 COS_EPS = 1e-12
 COS_FUSED_DIMS = (8, 16, 32, 64)
 _COS_PREP: dict = {}            # data_ptr of the codebook -> _VQPrep: what vqk_cos_prepare_f32 derived from it
-_COS_WS: dict = {}
+_COS_WS: dict = {}                  # _wkey() -> the per-row terms of the deterministic backward (core.grow_ws)
 
 
 def _cos_prepare_now(ent, cb) -> None:
@@ -27,11 +27,6 @@ def _cos_prepare_now(ent, cb) -> None:
 
 
 _PREP_TABLES.append((_COS_PREP, _cos_prepare_now))       # ops.refresh_vq_prepared keeps these workspaces current too
-
-
-def _f32c(t):
-    t = t.detach()
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
 
 
 def cos_prepared(codebook) -> torch.Tensor | None:
@@ -70,7 +65,7 @@ def _cos_ws(codebook):
     ws = cos_prepared(codebook)
     if ws is not None:
         return ws
-    cb = _f32c(codebook)
+    cb = core.f32c(codebook)
     k, d = cb.shape
     ws = torch.empty(_native.lib().vqk_cos_ws_bytes(k, d), dtype=torch.uint8, device=cb.device)
     _native.check(_native.lib().vqk_cos_prepare_f32(cb.data_ptr(), k, d, ws.data_ptr(), ws.numel(), core._stream()), 'cos_prepare')
@@ -80,7 +75,7 @@ def _cos_ws(codebook):
 def l2norm_rows(x: torch.Tensor, want_inv: bool = False):
     """x [R, D] fp32 (D % 4 == 0) -> nrm(x) [R, D] (and inv [R]): vqk_l2norm_rows_f32, the bits every cosine kernel normalises with"""
     core._require_gpu(x)
-    x = _f32c(x)
+    x = core.f32c(x)
     r, d = x.shape
     xn = torch.empty_like(x)
     inv = torch.empty(r, dtype=torch.float32, device=x.device) if want_inv else None
@@ -144,7 +139,7 @@ def _cos_forward(flat_z, codebook, want_q32: bool, want_lo: bool, want_stats: bo
 def cos_assign(flat_z: torch.Tensor, codebook: torch.Tensor) -> torch.Tensor:
     """flat_z [N, D] fp32 -> idx [N] int64: the forward without q and the statistics"""
     core._require_gpu(flat_z)
-    return _cos_forward(_f32c(flat_z), codebook, False, False, False)[0]
+    return _cos_forward(core.f32c(flat_z), codebook, False, False, False)[0]
 
 
 def cos_decode(idx: torch.Tensor, codebook: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
@@ -160,16 +155,6 @@ def cos_decode(idx: torch.Tensor, codebook: torch.Tensor, out_dtype=torch.float3
     _native.check(_native.lib().vqk_cos_decode_f32(flat.data_ptr(), ws.data_ptr(), ws.numel(), n, k, d, 0 if lo else q.data_ptr(),
                                                    q.data_ptr() if lo else 0, core._stream()), 'cos_decode')
     return q.view(*idx.shape, d)
-
-
-def _cos_bwd_ws(device, nbytes: int) -> torch.Tensor:
-    """the per-row terms of the deterministic backward, one per (device, stream, host thread)"""
-    core._stream()
-    key = core._wkey(device)
-    ws = _COS_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _COS_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
 
 
 class CosLookupFn(torch.autograd.Function):
@@ -215,7 +200,7 @@ class CosLookupFn(torch.autograd.Function):
         ws = _cos_ws(cbp)
         if d in COS_FUSED_DIMS:
             lib = _native.lib()
-            ws2 = _cos_bwd_ws(z.device, lib.vqk_cos_backward_ws_bytes(n, d)) if (core.DETERMINISTIC and de is not None) else None
+            ws2 = core.grow_ws(_COS_WS, z.device, lib.vqk_cos_backward_ws_bytes(n, d)) if (core.DETERMINISTIC and de is not None) else None
             _native.check(lib.vqk_cos_backward_f32(z.data_ptr(), ws.data_ptr(), idx.data_ptr(), core._p(dqc),
                                                    core.dcode(dqc.dtype) if dqc is not None else core.F32, n, k, d, cz, ce, core._p(gs),
                                                    dz.data_ptr(), core._p(de), core._p(ws2), ws2.numel() if ws2 is not None else 0,

@@ -15,17 +15,7 @@ from . import ops as core
 from ._ops_vq import ema_stats, vq_assign
 
 KMEANS_SEED_ROWS = 64           # rows per block of the seeding step (csrc/kmeans.hip: KM_ROWS): N = multiples of it +- 1 are its edges
-_KMEANS_WS: dict = {}
-
-
-def _kmeans_ws(device, nbytes: int) -> torch.Tensor:
-    """the seeding step's block partial sums, one buffer per (device, stream, host thread)"""
-    core._stream()
-    key = core._wkey(device)
-    ws = _KMEANS_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _KMEANS_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
+_KMEANS_WS: dict = {}               # _wkey() -> the block partial sums of the seeding step (core.grow_ws)
 
 
 def _check_rows(x: torch.Tensor, what: str) -> None:
@@ -48,7 +38,7 @@ def kmeans_seed_step(x: torch.Tensor, k: int, j: int, u: torch.Tensor, picks: to
     n, d = x.shape
     lib = _native.lib()
     nbytes = lib.vqk_kmeans_seed_ws_bytes(n)
-    ws = _kmeans_ws(x.device, max(int(nbytes), 16))
+    ws = core.grow_ws(_KMEANS_WS, x.device, max(int(nbytes), 16))
     _native.check(lib.vqk_kmeans_seed_step_f32(x.data_ptr(), n, d, k, j, u.data_ptr(), picks.data_ptr(), mind.data_ptr(), core._p(total),
                                                ws.data_ptr(), ws.numel(), core._stream()), 'kmeans_seed_step')
 
@@ -70,7 +60,7 @@ def kmeans_seed(x: torch.Tensor, k: int, u: torch.Tensor, return_total: bool = F
     mind = torch.empty(n, dtype=torch.float32, device=x.device)
     total = torch.empty(k, dtype=torch.float64, device=x.device) if return_total else None
     lib = _native.lib()
-    ws = _kmeans_ws(x.device, max(int(lib.vqk_kmeans_seed_ws_bytes(n)), 16))
+    ws = core.grow_ws(_KMEANS_WS, x.device, max(int(lib.vqk_kmeans_seed_ws_bytes(n)), 16))
     st = core._stream()
     args = (u.data_ptr(), picks.data_ptr(), mind.data_ptr(), core._p(total), ws.data_ptr(), ws.numel(), st)
     fn, xp = lib.vqk_kmeans_seed_step_f32, x.data_ptr()

@@ -1,6 +1,6 @@
 """Residual-quantizer operators over the vqk C-ABI (csrc/rvq.hip): the autograd Function behind ``ResidualVectorQuantizer`` plus the
 assignment-only and decode launchers, and the STAGED formulation of the same definition on the single-stage lookup.  Private part of
-:mod:`ops` like ``_ops_fsq.py`` (imported at the end of ``ops.py``, which re-exports every name); shared infrastructure is reached
+:mod:`ops` like ``_ops_proj.py`` (imported at the end of ``ops.py``, which re-exports every name); shared infrastructure is reached
 through ``core``.
 
 Definition (include/vqk.h, "residual quantizer"): r_0 = z; k_q = the standard quantizer's argmin on r_{q-1}; r_q = r_{q-1} - e[k_q];
@@ -14,7 +14,7 @@ from . import ops as core
 from ._ops_vq import vq_assign, vq_prepared
 
 RVQ_MAX_DEPTH = 8
-_RVQ_WS: dict = {}
+_RVQ_WS: dict = {}                  # _wkey() -> the residual stack of the deterministic backward (core.grow_ws)
 
 
 def _check_depth(depth) -> int:
@@ -22,21 +22,6 @@ def _check_depth(depth) -> int:
     if not 1 <= depth <= RVQ_MAX_DEPTH:
         raise ValueError(f'residual quantizer: depth must be between 1 and {RVQ_MAX_DEPTH}, got {depth}')
     return depth
-
-
-def _rvq_ws(device, nbytes: int) -> torch.Tensor:
-    """the residual stack of the deterministic backward, one per (device, stream, host thread)"""
-    core._stream()
-    key = core._wkey(device)
-    ws = _RVQ_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _RVQ_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
-
-
-def _f32c(t):
-    t = t.detach()
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
 
 
 def rvq_fused_serves(codebook) -> bool:
@@ -53,14 +38,14 @@ def rvq_staged(flat_z: torch.Tensor, codebook: torch.Tensor, depth: int, want_lo
     depth = _check_depth(depth)
     n, d = flat_z.shape
     k = codebook.shape[0]
-    cb = _f32c(codebook)
+    cb = core.f32c(codebook)
     dev = flat_z.device
     lib, st = _native.lib(), core._stream()
     ws = vq_prepared(codebook) if codebook.is_contiguous() else None
     zbuf = torch.zeros(depth * k + depth, dtype=torch.int32, device=dev)
     hist, sse = zbuf[:depth * k].view(depth, k), zbuf[depth * k:].view(torch.float32)
     idx = torch.empty((n, depth), dtype=torch.int64, device=dev)
-    r = _f32c(flat_z)
+    r = core.f32c(flat_z)
     zhat = None
     for q in range(depth):
         q32 = torch.empty((n, d), dtype=torch.float32, device=dev)
@@ -105,14 +90,14 @@ def rvq_assign(flat_z: torch.Tensor, codebook: torch.Tensor, depth: int) -> torc
     """flat_z [N, D] fp32 -> idx [N, depth] int64: the forward without zhat and the statistics"""
     core._require_gpu(flat_z)
     depth = _check_depth(depth)
-    return _rvq_forward(_f32c(flat_z), codebook, depth, False, False, False)[0]
+    return _rvq_forward(core.f32c(flat_z), codebook, depth, False, False, False)[0]
 
 
 def rvq_decode(idx: torch.Tensor, codebook: torch.Tensor, out_dtype=torch.float32) -> torch.Tensor:
     """idx [..., depth] int64 -> zhat [..., D] in ``out_dtype``: the bits the forward writes for the same tokens"""
     depth = _check_depth(idx.shape[-1])
     core._require_gpu(idx)
-    cb = _f32c(codebook)
+    cb = core.f32c(codebook)
     k, d = cb.shape
     flat = idx.reshape(-1, depth).to(torch.int64).contiguous()
     n = flat.shape[0]
@@ -167,7 +152,7 @@ class RVQLookupFn(torch.autograd.Function):
         cz, ce = beta * scale, scale
         if d == 256:
             lib = _native.lib()
-            ws = _rvq_ws(z.device, lib.vqk_rvq_backward_ws_bytes(n, d, depth)) if (core.DETERMINISTIC and de is not None) else None
+            ws = core.grow_ws(_RVQ_WS, z.device, lib.vqk_rvq_backward_ws_bytes(n, d, depth)) if (core.DETERMINISTIC and de is not None) else None
             _native.check(lib.vqk_rvq_backward_f32(z.data_ptr(), cb.data_ptr(), idx.data_ptr(), core._p(dqc),
                                                    core.dcode(dqc.dtype) if dqc is not None else core.F32, n, k, d, depth, cz, ce,
                                                    core._p(gs), dz.data_ptr(), core._p(de), core._p(ws),

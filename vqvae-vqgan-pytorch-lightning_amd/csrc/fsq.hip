@@ -1,24 +1,18 @@
 // Finite scalar quantizer (Mentzer et al. 2023): u = W_in z + b_in, bounded = tanh(u + shift) * half_l - offset, r = rint(bounded),
 // token = mixed-radix number of (r + half_width), q = W_out (r / half_width) + b_out.  No codebook, no search: one streaming pass.
 //
-// All three kernels work a WAVE PER ROW.  Lane l owns the 16-byte chunks l, l + 64, ... of the row (4 fp32 channels each; at D = 256
-// every lane owns exactly one), so every global access of z / q / dq / dz is 16 bytes per lane (8 bytes for 4 packed bf16) and
-// contiguous over the wave.  W_in [d][D] and W_out^T [d][D] sit in LDS in the same chunk order: a lane reads its own 16 bytes of every
-// projection row, conflict-free.  The d (<= 8) projections of a row are partial dot products per lane + a butterfly over the wave
-// (fixed order: every lane ends with the same bits), after which every lane bounds, rounds and forms the token redundantly.
+// All three kernels work a WAVE PER ROW on the core of proj_quant.h (up to 8 projection channels, 4 chunks per lane: D <= 1024); after the
+// butterfly every lane bounds, rounds and forms the token redundantly.
 // The levels and what derives from them travel BY VALUE in the launch arguments (FsqP): nothing about them is read from memory.
 #include "common.h"
-#include "proj_slab.h"
+#include "proj_quant.h"
 
 #include <cmath>
 
 namespace {
 
 constexpr int kFsqMaxD = 8;          // projection channels
-constexpr int kFsqWaves = 4;         // waves (= rows in flight) per block
-constexpr int kFsqThreads = 64 * kFsqWaves;
 constexpr int kFsqMaxChunks = 4;     // 16-byte chunks per lane: D <= 4 * 64 * 4 = 1024
-constexpr int kFsqSlice = 256;       // channels per backward block (one chunk per lane)
 constexpr int kFsqAcc = 2 * kFsqMaxD * 4 + 4 + kFsqMaxD;     // backward accumulators per lane: dW_in, dW_out, db_out, db_in = 76
 
 struct FsqP {
@@ -35,48 +29,7 @@ __device__ __forceinline__ float fsq_round(const FsqP& p, int j, float u, float&
     return fminf(fmaxf(r, (float)-p.hw[j]), (float)(p.lv[j] - 1 - p.hw[j]));
 }
 
-// 4 channels of q = b_out + sum_j W_out[:, j] c_j, j ascending: THE decode function -- forward and decode share it, same bits
-__device__ __forceinline__ void fsq_q_chunk(const float* woT, int dm, int d, const float (&c)[kFsqMaxD], const float* b_out, int ch,
-                                            float (&o)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = b_out[ch + i];
-#pragma unroll
-    for (int j = 0; j < kFsqMaxD; ++j)
-        if (j < d) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(woT + j * dm + ch);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = fmaf(w[i], c[j], o[i]);
-        }
-}
-
-__device__ __forceinline__ void fsq_store_q(float* q, bf16_raw* q_lo, int64_t at, const float (&o)[4]) {
-    if (q) Vec16<float>::store(q + at, o);
-    if (q_lo) {
-        typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-        const u32x2 v = {vqk_pack_bf16x2(o[0], o[1]), vqk_pack_bf16x2(o[2], o[3])};
-        *reinterpret_cast<u32x2*>(q_lo + at) = v;
-    }
-}
-
-// W_in rows [c0, c0 + cn) -> wi [d][cn], W_out^T (all D channels) -> woT [d][dm]; scalar loads: the parameters need no alignment
-__device__ __forceinline__ void fsq_stage_weights(const float* w_in, const float* w_out, int dm, int d, int c0, int cn, float* wi,
-                                                  float* woT) {
-    if (wi)
-        for (int i = threadIdx.x; i < d * cn; i += kFsqThreads) wi[i] = w_in[(i / cn) * dm + c0 + i % cn];
-    if (woT)
-        for (int i = threadIdx.x; i < d * dm; i += kFsqThreads) woT[(i % d) * dm + i / d] = w_out[i];
-    __syncthreads();
-}
-
-__device__ __forceinline__ void fsq_load_row(const float* z, int64_t row, int dm, int lane, float (&zc)[kFsqMaxChunks][4]) {
-#pragma unroll
-    for (int c = 0; c < kFsqMaxChunks; ++c) {
-        const int ch = (c * 64 + lane) * 4;
-        if (ch < dm) Vec16<float>::load(z + row * dm + ch, zc[c]);
-    }
-}
-
-__global__ __launch_bounds__(kFsqThreads) void fsq_forward_kernel(const float* __restrict__ z, const float* __restrict__ w_in,
+__global__ __launch_bounds__(kProjThreads) void fsq_forward_kernel(const float* __restrict__ z, const float* __restrict__ w_in,
                                                                     const float* __restrict__ b_in, const float* __restrict__ w_out,
                                                                     const float* __restrict__ b_out, int64_t n, int dm, FsqP p,
                                                                     int64_t* __restrict__ idx, float* __restrict__ u_out,
@@ -87,28 +40,21 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_forward_kernel(const float* _
     const bool want_q = q || q_lo;
     float* wi = fsq_smem;
     float* woT = fsq_smem + d * dm;
-    fsq_stage_weights(w_in, w_out, dm, d, 0, dm, wi, want_q ? woT : nullptr);
-    const int64_t stride = (int64_t)gridDim.x * kFsqWaves;
-    int64_t row = (int64_t)blockIdx.x * kFsqWaves + wave;
+    proj_stage_weights(w_in, w_out, dm, d, 0, dm, wi, want_q ? woT : nullptr);
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * kProjWaves;
+    int64_t row = (int64_t)blockIdx.x * kProjWaves + wave;
     float zc[kFsqMaxChunks][4], zn[kFsqMaxChunks][4];
-    if (row < n) fsq_load_row(z, row, dm, lane, zc);
+    if (row < n) proj_load_row(z, row, dm, lane, zc);
     for (; row < n; row += stride) {
-        if (row + stride < n) fsq_load_row(z, row + stride, dm, lane, zn);       // the next row is in flight under this one
+        if (row + stride < n) proj_load_row(z, row + stride, dm, lane, zn);      // the next row is in flight under this one
         float acc[kFsqMaxD];
 #pragma unroll
         for (int j = 0; j < kFsqMaxD; ++j) acc[j] = 0.f;
 #pragma unroll
         for (int c = 0; c < kFsqMaxChunks; ++c) {
             const int ch = (c * 64 + lane) * 4;
-            if (ch < dm) {
-#pragma unroll
-                for (int j = 0; j < kFsqMaxD; ++j)
-                    if (j < d) {
-                        const f32x4 w = *reinterpret_cast<const f32x4*>(wi + j * dm + ch);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[j] = fmaf(zc[c][i], w[i], acc[j]);
-                    }
-            }
+            if (ch < dm) proj_dot_chunk(wi, dm, d, ch, zc[c], acc);
         }
         float cj[kFsqMaxD], uj[kFsqMaxD];
         int token = 0;
@@ -139,8 +85,8 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_forward_kernel(const float* _
                 const int ch = (c * 64 + lane) * 4;
                 if (ch < dm) {
                     float o[4];
-                    fsq_q_chunk(woT, dm, d, cj, b_out, ch, o);
-                    fsq_store_q(q, q_lo, row * dm + ch, o);
+                    proj_q_chunk<kFsqMaxD>(woT, dm, d, [&](int j) { return cj[j]; }, b_out, ch, o);
+                    proj_store_q(q, q_lo, row * dm + ch, o);
                 }
             }
         }
@@ -152,15 +98,16 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_forward_kernel(const float* _
 }
 
 // token -> q: digits by integer arithmetic on the index (no table: an index outside [0, K) still yields in-range digits)
-__global__ __launch_bounds__(kFsqThreads) void fsq_decode_kernel(const int64_t* __restrict__ idx, const float* __restrict__ w_out,
+__global__ __launch_bounds__(kProjThreads) void fsq_decode_kernel(const int64_t* __restrict__ idx, const float* __restrict__ w_out,
                                                                    const float* __restrict__ b_out, int64_t n, int dm, FsqP p,
                                                                    float* __restrict__ q, bf16_raw* __restrict__ q_lo) {
     extern __shared__ __attribute__((aligned(16))) float fsq_smem[];
     const int d = p.d, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* woT = fsq_smem;
-    fsq_stage_weights(nullptr, w_out, dm, d, 0, dm, nullptr, woT);
-    const int64_t stride = (int64_t)gridDim.x * kFsqWaves;
-    for (int64_t row = (int64_t)blockIdx.x * kFsqWaves + wave; row < n; row += stride) {
+    proj_stage_weights(nullptr, w_out, dm, d, 0, dm, nullptr, woT);
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * kProjWaves;
+    for (int64_t row = (int64_t)blockIdx.x * kProjWaves + wave; row < n; row += stride) {
         unsigned rem = (unsigned)idx[row];
         float cj[kFsqMaxD];
 #pragma unroll
@@ -178,38 +125,29 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_decode_kernel(const int64_t* 
             const int ch = (c * 64 + lane) * 4;
             if (ch < dm) {
                 float o[4];
-                fsq_q_chunk(woT, dm, d, cj, b_out, ch, o);
-                fsq_store_q(q, q_lo, row * dm + ch, o);
+                proj_q_chunk<kFsqMaxD>(woT, dm, d, [&](int j) { return cj[j]; }, b_out, ch, o);
+                proj_store_q(q, q_lo, row * dm + ch, o);
             }
         }
     }
 }
 
-template <typename Td> __device__ __forceinline__ void fsq_load4(const Td* p, float (&o)[4]);
-template <> __device__ __forceinline__ void fsq_load4<float>(const float* p, float (&o)[4]) { Vec16<float>::load(p, o); }
-template <> __device__ __forceinline__ void fsq_load4<bf16_raw>(const bf16_raw* p, float (&o)[4]) {
-    const u16x4 v = *reinterpret_cast<const u16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = bf16_to_f32(v[i]);
-}
-
-// Backward.  grid = (blocks over rows, 256-channel slices): a block owns ONE chunk per lane (76 accumulators whatever D is); the
-// cotangent g = W_out^T dq of a row needs the whole row of dq, which every slice reads (one slice up to D = 256).  The parameter
-// gradients are sums over rows: per lane in registers over the rows of its wave (fixed by the grid), over the block's waves through
-// LDS in wave order, then ONE slab per block in the workspace -- plain stores, no atomics, nothing waits on another block.
+// Backward.  grid = (blocks over rows, 256-channel slices), see proj_quant.h: 76 accumulators per lane whatever D is, the block's waves
+// added through LDS in ONE pass over all of them.
 template <typename Td>
-__global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* __restrict__ z, const float* __restrict__ u,
+__global__ __launch_bounds__(kProjThreads) void fsq_backward_kernel(const float* __restrict__ z, const float* __restrict__ u,
                                                                      const Td* __restrict__ dq, const float* __restrict__ w_in,
                                                                      const float* __restrict__ w_out, int64_t n, int dm, FsqP p,
                                                                      float* __restrict__ dz, float* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) float fsq_smem[];
     const int d = p.d, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c0 = blockIdx.y * kFsqSlice;
-    const int cn = dm - c0 < kFsqSlice ? dm - c0 : kFsqSlice;
+    const int c0 = blockIdx.y * kProjSlice;
+    const int cn = dm - c0 < kProjSlice ? dm - c0 : kProjSlice;
     float* woT = fsq_smem;                       // [d][dm]
     float* wi = woT + d * dm;                    // [d][cn]
-    float* red = wi + d * kFsqSlice;             // [kFsqAcc][64]
-    fsq_stage_weights(w_in, w_out, dm, d, c0, cn, wi, woT);
+    float* red = wi + d * kProjSlice;            // [kFsqAcc][64]
+    proj_stage_weights(w_in, w_out, dm, d, c0, cn, wi, woT);
+    __syncthreads();
     const int own = lane * 4;                    // channel inside the slice
     const bool has = own < cn;
     const int nchunks = (dm + 255) / 256;
@@ -223,8 +161,8 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* 
 #pragma unroll
     for (int i = 0; i < 4; ++i) a_bo[i] = 0.f;
 
-    const int64_t stride = (int64_t)gridDim.x * kFsqWaves;
-    for (int64_t row = (int64_t)blockIdx.x * kFsqWaves + wave; row < n; row += stride) {
+    const int64_t stride = (int64_t)gridDim.x * kProjWaves;
+    for (int64_t row = (int64_t)blockIdx.x * kProjWaves + wave; row < n; row += stride) {
         float g[kFsqMaxD], dqo[4] = {0.f, 0.f, 0.f, 0.f}, zo[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < kFsqMaxD; ++j) g[j] = 0.f;
@@ -236,18 +174,12 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* 
             const int ch = (c * 64 + lane) * 4;
             if (ch < dm) {
                 float v[4];
-                fsq_load4<Td>(dq + row * dm + ch, v);
+                proj_load4<Td>(dq + row * dm + ch, v);
                 if (c == (int)blockIdx.y) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) dqo[i] = v[i];
                 }
-#pragma unroll
-                for (int j = 0; j < kFsqMaxD; ++j)
-                    if (j < d) {
-                        const f32x4 w = *reinterpret_cast<const f32x4*>(woT + j * dm + ch);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) g[j] = fmaf(v[i], w[i], g[j]);
-                    }
+                proj_dot_chunk(woT, dm, d, ch, v, g);
             }
         }
         float dzo[4] = {0.f, 0.f, 0.f, 0.f};
@@ -259,25 +191,13 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* 
                 const float cj = fsq_round(p, j, ur[j], t) / hw;
                 const float du = wave_sum(g[j]) / hw * p.half_l[j] * (1.f - t * t);      // straight-through: d r / d bounded = 1
                 a_bi[j] += du;
-                if (has) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(wi + j * cn + own);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        dzo[i] = fmaf(w[i], du, dzo[i]);
-                        a_wi[j][i] = fmaf(du, zo[i], a_wi[j][i]);
-                        a_wo[j][i] = fmaf(dqo[i], cj, a_wo[j][i]);
-                    }
-                }
+                if (has) proj_accumulate(wi + j * cn + own, du, cj, zo, dqo, dzo, a_wi[j], a_wo[j]);
             }
-        if (has) {
-            Vec16<float>::store(dz + row * dm + c0 + own, dzo);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a_bo[i] += dqo[i];
-        }
+        if (has) proj_finish_row(dz + row * dm + c0 + own, dzo, dqo, a_bo);
     }
 
     // the block's waves, added to wave 0 in wave order
-    for (int w = 1; w < kFsqWaves; ++w) {
+    for (int w = 1; w < kProjWaves; ++w) {
         __syncthreads();
         if (wave == w) {
 #pragma unroll
@@ -308,22 +228,7 @@ __global__ __launch_bounds__(kFsqThreads) void fsq_backward_kernel(const float* 
         }
     }
     if (wave != 0) return;
-    float* slab = ws + (int64_t)blockIdx.x * proj_slab_floats(dm, d);
-    float* s_bi = slab + d * dm;
-    float* s_wo = s_bi + d;
-    float* s_bo = s_wo + dm * d;
-    if (has) {
-        const int ch = c0 + own;
-#pragma unroll
-        for (int j = 0; j < kFsqMaxD; ++j)
-            if (j < d) {
-                Vec16<float>::store(slab + j * dm + ch, a_wi[j]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s_wo[(ch + i) * d + j] = a_wo[j][i];
-            }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_bo[ch + i] = a_bo[i];
-    }
+    float* s_bi = proj_store_slab(ws, dm, d, c0 + own, has, a_wi, a_wo, a_bo);
     if (blockIdx.y == 0 && lane == 0) {
 #pragma unroll
         for (int j = 0; j < kFsqMaxD; ++j)
@@ -354,7 +259,7 @@ int fsq_params(int dm, int d, const int32_t* levels, FsqP& p) {
 }
 
 int fsq_row_blocks(int64_t n, int rows_per_block, int cap) { return vqk_grid_1d(n, rows_per_block, cap); }
-int fsq_backward_blocks(int64_t n) { return fsq_row_blocks(n, 4 * kFsqWaves, 256); }      // a function of n only: the same sums every run
+int fsq_backward_blocks(int64_t n) { return fsq_row_blocks(n, 4 * kProjWaves, 256); }      // a function of n only: the same sums every run
 
 }  // namespace
 
@@ -371,7 +276,7 @@ int vqk_fsq_forward(const float* z, const float* w_in, const float* b_in, const 
     VQK_REQUIRE(vqk_aligned16(z) && vqk_aligned16(q) && vqk_aligned16(q_lo), VQK_ERR_ALIGN);
     if (n == 0) return VQK_OK;
     const size_t lds = (size_t)((q || q_lo) ? 2 : 1) * d * dm * sizeof(float);
-    hipLaunchKernelGGL(fsq_forward_kernel, dim3((unsigned)fsq_row_blocks(n, 4 * kFsqWaves, 512)), dim3(kFsqThreads), lds,
+    hipLaunchKernelGGL(fsq_forward_kernel, dim3((unsigned)fsq_row_blocks(n, 4 * kProjWaves, 512)), dim3(kProjThreads), lds,
                        vqk_stream(stream), z, w_in, b_in, w_out, b_out, n, dm, p, idx, u, q, reinterpret_cast<bf16_raw*>(q_lo), hist);
     VQK_CHECK_LAUNCH();
     return VQK_OK;
@@ -385,7 +290,7 @@ int vqk_fsq_decode(const int64_t* idx, const float* w_out, const float* b_out, i
     VQK_REQUIRE(n >= 0 && idx && w_out && b_out && (q || q_lo), VQK_ERR_ARG);
     VQK_REQUIRE(vqk_aligned16(q) && vqk_aligned16(q_lo), VQK_ERR_ALIGN);
     if (n == 0) return VQK_OK;
-    hipLaunchKernelGGL(fsq_decode_kernel, dim3((unsigned)fsq_row_blocks(n, 4 * kFsqWaves, 512)), dim3(kFsqThreads),
+    hipLaunchKernelGGL(fsq_decode_kernel, dim3((unsigned)fsq_row_blocks(n, 4 * kProjWaves, 512)), dim3(kProjThreads),
                        (size_t)d * dm * sizeof(float), vqk_stream(stream), idx, w_out, b_out, n, dm, p, q,
                        reinterpret_cast<bf16_raw*>(q_lo));
     VQK_CHECK_LAUNCH();
@@ -409,22 +314,18 @@ int vqk_fsq_backward(const float* z, const float* u, const void* dq, int dq_dtyp
     VQK_REQUIRE(ws_bytes >= vqk_fsq_backward_ws_bytes(n, dm, d), VQK_ERR_WORKSPACE);
     const int blocks = n > 0 ? fsq_backward_blocks(n) : 0;
     if (n > 0) {
-        const dim3 grid((unsigned)blocks, (unsigned)((dm + kFsqSlice - 1) / kFsqSlice));
-        const size_t lds = ((size_t)d * dm + (size_t)d * kFsqSlice + (size_t)kFsqAcc * 64) * sizeof(float);
+        const dim3 grid((unsigned)blocks, (unsigned)((dm + kProjSlice - 1) / kProjSlice));
+        const size_t lds = ((size_t)d * dm + (size_t)d * kProjSlice + (size_t)kFsqAcc * 64) * sizeof(float);
         float* wsf = reinterpret_cast<float*>(ws);
         if (dq_dtype == VQK_F32)
-            hipLaunchKernelGGL(fsq_backward_kernel<float>, grid, dim3(kFsqThreads), lds, vqk_stream(stream), z, u, (const float*)dq, w_in,
+            hipLaunchKernelGGL(fsq_backward_kernel<float>, grid, dim3(kProjThreads), lds, vqk_stream(stream), z, u, (const float*)dq, w_in,
                                w_out, n, dm, p, dz, wsf);
         else
-            hipLaunchKernelGGL(fsq_backward_kernel<bf16_raw>, grid, dim3(kFsqThreads), lds, vqk_stream(stream), z, u,
+            hipLaunchKernelGGL(fsq_backward_kernel<bf16_raw>, grid, dim3(kProjThreads), lds, vqk_stream(stream), z, u,
                                (const bf16_raw*)dq, w_in, w_out, n, dm, p, dz, wsf);
         VQK_CHECK_LAUNCH();
     }
-    const int total = 2 * d * dm + dm + d;
-    hipLaunchKernelGGL(proj_slab_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, vqk_stream(stream),
-                       reinterpret_cast<const float*>(ws), blocks, dm, d, accumulate, dw_in, db_in, dw_out, db_out);
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
+    return proj_launch_slab_sum(ws, blocks, dm, d, accumulate, dw_in, db_in, dw_out, db_out, vqk_stream(stream));
 }
 
 }  // extern "C"

@@ -3,14 +3,13 @@
 // p_nj = sigmoid(a u_nj), a = 4 / tau: the softmax over the 2^d sign codes factorises into d sigmoids, so H_sample costs d terms per
 // row, and the batch-average distribution is kept per GROUP of g consecutive bits (tables of 2^g entries).  No codebook, no search.
 //
-// The kernels follow fsq.hip: a WAVE PER ROW, lane l owns the 16-byte chunks l, l + 64 of the row, W_in [d][D] and W_out^T [d][D] sit in
-// LDS in chunk order, the d projections of a row are per-lane partial dot products + a butterfly (every lane ends with the same bits).
+// The kernels work a WAVE PER ROW on the core of proj_quant.h (up to 18 projection channels, 2 chunks per lane: D <= 512).
 // What is per CHANNEL (sigmoid, entropy term, commitment term) runs once per row on lane j for channel j; what is per group CODE runs
 // on the lane whose id equals the code's low 6 bits, looping over the remaining 2^(g_s - 6) codes.
 // Every sum over rows is ordered: registers / wave-private LDS tables over the rows of a wave (fixed by the grid), the block's waves in
 // wave order, one slab per block in the workspace, a second launch that adds the slabs in an order fixed by their count.  No fp32 atomics.
 #include "common.h"
-#include "proj_slab.h"
+#include "proj_quant.h"
 
 #include <cmath>
 
@@ -18,11 +17,8 @@ namespace {
 
 constexpr int kLfqMaxBits = 18;      // projection channels
 constexpr int kLfqMaxGroup = 10;     // bits per entropy group: tables of at most 1024 entries
-constexpr int kLfqWaves = 4;         // waves (= rows in flight) per block
-constexpr int kLfqThreads = 64 * kLfqWaves;
 constexpr int kLfqMaxChunks = 2;     // 16-byte chunks per lane: D <= 2 * 64 * 4 = 512
 constexpr int kLfqMaxD = 4 * 64 * kLfqMaxChunks;
-constexpr int kLfqSlice = 256;       // channels per backward block (one chunk per lane)
 constexpr int kLfqRed = kLfqMaxBits * 4 + 4;      // floats per lane of one block-reduction pass: 72 + (db_out 4 | db_in 1)
 constexpr int kLfqFinish = 1024;     // threads of the forward's finish launch
 constexpr float kLfqEps = 1e-10f;    // the epsilon of get_codebook_usage
@@ -34,50 +30,14 @@ struct LfqP {
 
 // the largest table over the served (d, g): d = 18, g = 10 -> 2 groups of 1024
 constexpr int kLfqMaxTab = 2 << kLfqMaxGroup;
-constexpr int kLfqFwdLds = (2 * kLfqMaxBits * kLfqMaxD + kLfqWaves * kLfqMaxTab + 2 * kLfqWaves) * 4;
-constexpr int kLfqBwdLds = (kLfqMaxBits * kLfqMaxD + kLfqMaxBits * kLfqSlice + kLfqMaxTab + kLfqRed * 64) * 4;
+constexpr int kLfqFwdLds = (2 * kLfqMaxBits * kLfqMaxD + kProjWaves * kLfqMaxTab + 2 * kProjWaves) * 4;
+constexpr int kLfqBwdLds = (kLfqMaxBits * kLfqMaxD + kLfqMaxBits * kProjSlice + kLfqMaxTab + kLfqRed * 64) * 4;
 
-// 4 channels of q = b_out + sum_j W_out[:, j] c_j, j ascending: THE decode function -- forward and decode share it, same bits.
-// bit j of `token` set: c_j = +1, else -1
-__device__ __forceinline__ void lfq_q_chunk(const float* woT, int dm, int d, unsigned token, const float* b_out, int ch, float (&o)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = b_out[ch + i];
-#pragma unroll
-    for (int j = 0; j < kLfqMaxBits; ++j)
-        if (j < d) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(woT + j * dm + ch);
-            const float c = ((token >> j) & 1u) ? 1.f : -1.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = fmaf(w[i], c, o[i]);
-        }
-}
-
-__device__ __forceinline__ void lfq_store_q(float* q, bf16_raw* q_lo, int64_t at, const float (&o)[4]) {
-    if (q) Vec16<float>::store(q + at, o);
-    if (q_lo) {
-        typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-        const u32x2 v = {vqk_pack_bf16x2(o[0], o[1]), vqk_pack_bf16x2(o[2], o[3])};
-        *reinterpret_cast<u32x2*>(q_lo + at) = v;
-    }
-}
-
-// W_in rows [c0, c0 + cn) -> wi [d][cn], W_out^T (all D channels) -> woT [d][dm]; scalar loads: the parameters need no alignment.
-// The caller synchronises.
-__device__ __forceinline__ void lfq_stage_weights(const float* w_in, const float* w_out, int dm, int d, int c0, int cn, float* wi,
-                                                  float* woT) {
-    if (wi)
-        for (int i = threadIdx.x; i < d * cn; i += kLfqThreads) wi[i] = w_in[(i / cn) * dm + c0 + i % cn];
-    if (woT)
-        for (int i = threadIdx.x; i < d * dm; i += kLfqThreads) woT[(i % d) * dm + i / d] = w_out[i];
-}
-
-__device__ __forceinline__ void lfq_load_row(const float* z, int64_t row, int dm, int lane, float (&zc)[kLfqMaxChunks][4]) {
-#pragma unroll
-    for (int c = 0; c < kLfqMaxChunks; ++c) {
-        const int ch = (c * 64 + lane) * 4;
-        if (ch < dm) Vec16<float>::load(z + row * dm + ch, zc[c]);
-    }
-}
+// channel j's code out of the token: bit j set: c_j = +1, else -1
+struct LfqCode {
+    unsigned token;
+    __device__ __forceinline__ float operator()(int j) const { return ((token >> j) & 1u) ? 1.f : -1.f; }
+};
 
 // the value lane `lane` owns out of a wave-uniform register array (0 for lane >= d)
 __device__ __forceinline__ float lfq_own(const float (&v)[kLfqMaxBits], int lane) {
@@ -130,7 +90,7 @@ __device__ __forceinline__ float lfq_group_high(const float (&ph)[4], const floa
 __host__ __device__ inline int64_t lfq_fwd_slab_floats(int tab) { return ((int64_t)tab + 2 + 3) & ~(int64_t)3; }
 
 // Forward.  ws == nullptr: assignment only (no loss, no tables).
-__global__ __launch_bounds__(kLfqThreads) void lfq_forward_kernel(const float* __restrict__ z, const float* __restrict__ w_in,
+__global__ __launch_bounds__(kProjThreads) void lfq_forward_kernel(const float* __restrict__ z, const float* __restrict__ w_in,
                                                                     const float* __restrict__ b_in, const float* __restrict__ w_out,
                                                                     const float* __restrict__ b_out, int64_t n, int dm, LfqP p,
                                                                     int64_t* __restrict__ idx, float* __restrict__ u_out,
@@ -142,20 +102,20 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_forward_kernel(const float* _
     float* wi = lfq_smem;                                        // [d][dm]
     float* woT = wi + d * dm;                                    // [d][dm] when q is wanted
     float* tabs = woT + (want_q ? d * dm : 0);                   // [waves][p.tab] when the loss is wanted
-    float* red = tabs + (ws ? kLfqWaves * p.tab : 0);            // [waves][2]
-    lfq_stage_weights(w_in, w_out, dm, d, 0, dm, wi, want_q ? woT : nullptr);
+    float* red = tabs + (ws ? kProjWaves * p.tab : 0);           // [waves][2]
+    proj_stage_weights(w_in, w_out, dm, d, 0, dm, wi, want_q ? woT : nullptr);
     if (ws)
-        for (int i = threadIdx.x; i < kLfqWaves * p.tab; i += kLfqThreads) tabs[i] = 0.f;
+        for (int i = threadIdx.x; i < kProjWaves * p.tab; i += kProjThreads) tabs[i] = 0.f;
     __syncthreads();
     float* tab = tabs + wave * p.tab;                            // this wave's own tables: no other wave touches them before the end
     float a_commit = 0.f, a_h = 0.f;                             // lane j: channel j over the rows of this wave
 
-    const int64_t stride = (int64_t)gridDim.x * kLfqWaves;
-    int64_t row = (int64_t)blockIdx.x * kLfqWaves + wave;
+    const int64_t stride = (int64_t)gridDim.x * kProjWaves;
+    int64_t row = (int64_t)blockIdx.x * kProjWaves + wave;
     float zc[kLfqMaxChunks][4], zn[kLfqMaxChunks][4];
-    if (row < n) lfq_load_row(z, row, dm, lane, zc);
+    if (row < n) proj_load_row(z, row, dm, lane, zc);
     for (; row < n; row += stride) {
-        if (row + stride < n) lfq_load_row(z, row + stride, dm, lane, zn);       // the next row is in flight under this one
+        if (row + stride < n) proj_load_row(z, row + stride, dm, lane, zn);      // the next row is in flight under this one
         float uj[kLfqMaxBits];
 #pragma unroll
         for (int j = 0; j < kLfqMaxBits; ++j) uj[j] = 0.f;
@@ -163,6 +123,7 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_forward_kernel(const float* _
         for (int c = 0; c < kLfqMaxChunks; ++c) {
             const int ch = (c * 64 + lane) * 4;
             if (ch < dm) {
+                // proj_dot_chunk, written out: through the helper this kernel is allocated 94 VGPRs instead of 98 and scheduled anew
 #pragma unroll
                 for (int j = 0; j < kLfqMaxBits; ++j)
                     if (j < d) {
@@ -191,8 +152,8 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_forward_kernel(const float* _
                 const int ch = (c * 64 + lane) * 4;
                 if (ch < dm) {
                     float o[4];
-                    lfq_q_chunk(woT, dm, d, token, b_out, ch, o);
-                    lfq_store_q(q, q_lo, row * dm + ch, o);
+                    proj_q_chunk<kLfqMaxBits>(woT, dm, d, LfqCode{token}, b_out, ch, o);
+                    proj_store_q(q, q_lo, row * dm + ch, o);
                 }
             }
         }
@@ -224,14 +185,14 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_forward_kernel(const float* _
     if (lane == 0) { red[wave * 2] = c_sum; red[wave * 2 + 1] = h_sum; }
     __syncthreads();
     float* slab = ws + (int64_t)blockIdx.x * lfq_fwd_slab_floats(p.tab);
-    for (int i = threadIdx.x; i < p.tab; i += kLfqThreads) {
+    for (int i = threadIdx.x; i < p.tab; i += kProjThreads) {
         float s = tabs[i];
-        for (int w = 1; w < kLfqWaves; ++w) s += tabs[w * p.tab + i];
+        for (int w = 1; w < kProjWaves; ++w) s += tabs[w * p.tab + i];
         slab[i] = s;
     }
     if (threadIdx.x < 2) {
         float s = red[threadIdx.x];
-        for (int w = 1; w < kLfqWaves; ++w) s += red[w * 2 + threadIdx.x];
+        for (int w = 1; w < kProjWaves; ++w) s += red[w * 2 + threadIdx.x];
         slab[p.tab + threadIdx.x] = s;
     }
 }
@@ -284,61 +245,53 @@ __global__ __launch_bounds__(kLfqFinish) void lfq_finish_kernel(const float* __r
 }
 
 // token -> q by bit arithmetic on the index (no table: any int64 yields a valid sign vector)
-__global__ __launch_bounds__(kLfqThreads) void lfq_decode_kernel(const int64_t* __restrict__ idx, const float* __restrict__ w_out,
+__global__ __launch_bounds__(kProjThreads) void lfq_decode_kernel(const int64_t* __restrict__ idx, const float* __restrict__ w_out,
                                                                    const float* __restrict__ b_out, int64_t n, int dm, int d,
                                                                    float* __restrict__ q, bf16_raw* __restrict__ q_lo) {
     extern __shared__ __attribute__((aligned(16))) float lfq_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* woT = lfq_smem;
-    lfq_stage_weights(nullptr, w_out, dm, d, 0, dm, nullptr, woT);
+    proj_stage_weights(nullptr, w_out, dm, d, 0, dm, nullptr, woT);
     __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * kLfqWaves;
-    for (int64_t row = (int64_t)blockIdx.x * kLfqWaves + wave; row < n; row += stride) {
+    const int64_t stride = (int64_t)gridDim.x * kProjWaves;
+    for (int64_t row = (int64_t)blockIdx.x * kProjWaves + wave; row < n; row += stride) {
         const unsigned token = (unsigned)idx[row];
 #pragma unroll
         for (int c = 0; c < kLfqMaxChunks; ++c) {
             const int ch = (c * 64 + lane) * 4;
             if (ch < dm) {
                 float o[4];
-                lfq_q_chunk(woT, dm, d, token, b_out, ch, o);
-                lfq_store_q(q, q_lo, row * dm + ch, o);
+                proj_q_chunk<kLfqMaxBits>(woT, dm, d, LfqCode{token}, b_out, ch, o);
+                proj_store_q(q, q_lo, row * dm + ch, o);
             }
         }
     }
-}
-
-template <typename Td> __device__ __forceinline__ void lfq_load4(const Td* p, float (&o)[4]);
-template <> __device__ __forceinline__ void lfq_load4<float>(const float* p, float (&o)[4]) { Vec16<float>::load(p, o); }
-template <> __device__ __forceinline__ void lfq_load4<bf16_raw>(const bf16_raw* p, float (&o)[4]) {
-    const u16x4 v = *reinterpret_cast<const u16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = bf16_to_f32(v[i]);
 }
 
 struct LfqLossP {
     float c_commit, c_hs, c_hb;      // 2 beta / (N d),  w a^2 / N,  w gamma a / N: the loss gradient at u without the cotangent
 };
 
-// Backward.  grid = (blocks over rows, 256-channel slices) as in fsq.hip.  The gradient at u is straight-through from dq (g = W_out^T dq,
+// Backward.  grid = (blocks over rows, 256-channel slices), see proj_quant.h.  The gradient at u is straight-through from dq (g = W_out^T dq,
 // no tanh) plus s * dloss/du, s = *gscale_dev:
 //   dloss/du_nj = c_commit (u - c) - c_hs u p (1 - p) + c_hb sum_m L(m) P_n(m) (bit_j(m) - p_nj)   (m over the codes of j's group)
 // The group sum is walked as in the forward: S = sum_m L P and S_j = sum_{m: bit_j(m)} L P per bit, then S_j - p_j S.
 template <typename Td>
-__global__ __launch_bounds__(kLfqThreads) void lfq_backward_kernel(const float* __restrict__ z, const float* __restrict__ u,
+__global__ __launch_bounds__(kProjThreads) void lfq_backward_kernel(const float* __restrict__ z, const float* __restrict__ u,
                                                                      const Td* __restrict__ dq, const float* __restrict__ w_in,
                                                                      const float* __restrict__ w_out, const float* __restrict__ ltab,
                                                                      const float* __restrict__ gscale_dev, int64_t n, int dm, LfqP p,
                                                                      LfqLossP lp, float* __restrict__ dz, float* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) float lfq_smem[];
     const int d = p.d, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c0 = blockIdx.y * kLfqSlice;
-    const int cn = dm - c0 < kLfqSlice ? dm - c0 : kLfqSlice;
+    const int c0 = blockIdx.y * kProjSlice;
+    const int cn = dm - c0 < kProjSlice ? dm - c0 : kProjSlice;
     float* woT = lfq_smem;                       // [d][dm]
     float* wi = woT + d * dm;                    // [d][cn]
-    float* lt = wi + d * kLfqSlice;              // [p.tab]
+    float* lt = wi + d * kProjSlice;             // [p.tab]
     float* red = lt + p.tab;                     // [kLfqRed][64]
-    lfq_stage_weights(w_in, w_out, dm, d, c0, cn, wi, woT);
-    for (int i = threadIdx.x; i < p.tab; i += kLfqThreads) lt[i] = ltab[i];
+    proj_stage_weights(w_in, w_out, dm, d, c0, cn, wi, woT);
+    for (int i = threadIdx.x; i < p.tab; i += kProjThreads) lt[i] = ltab[i];
     __syncthreads();
     const float gs_loss = gscale_dev ? *gscale_dev : 1.f;
     const int own = lane * 4;                    // channel inside the slice
@@ -353,8 +306,8 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_backward_kernel(const float* 
 #pragma unroll
     for (int i = 0; i < 4; ++i) a_bo[i] = 0.f;
 
-    const int64_t stride = (int64_t)gridDim.x * kLfqWaves;
-    for (int64_t row = (int64_t)blockIdx.x * kLfqWaves + wave; row < n; row += stride) {
+    const int64_t stride = (int64_t)gridDim.x * kProjWaves;
+    for (int64_t row = (int64_t)blockIdx.x * kProjWaves + wave; row < n; row += stride) {
         float g[kLfqMaxBits], dqo[4] = {0.f, 0.f, 0.f, 0.f}, zo[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < kLfqMaxBits; ++j) g[j] = 0.f;
@@ -364,18 +317,12 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_backward_kernel(const float* 
             const int ch = (c * 64 + lane) * 4;
             if (ch < dm) {
                 float v[4];
-                lfq_load4<Td>(dq + row * dm + ch, v);
+                proj_load4<Td>(dq + row * dm + ch, v);
                 if (c == (int)blockIdx.y) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) dqo[i] = v[i];
                 }
-#pragma unroll
-                for (int j = 0; j < kLfqMaxBits; ++j)
-                    if (j < d) {
-                        const f32x4 w = *reinterpret_cast<const f32x4*>(woT + j * dm + ch);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) g[j] = fmaf(v[i], w[i], g[j]);
-                    }
+                proj_dot_chunk(woT, dm, d, ch, v, g);
             }
         }
         // the loss gradient of channel `lane`, on lane `lane`
@@ -411,26 +358,14 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_backward_kernel(const float* 
                 const float du = wave_sum(g[j]) + __shfl(lgrad, j, 64);
                 const float cj = __shfl(cj_mine, j, 64);
                 if (lane == j) a_bi += du;
-                if (has) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(wi + j * cn + own);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        dzo[i] = fmaf(w[i], du, dzo[i]);
-                        a_wi[j][i] = fmaf(du, zo[i], a_wi[j][i]);
-                        a_wo[j][i] = fmaf(dqo[i], cj, a_wo[j][i]);
-                    }
-                }
+                if (has) proj_accumulate(wi + j * cn + own, du, cj, zo, dqo, dzo, a_wi[j], a_wo[j]);
             }
-        if (has) {
-            Vec16<float>::store(dz + row * dm + c0 + own, dzo);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a_bo[i] += dqo[i];
-        }
+        if (has) proj_finish_row(dz + row * dm + c0 + own, dzo, dqo, a_bo);
     }
 
     // the block's waves, added to wave 0 in wave order; two passes through one buffer: (dW_in, db_out), then (dW_out, db_in)
     for (int pass = 0; pass < 2; ++pass)
-        for (int w = 1; w < kLfqWaves; ++w) {
+        for (int w = 1; w < kProjWaves; ++w) {
             __syncthreads();
             if (wave == w) {
 #pragma unroll
@@ -458,22 +393,7 @@ __global__ __launch_bounds__(kLfqThreads) void lfq_backward_kernel(const float* 
             }
         }
     if (wave != 0) return;
-    float* slab = ws + (int64_t)blockIdx.x * proj_slab_floats(dm, d);
-    float* s_bi = slab + d * dm;
-    float* s_wo = s_bi + d;
-    float* s_bo = s_wo + dm * d;
-    if (has) {
-        const int ch = c0 + own;
-#pragma unroll
-        for (int j = 0; j < kLfqMaxBits; ++j)
-            if (j < d) {
-                Vec16<float>::store(slab + j * dm + ch, a_wi[j]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s_wo[(ch + i) * d + j] = a_wo[j][i];
-            }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_bo[ch + i] = a_bo[i];
-    }
+    float* s_bi = proj_store_slab(ws, dm, d, c0 + own, has, a_wi, a_wo, a_bo);
     if (blockIdx.y == 0 && lane < d) s_bi[lane] = a_bi;
 }
 
@@ -491,7 +411,7 @@ int lfq_params(int dm, int d, int g, float tau, LfqP& p) {
 }
 
 // a function of n only: the same sums every run
-int lfq_blocks(int64_t n) { return vqk_grid_1d(n, 4 * kLfqWaves, 256); }
+int lfq_blocks(int64_t n) { return vqk_grid_1d(n, 4 * kProjWaves, 256); }
 
 }  // namespace
 
@@ -521,8 +441,8 @@ int vqk_lfq_forward(const float* z, const float* w_in, const float* b_in, const 
         static const hipError_t attr = hipFuncSetAttribute((const void*)lfq_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                            kLfqFwdLds);
         if (attr != hipSuccess) return VQK_ERR_LAUNCH;
-        const size_t lds = ((size_t)((q || q_lo) ? 2 : 1) * d * dm + (ws ? (size_t)kLfqWaves * p.tab + 2 * kLfqWaves : 0)) * sizeof(float);
-        hipLaunchKernelGGL(lfq_forward_kernel, dim3((unsigned)blocks), dim3(kLfqThreads), lds, st, z, w_in, b_in, w_out, b_out, n, dm, p,
+        const size_t lds = ((size_t)((q || q_lo) ? 2 : 1) * d * dm + (ws ? (size_t)kProjWaves * p.tab + 2 * kProjWaves : 0)) * sizeof(float);
+        hipLaunchKernelGGL(lfq_forward_kernel, dim3((unsigned)blocks), dim3(kProjThreads), lds, st, z, w_in, b_in, w_out, b_out, n, dm, p,
                            idx, u, q, reinterpret_cast<bf16_raw*>(q_lo), hist, reinterpret_cast<float*>(ws));
         VQK_CHECK_LAUNCH();
     }
@@ -541,7 +461,7 @@ int vqk_lfq_decode(const int64_t* idx, const float* w_out, const float* b_out, i
     VQK_REQUIRE(n >= 0 && idx && w_out && b_out && (q || q_lo), VQK_ERR_ARG);
     VQK_REQUIRE(vqk_aligned16(q) && vqk_aligned16(q_lo), VQK_ERR_ALIGN);
     if (n == 0) return VQK_OK;
-    hipLaunchKernelGGL(lfq_decode_kernel, dim3((unsigned)lfq_blocks(n)), dim3(kLfqThreads), (size_t)d * dm * sizeof(float),
+    hipLaunchKernelGGL(lfq_decode_kernel, dim3((unsigned)lfq_blocks(n)), dim3(kProjThreads), (size_t)d * dm * sizeof(float),
                        vqk_stream(stream), idx, w_out, b_out, n, dm, d, q, reinterpret_cast<bf16_raw*>(q_lo));
     VQK_CHECK_LAUNCH();
     return VQK_OK;
@@ -564,29 +484,25 @@ int vqk_lfq_backward(const float* z, const float* u, const void* dq, int dq_dtyp
         const double nn = (double)n;
         const LfqLossP lp = {(float)(2.0 * beta / (nn * d)), (float)((double)ratio * p.a * p.a / nn),
                              (float)((double)ratio * gamma * p.a / nn)};
-        const dim3 grid((unsigned)blocks, (unsigned)((dm + kLfqSlice - 1) / kLfqSlice));
-        const size_t lds = ((size_t)d * dm + (size_t)d * kLfqSlice + (size_t)p.tab + (size_t)kLfqRed * 64) * sizeof(float);
+        const dim3 grid((unsigned)blocks, (unsigned)((dm + kProjSlice - 1) / kProjSlice));
+        const size_t lds = ((size_t)d * dm + (size_t)d * kProjSlice + (size_t)p.tab + (size_t)kLfqRed * 64) * sizeof(float);
         float* wsf = reinterpret_cast<float*>(ws);
         if (dq_dtype == VQK_F32) {
             static const hipError_t attr = hipFuncSetAttribute((const void*)lfq_backward_kernel<float>,
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, kLfqBwdLds);
             if (attr != hipSuccess) return VQK_ERR_LAUNCH;
-            hipLaunchKernelGGL(lfq_backward_kernel<float>, grid, dim3(kLfqThreads), lds, st, z, u, (const float*)dq, w_in, w_out, ltab,
+            hipLaunchKernelGGL(lfq_backward_kernel<float>, grid, dim3(kProjThreads), lds, st, z, u, (const float*)dq, w_in, w_out, ltab,
                                gscale_dev, n, dm, p, lp, dz, wsf);
         } else {
             static const hipError_t attr = hipFuncSetAttribute((const void*)lfq_backward_kernel<bf16_raw>,
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, kLfqBwdLds);
             if (attr != hipSuccess) return VQK_ERR_LAUNCH;
-            hipLaunchKernelGGL(lfq_backward_kernel<bf16_raw>, grid, dim3(kLfqThreads), lds, st, z, u, (const bf16_raw*)dq, w_in, w_out,
+            hipLaunchKernelGGL(lfq_backward_kernel<bf16_raw>, grid, dim3(kProjThreads), lds, st, z, u, (const bf16_raw*)dq, w_in, w_out,
                                ltab, gscale_dev, n, dm, p, lp, dz, wsf);
         }
         VQK_CHECK_LAUNCH();
     }
-    const int total = 2 * d * dm + dm + d;
-    hipLaunchKernelGGL(proj_slab_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float*>(ws),
-                       blocks, dm, d, accumulate, dw_in, db_in, dw_out, db_out);
-    VQK_CHECK_LAUNCH();
-    return VQK_OK;
+    return proj_launch_slab_sum(ws, blocks, dm, d, accumulate, dw_in, db_in, dw_out, db_out, st);
 }
 
 }  // extern "C"

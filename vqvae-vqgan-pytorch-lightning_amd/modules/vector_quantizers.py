@@ -133,10 +133,7 @@ class EMAVectorQuantizer(BaseVectorQuantizer):
         ops.ema_apply(self.pending_stats, self.ema_count, self.ema_weight, self.codebook.weight.data, self.decay,
                       self.epsilon, batch)
 
-    @torch.no_grad()
-    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
-        z = ops.nhwc(x.to(torch.float32))
-        return ops.vq_assign(_flat_view(z), self.codebook.weight.detach().contiguous(), 0).view(x.shape[0], -1)
+    vec_to_codes = VectorQuantizer.vec_to_codes           # the same nearest-code assignment
 
 
 class EntropyVectorQuantizer(BaseVectorQuantizer):
@@ -214,14 +211,59 @@ class GumbelVectorQuantizer(BaseVectorQuantizer):
         return idx
 
 
-class FSQuantizer(BaseVectorQuantizer):
+class _ProjectionQuantizer(BaseVectorQuantizer):
+    """What the quantizers without a learned codebook share (``FSQuantizer``, ``LFQuantizer``): the D-channel latent is projected to
+    ``channels`` channels, every channel is quantized on its own, the token is a number formed from the channels' codes and the code
+    vector is projected back to D channels (the kernel core of csrc/proj_quant.h).  The two 1x1 projections are ``Conv2d`` modules for
+    their parameters (names, initialisation, weight-decay group) only -- the kernels read their [d, D] / [D, d] weight memory directly.
+    ``codebook`` holds the IMPLICIT codebook [K, channels], frozen.  A subclass validates its arguments, then supplies
+    ``implicit_codebook()``, ``forward()`` and its assignment / decode operator (``_assign(flat_z)``, ``_decode(codes)``); ``kind``
+    words the messages."""
+    kind = ''
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, channels: int):
+        super().__init__(num_embeddings, channels)            # the codebook the base class owns is the implicit one, frozen
+        self.embedding_dim = embedding_dim
+        self.codebook.requires_grad_(False)
+        self.project_in = Conv2d(embedding_dim, channels, 1, bias=True)      # registration order codebook, project_in, project_out:
+        self.project_out = Conv2d(channels, embedding_dim, 1, bias=True)     # the optimizer's arena layout follows it
+
+    @torch.no_grad()
+    def init_codebook(self) -> None:
+        self.codebook.weight.copy_(self.implicit_codebook())
+
+    def _projections(self):
+        return self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        z = ops.nhwc(x.to(torch.float32))
+        return self._assign(_flat_view(z)).view(x.shape[0], -1)
+
+    @torch.no_grad()
+    def get_codebook(self) -> torch.Tensor:
+        """the [K, D] decoder-side vectors: every token decoded"""
+        return self.codes_to_vec(torch.arange(self.num_embeddings, dtype=torch.int64, device=self.project_out.weight.device))
+
+    @torch.no_grad()
+    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes (B,N) -> (B,N,D), by arithmetic on the token (no [K, D] table is built)"""
+        return self._decode(codes)
+
+    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
+        raise RuntimeError(f'{self.kind}: there is no learned codebook to re-initialise')
+
+    def init_codebook_from_data(self, *args, **kwargs):
+        raise ValueError(f'{self.kind}: there is no learned codebook to initialise from data')
+
+
+class FSQuantizer(_ProjectionQuantizer):
     """Finite scalar quantization (Mentzer et al. 2023): the D-channel latent is projected to ``len(levels)`` channels, each is
     tanh-bounded and rounded to one of its ``levels[j]`` integer values, the mixed-radix number of the rounded vector is the
     token, and the rounded vector is projected back to D channels.  No learned codebook, no latent loss, no dead codes, no
-    statistics to all-reduce; training and evaluation behave the same.  One fused kernel each way (csrc/fsq.hip): the two 1x1
-    projections are ``Conv2d`` modules for their parameters (names, initialisation, weight-decay group) only -- the kernels read
-    their [d, D] / [D, d] weight memory directly.  ``codebook`` holds the IMPLICIT codebook, frozen: row i = the rounded vector
-    of token i, scaled to [-1, 1]."""
+    statistics to all-reduce; training and evaluation behave the same.  One fused kernel each way (csrc/fsq.hip).  ``codebook`` holds
+    the IMPLICIT codebook, frozen: row i = the rounded vector of token i, scaled to [-1, 1]."""
+    kind = 'fsq'
 
     def __init__(self, num_embeddings: int, embedding_dim: int, levels):
         levels = [int(v) for v in levels]
@@ -231,13 +273,15 @@ class FSQuantizer(BaseVectorQuantizer):
             raise ValueError(f'fsq: every level must be >= 2, got {levels}')
         if math.prod(levels) != num_embeddings:
             raise ValueError(f'fsq: num_embeddings = {num_embeddings} must equal prod(levels) = {math.prod(levels)}')
-        super().__init__(num_embeddings, len(levels))         # the codebook the base class owns is the implicit one: [K, d], frozen
-        self.embedding_dim = embedding_dim
-        self.codebook.requires_grad_(False)
+        super().__init__(num_embeddings, embedding_dim, len(levels))
         self.levels = tuple(levels)
-        self.project_in = Conv2d(embedding_dim, len(levels), 1, bias=True)
-        self.project_out = Conv2d(len(levels), embedding_dim, 1, bias=True)
         self.init_codebook()
+
+    def _assign(self, flat_z: torch.Tensor) -> torch.Tensor:
+        return ops.fsq_assign(flat_z, self.project_in.weight, self.project_in.bias, self.levels)
+
+    def _decode(self, codes: torch.Tensor) -> torch.Tensor:
+        return ops.fsq_decode(codes, self.project_out.weight, self.project_out.bias, self.levels)
 
     def implicit_codebook(self) -> torch.Tensor:
         """[K, d] fp32: row i = (digit_j(i) - L_j // 2) / (L_j // 2), digit_j the j-th mixed-radix digit of i (first level fastest)"""
@@ -248,51 +292,22 @@ class FSQuantizer(BaseVectorQuantizer):
             rem = rem // lv
         return torch.stack(cols, 1)
 
-    @torch.no_grad()
-    def init_codebook(self) -> None:
-        self.codebook.weight.copy_(self.implicit_codebook())
-
-    def _projections(self):
-        return self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias
-
     def forward(self, x: torch.Tensor):
         q, idx, loss, hist = ops.FSQFn.apply(x, *self._projections(), self.levels, self.compute_dtype)
         self.last_hist = hist
         return q, idx, loss
 
-    @torch.no_grad()
-    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
-        z = ops.nhwc(x.to(torch.float32))
-        return ops.fsq_assign(_flat_view(z), self.project_in.weight, self.project_in.bias, self.levels).view(x.shape[0], -1)
 
-    @torch.no_grad()
-    def get_codebook(self) -> torch.Tensor:
-        """the [K, D] decoder-side vectors: every token decoded"""
-        tokens = torch.arange(self.num_embeddings, dtype=torch.int64, device=self.project_out.weight.device)
-        return ops.fsq_decode(tokens, self.project_out.weight, self.project_out.bias, self.levels)
-
-    @torch.no_grad()
-    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
-        """codes (B,N) -> (B,N,D), by arithmetic on the token (no [K, D] table is built)"""
-        return ops.fsq_decode(codes, self.project_out.weight, self.project_out.bias, self.levels)
-
-    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
-        raise RuntimeError('fsq: there is no learned codebook to re-initialise')
-
-    def init_codebook_from_data(self, *args, **kwargs):
-        raise ValueError('fsq: there is no learned codebook to initialise from data')
-
-
-class LFQuantizer(BaseVectorQuantizer):
+class LFQuantizer(_ProjectionQuantizer):
     """Lookup-free quantization (Yu et al. 2023, MAGVIT-v2; Open-MAGVIT2): the D-channel latent is projected to ``bits`` channels, each
     is quantized to its sign, the bit pattern is the token (K = 2^bits, first channel = bit 0) and the sign vector is projected back
     to D channels.  loss = commitment_cost * commit + ent_loss_ratio * (H_sample - diversity_gamma * H_batch): the per-position
     entropy keeps the bits confident, the entropy of the batch-average distribution -- factorised over groups of ``ent_group_bits``
     bits -- keeps the vocabulary evenly used.  No learned codebook, no search, no dead codes, no collective (data parallel, the batch
     average is per rank, as the entropy quantizer's statistics are); training and evaluation behave the same.  One fused kernel each
-    way (csrc/lfq.hip); the two 1x1 projections are ``Conv2d`` modules for their parameters only, as in ``FSQuantizer``.  ``codebook``
-    holds the IMPLICIT codebook, frozen: row i = the +-1 vector of token i.  ``last_parts`` = (commit, H_sample, H_batch) of the last
-    forward, on the device, for logging."""
+    way (csrc/lfq.hip).  ``codebook`` holds the IMPLICIT codebook, frozen: row i = the +-1 vector of token i.  ``last_parts`` =
+    (commit, H_sample, H_batch) of the last forward, on the device, for logging."""
+    kind = 'lfq'
 
     def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float = 0.25, ent_loss_ratio: float = 0.1,
                  ent_temperature: float = 0.01, diversity_gamma: float = 1.0, ent_group_bits: int = 9):
@@ -305,56 +320,29 @@ class LFQuantizer(BaseVectorQuantizer):
             raise ValueError(f'lfq: ent_group_bits must be between 1 and {ops.LFQ_MAX_GROUP_BITS}, got {ent_group_bits}')
         if not float(ent_temperature) > 0.0:
             raise ValueError(f'lfq: ent_temperature must be > 0, got {ent_temperature}')
-        super().__init__(num_embeddings, bits)                # the codebook the base class owns is the implicit one: [K, bits], frozen
-        self.embedding_dim = embedding_dim
-        self.codebook.requires_grad_(False)
+        super().__init__(num_embeddings, embedding_dim, bits)
         self.bits, self.ent_group_bits = bits, ent_group_bits
         self.commitment_cost, self.ent_loss_ratio = float(commitment_cost), float(ent_loss_ratio)
         self.ent_temperature, self.diversity_gamma = float(ent_temperature), float(diversity_gamma)
-        self.project_in = Conv2d(embedding_dim, bits, 1, bias=True)
-        self.project_out = Conv2d(bits, embedding_dim, 1, bias=True)
         self.last_parts = None
         self.init_codebook()
+
+    def _assign(self, flat_z: torch.Tensor) -> torch.Tensor:
+        return ops.lfq_assign(flat_z, self.project_in.weight, self.project_in.bias, self.bits)
+
+    def _decode(self, codes: torch.Tensor) -> torch.Tensor:
+        return ops.lfq_decode(codes, self.project_out.weight, self.project_out.bias, self.bits)
 
     def implicit_codebook(self) -> torch.Tensor:
         """[K, bits] fp32: row i, column j = +1 if bit j of i is set, else -1"""
         tokens = torch.arange(self.num_embeddings, dtype=torch.int64)
         return (((tokens[:, None] >> torch.arange(self.bits)) & 1) * 2 - 1).to(torch.float32)
 
-    @torch.no_grad()
-    def init_codebook(self) -> None:
-        self.codebook.weight.copy_(self.implicit_codebook())
-
-    def _projections(self):
-        return self.project_in.weight, self.project_in.bias, self.project_out.weight, self.project_out.bias
-
     def forward(self, x: torch.Tensor):
         cfg = (self.bits, self.ent_group_bits, self.commitment_cost, self.ent_loss_ratio, self.diversity_gamma, self.ent_temperature)
         q, idx, loss, hist, parts = ops.LFQFn.apply(x, *self._projections(), cfg, self.compute_dtype)
         self.last_hist, self.last_parts = hist, parts
         return q, idx, loss
-
-    @torch.no_grad()
-    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
-        z = ops.nhwc(x.to(torch.float32))
-        return ops.lfq_assign(_flat_view(z), self.project_in.weight, self.project_in.bias, self.bits).view(x.shape[0], -1)
-
-    @torch.no_grad()
-    def get_codebook(self) -> torch.Tensor:
-        """the [K, D] decoder-side vectors: every token decoded"""
-        tokens = torch.arange(self.num_embeddings, dtype=torch.int64, device=self.project_out.weight.device)
-        return ops.lfq_decode(tokens, self.project_out.weight, self.project_out.bias, self.bits)
-
-    @torch.no_grad()
-    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
-        """codes (B,N) -> (B,N,D), by bit arithmetic on the token (no [K, D] table is built)"""
-        return ops.lfq_decode(codes, self.project_out.weight, self.project_out.bias, self.bits)
-
-    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
-        raise RuntimeError('lfq: there is no learned codebook to re-initialise')
-
-    def init_codebook_from_data(self, *args, **kwargs):
-        raise ValueError('lfq: there is no learned codebook to initialise from data')
 
 
 class ResidualVectorQuantizer(BaseVectorQuantizer):

@@ -171,6 +171,23 @@ def _require_gpu(t: torch.Tensor):
         raise RuntimeError('vqk: operators run on the GPU only (HIP kernels, no CPU fallback); got a CPU tensor')
 
 
+def f32c(t: torch.Tensor) -> torch.Tensor:
+    """t detached, as contiguous fp32 (t itself when it already is): what a launcher hands to the C-ABI"""
+    t = t.detach()
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
+
+
+def grow_ws(table: dict, device, nbytes: int) -> torch.Tensor:
+    """the byte workspace of ``table`` for the calling (device, stream, host thread) (``_wkey``), grown when ``nbytes`` exceed it,
+    never shrunk: what an operator family's kernels write between two of its launches"""
+    _stream()
+    key = _wkey(device)
+    ws = table.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = table[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
 _zero_pages = {}
 
 
@@ -2140,8 +2157,7 @@ if TRACE:
 # operator families kept in their own files (this module stays the one import: `ops.VQLookupFn`, `ops.conv_act`, ...)
 # ------------------------------------------------------------------------------------------------------
 from ._ops_vq import *        # noqa: E402,F401,F403  quantizers
-from ._ops_fsq import *       # noqa: E402,F401,F403  finite scalar quantizer
-from ._ops_lfq import *       # noqa: E402,F401,F403  lookup-free quantizer
+from ._ops_proj import *      # noqa: E402,F401,F403  projection quantizers: finite scalar, lookup-free
 from ._ops_rvq import *       # noqa: E402,F401,F403  residual quantizer
 from ._ops_cos import *       # noqa: E402,F401,F403  cosine quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
