@@ -542,7 +542,7 @@ int vqk_ctx_set_scratch(vqk_ctx* ctx, void* ws, int64_t ws_bytes);
 int vqk_ctx_set_tile_queue(vqk_ctx* ctx, void* ws, int64_t ws_bytes);
 int vqk_ctx_set_deterministic(vqk_ctx* ctx, int on, void* ws, int64_t ws_bytes);
 /* Tuning slots: the launch heuristics that tools/ sweep (formerly read-once environment variables).  name = one of
- * vqk_tuning_name(0 .. vqk_tuning_count() - 1): MX, MX_1X1, TW16, STREAM_BLOCKS, MX_MIN_TILES, FPROP_SPLITK, SK_BLOCKS, SK_MINSTEPS, SK_MAXMB, UPS_PHASE, WGRAD_BLOCKS, WGMX, WGRAD_GEN_BLOCKS, WGRAD_NO_PW16, WGRAD_NO_P16K, MX_HALF, MX_HALF_HW, UPFIRDN_TILE, GN_BLOCKS_REDUCE, GN_BLOCKS_APPLY, GN_NT_MB, GN_NO_SMALL, WGMX_COEF_E4, GN_CLUSTER_MAX_HW, COMM_CUS, MX_QUARTER, MX_S2, MX_S2_DGRAD_MIN, UPS_MERGE, TILE_QUEUE.
+ * vqk_tuning_name(0 .. vqk_tuning_count() - 1): MX, MX_1X1, TW16, STREAM_BLOCKS, MX_MIN_TILES, FPROP_SPLITK, SK_BLOCKS, SK_MINSTEPS, SK_MAXMB, UPS_PHASE, WGRAD_BLOCKS, WGMX, WGRAD_GEN_BLOCKS, WGRAD_NO_PW16, WGRAD_NO_P16K, MX_HALF, MX_HALF_HW, UPFIRDN_TILE, GN_BLOCKS_REDUCE, GN_BLOCKS_APPLY, GN_NT_MB, GN_NO_SMALL, WGMX_COEF_E4, GN_CLUSTER_MAX_HW, COMM_CUS, MX_QUARTER, MX_S2, MX_S2_DGRAD_MIN, UPS_MERGE, TILE_QUEUE, WGRAD_GROUP_LOAD_PCT, WGRAD_GROUP_MIN_PPS.
  * A set slot overrides the built-in default at the next launch; vqk_reset_tuning returns every slot to its default.
  * Process-wide (relaxed atomics); VQK_ERR_ARG for an unknown name.  The Python host maps VQK_<NAME> environment variables
  * onto these calls when it loads the library (_native.py), so the A/B scripts keep their interface. */
@@ -575,6 +575,29 @@ int vqk_conv_pack_dgrad(const float* w, void* wt, int dtype, int cout, int cin, 
  * (split-K partials are combined with fp32 atomics). */
 int vqk_conv2d_wgrad(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin,
                      int cout, int ksize, int ups, const void* zeros, void* stream);
+/* GROUPED 3x3 weight gradients: the layers of a backward stage whose maps are too small to fill the chip one at a time (a
+ * 512 -> 512 conv at 16x16 has 64 dW tiles; alone it is split over K and pays an atomic pass per split) in ONE launch per 16
+ * items.  Per item: dw[Cout][3][3][Cin] (fp32) += scale * sum_pix dy[pix][co] * x[pix (+) tap][ci], x [n][h][w][cin], dy
+ * [n][h][w][cout] bf16 nhwc.  Served per item: dtype VQK_BF16, ksize 3, ups 0 (plain stride-1 3x3), h % 8 == 0, w % 16 == 0,
+ * cin % 64 == 0, cout % 64 == 0 (VQK_ERR_SHAPE), x / dy / dw 16-byte aligned (VQK_ERR_ALIGN), no NULL (VQK_ERR_ARG); ONE item
+ * that does not qualify refuses the call and nothing is launched.  Deterministic mode: VQK_ERR_SHAPE (callers launch
+ * vqk_conv2d_wgrad per layer, whose ordered workspace sums stay as they are).
+ * The work table travels in the kernel arguments (no device copy: the call can be captured into a graph); the items are
+ * caller-owned and only read during the call.  Partition (tuning slots WGRAD_GROUP_LOAD_PCT, WGRAD_GROUP_MIN_PPS): a layer's K is
+ * split only when one block per dW tile would run longer than the even share of the launch's work per CU.  An unsplit layer is
+ * added to dw with plain loads and stores -- the same bits every run; a split one with fp32 atomics, like vqk_conv2d_wgrad.
+ * vqk_conv3x3_wgrad_group_plan: the same validation, no launch; splits[i] = the K-splits item i would get, *launches = the
+ * number of kernel launches. */
+typedef struct vqk_wgrad_item {
+    const void* x;
+    const void* dy;
+    float* dw;
+    int dtype, n, h, w, cin, cout, ksize, ups;
+    float scale;
+    int reserved;
+} vqk_wgrad_item;
+int vqk_conv3x3_wgrad_group(const vqk_wgrad_item* items, int n_items, const void* zeros, void* stream);
+int vqk_conv3x3_wgrad_group_plan(const vqk_wgrad_item* items, int n_items, int* splits, int* launches);
 /* The 3x3 weight gradient of the two EDGE convs (one 16-byte chunk of channels on one side: the padded 3-channel image /
  * reconstruction; vqvae/modules/autoencoder.py:114 and :170), bf16: (cin, cout) = (8, 128) or (128, 8), h*w % 128 == 0 and
  * (w % 128 == 0 or 128 % w == 0).

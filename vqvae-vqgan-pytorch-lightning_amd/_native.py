@@ -23,6 +23,13 @@ _lib = None
 P = c_void_p
 I, L, F = c_int, c_int64, c_float
 
+
+class WgradItem(ctypes.Structure):
+    """``vqk_wgrad_item`` (include/vqk.h): one layer of a grouped 3x3 weight-gradient launch"""
+    _fields_ = [('x', c_void_p), ('dy', c_void_p), ('dw', c_void_p), ('dtype', c_int), ('n', c_int), ('h', c_int), ('w', c_int),
+                ('cin', c_int), ('cout', c_int), ('ksize', c_int), ('ups', c_int), ('scale', c_float), ('reserved', c_int)]
+
+
 # name -> argtypes ; every function returns int (status) unless listed in _SPECIAL
 _PROTOS = {
     'vqk_row_sqnorm_f32': [P, L, I, P, P],
@@ -99,6 +106,8 @@ _PROTOS = {
     'vqk_ctx_set_deterministic': [P, I, P, L],
     'vqk_conv_pack_dgrad': [P, P, I, I, I, I, P],
     'vqk_conv2d_wgrad': [I, P, P, P, I, I, I, I, I, I, I, P, P],
+    'vqk_conv3x3_wgrad_group': [P, I, P, P],
+    'vqk_conv3x3_wgrad_group_plan': [P, I, P, P],
     'vqk_conv2d_wgrad_pooled_dy': [I, P, P, P, I, I, I, I, I, F, P, P],
     'vqk_conv2d_wgrad_ups_phase': [I, P, P, P, I, I, I, I, I, F, P, P],
     'vqk_split_pair_f32': [P, P, L, I, P],

@@ -109,4 +109,21 @@ int launch_conv3x3_wgrad_thin_f32(int mode, const float* wide, const float* thin
 int launch_conv3x3_wgrad_mx(const void* x, const void* dy, float* dw, const void* zeros, const ConvGeom& g, int tiles,
                             int splits, int pps, hipStream_t st, float* part = nullptr);
 
+// grouped form of the same kernel (conv_wgmx.hip: conv3x3_wgrad_mx_group_kernel): the work table of one launch, passed BY VALUE
+// in the kernel arguments (16 x 64 + 8 bytes, far below the 4-KiB argument limit).  Layer i owns the blocks
+// [blk0, blk0 + tiles * splits): block blk0 + s * tiles + t = dW tile t over the patches [s * pps, (s + 1) * pps).
+#define VQK_WGRAD_GROUP_MAX 16
+struct WgradGroupLayer {
+    const void* x; const void* dy; float* dw;
+    int n, h, w, cin, cout;
+    float scale;                    // dW += scale * (x^T dy)
+    int blk0, tiles, pps;
+    int own;                        // 1: no split-K -- every tile has ONE block, which adds it with plain loads and stores
+};
+struct WgradGroupTable {
+    int n_layers, pad_;
+    WgradGroupLayer layer[VQK_WGRAD_GROUP_MAX];
+};
+int launch_conv3x3_wgrad_mx_group(const WgradGroupTable& tb, int blocks, const void* zeros, hipStream_t st);
+
 }  // namespace vqkd

@@ -49,46 +49,24 @@ __device__ __forceinline__ bf16x8_t tr_frag2(const char* p) {
     return __builtin_bit_cast(bf16x8_t, v);
 }
 
+// The M-wave / X-wave body of one block: the dW tile (co0, ci0) (true channels; co0m / ci0m = the operands' channels in memory) over
+// the patches [p_begin, p_end) of (x, dy, g).  Shared by the one-layer kernel and the grouped one below: same fragment reads and
+// MFMA order, so a block's partial sums do not depend on which of the two launched it.  Final pass: `mine` != nullptr -- the
+// deterministic mode's workspace slot, plain stores; `own` -- this block is the ONLY one that adds to the tile (no split-K): plain
+// loads and stores, dW += in a fixed order, the same bits every run; otherwise fp32 atomics.
 template <int NT>
-__global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw* __restrict__ x,
-                                                                  const bf16_raw* __restrict__ dy, float* __restrict__ dw,
-                                                                  const char* __restrict__ zeros, ConvGeom g,
-                                                                  int patches_per_split, float* __restrict__ part) {
+__device__ __forceinline__ void wgrad_mx_body(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ dy, float* __restrict__ dw,
+                                              const char* __restrict__ zeros, const ConvGeom& g, int co0, int ci0, int co0m, int ci0m,
+                                              int cin_t, int phase, int p_begin, int p_end, float* __restrict__ mine, bool own,
+                                              char* smem) {
     constexpr int PWD = 16, PIX = 128, HWD = 18, HROWS = 180, X_ROWS = 192;
     constexpr int DY_HALF = PIX * 64, X_HALF = X_ROWS * 64, STAGE = 2 * DY_HALF + 2 * X_HALF;     // 40960
     constexpr int NDY = 4, NX = 6;                               // pieces per X wave and stage: 16 dy + 24 x over 4 waves
     constexpr int NST = VQK_WGMX_NST, LEAD = NST - 1;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // g.fold (split-product mode, conv_x3.hip): x / dy are (hi | lo) pair tensors with pixel pitches g.cin / g.cout = twice the TRUE
-    // channel counts; tile class 0 = dy_hi^T x_hi, 1 = dy_hi^T x_lo, 2 = dy_lo^T x_hi, all three added onto the same dW tile
-    const int cin_t = g.fold ? g.cin >> 1 : g.cin, cout_t = g.fold ? g.cout >> 1 : g.cout;
-    const int tiles_ci = cin_t >> 6;
-    const int vb = xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
-    const int bx0 = vb % (int)gridDim.x, by = vb / (int)gridDim.x;
-    const int tiles_pair = tiles_ci * (cout_t >> 6);
-    const int cls = g.fold ? bx0 / tiles_pair : 0;
-    const int bx = g.fold ? bx0 - cls * tiles_pair : bx0;
-    const int tco = bx / tiles_ci, tci = bx - tco * tiles_ci;
-    const int co0 = tco * 64, ci0 = tci * 64;                    // dW tile (true channels)
-    const int co0m = co0 + (cls == 2 ? cout_t : 0), ci0m = ci0 + (cls == 1 ? cin_t : 0);      // operand channels in memory
     const int pw = g.w >> 4, ph = g.h >> 3;
-    const int total_patches = g.n * ph * pw;
-    // NT = 4: g.dy_pool = 2 + phase (one phase per launch) or 6 (ALL FOUR phases in one launch: phase = by & 3, split = by >> 2 --
-    // a block still owns one phase, i.e. four accumulators, but the launch fills the chip with a quarter of the splits per phase:
-    // per-block prologue and atomic pass are amortised over 4x the patches of the one-phase-per-launch form)
-    // g.dy_pool = 7: as 6 with the operands' ROLES SWAPPED -- the weight gradient of a conv followed by a 2x2 average pool from the
-    // POOLED gradient: dW[ky][kx] = sum_YX dyp[Y>>1][X>>1] x[Y+ky-1][X+kx-1] re-indexed over the phases (a', b') of the FULL-resolution
-    // x: G'[r'][s'] = sum_ij x[2i+a'][2j+b'] dyp[i+r'][j+s'] over the same 2x2 windows.  The phase-gathered operand ("dy" of this
-    // kernel) is x, the windowed low-resolution operand ("x" of this kernel) is the pooled gradient; the tile comes out transposed
-    // (rows = the conv's input channels) and stands for the MIRRORED taps (2 - ky, 2 - kx): the final pass scatters accordingly.
-    const bool merged = NT == 4 && g.dy_pool >= 6, swapped = NT == 4 && g.dy_pool == 7;
-    const int phase = NT == 4 ? (merged ? (by & 3) : g.dy_pool - 2) : 0;
-    const int split = merged ? (by >> 2) : by;
-    const int p_begin = split * patches_per_split;
-    const int p_end = min(total_patches, p_begin + patches_per_split);
-    if (p_begin >= p_end) return;
+    const bool swapped = NT == 4 && g.dy_pool == 7;
     auto patch_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     if (wave < 4) {
@@ -190,10 +168,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw
             }
             return;
         } else {
-        if (part) {
-            // deterministic mode: this block's partial tile goes to the workspace slot (split by, tile bx) with plain stores;
+        if (mine) {
+            // deterministic mode: this block's partial tile goes to its workspace slot with plain stores;
             // wgrad_mx_reduce_kernel adds the splits in index order
-            float* mine = part + ((int64_t)by * gridDim.x + bx) * (64 * 9 * 64);
 #pragma unroll
             for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -201,6 +178,24 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw
                     const int col = wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * kgrp;
                     mine[(col * 9 + t) * 64 + wj * 32 + (lane & 31)] = acc[t][r] * g.acc_scale;
                 }
+            return;
+        }
+        if (own) {
+            // the tile's only block: dW += with plain loads and stores, one tap (16 rows x 128 bytes per half-wave) at a time
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                float old[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = co0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * kgrp;
+                    old[r] = dw[((int64_t)co * 9 + t) * cin_t + ci];
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = co0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * kgrp;
+                    dw[((int64_t)co * 9 + t) * cin_t + ci] = old[r] + acc[t][r] * g.acc_scale;
+                }
+            }
             return;
         }
 #pragma unroll
@@ -306,6 +301,69 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw
     }
 }
 
+template <int NT>
+__global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw* __restrict__ x,
+                                                                  const bf16_raw* __restrict__ dy, float* __restrict__ dw,
+                                                                  const char* __restrict__ zeros, ConvGeom g,
+                                                                  int patches_per_split, float* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // g.fold (split-product mode, conv_x3.hip): x / dy are (hi | lo) pair tensors with pixel pitches g.cin / g.cout = twice the TRUE
+    // channel counts; tile class 0 = dy_hi^T x_hi, 1 = dy_hi^T x_lo, 2 = dy_lo^T x_hi, all three added onto the same dW tile
+    const int cin_t = g.fold ? g.cin >> 1 : g.cin, cout_t = g.fold ? g.cout >> 1 : g.cout;
+    const int tiles_ci = cin_t >> 6;
+    const int vb = xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
+    const int bx0 = vb % (int)gridDim.x, by = vb / (int)gridDim.x;
+    const int tiles_pair = tiles_ci * (cout_t >> 6);
+    const int cls = g.fold ? bx0 / tiles_pair : 0;
+    const int bx = g.fold ? bx0 - cls * tiles_pair : bx0;
+    const int tco = bx / tiles_ci, tci = bx - tco * tiles_ci;
+    const int co0 = tco * 64, ci0 = tci * 64;                    // dW tile (true channels)
+    const int co0m = co0 + (cls == 2 ? cout_t : 0), ci0m = ci0 + (cls == 1 ? cin_t : 0);      // operand channels in memory
+    const int total_patches = g.n * (g.h >> 3) * (g.w >> 4);
+    // NT = 4: g.dy_pool = 2 + phase (one phase per launch) or 6 (ALL FOUR phases in one launch: phase = by & 3, split = by >> 2 --
+    // a block still owns one phase, i.e. four accumulators, but the launch fills the chip with a quarter of the splits per phase:
+    // per-block prologue and atomic pass are amortised over 4x the patches of the one-phase-per-launch form)
+    // g.dy_pool = 7: as 6 with the operands' ROLES SWAPPED -- the weight gradient of a conv followed by a 2x2 average pool from the
+    // POOLED gradient: dW[ky][kx] = sum_YX dyp[Y>>1][X>>1] x[Y+ky-1][X+kx-1] re-indexed over the phases (a', b') of the FULL-resolution
+    // x: G'[r'][s'] = sum_ij x[2i+a'][2j+b'] dyp[i+r'][j+s'] over the same 2x2 windows.  The phase-gathered operand ("dy" of this
+    // kernel) is x, the windowed low-resolution operand ("x" of this kernel) is the pooled gradient; the tile comes out transposed
+    // (rows = the conv's input channels) and stands for the MIRRORED taps (2 - ky, 2 - kx): the final pass scatters accordingly.
+    const bool merged = NT == 4 && g.dy_pool >= 6;
+    const int phase = NT == 4 ? (merged ? (by & 3) : g.dy_pool - 2) : 0;
+    const int split = merged ? (by >> 2) : by;
+    const int p_begin = split * patches_per_split;
+    const int p_end = min(total_patches, p_begin + patches_per_split);
+    if (p_begin >= p_end) return;
+    // deterministic mode: the workspace slot (split by, tile bx)
+    float* mine = (NT == 9 && part) ? part + ((int64_t)by * gridDim.x + bx) * (64 * 9 * 64) : nullptr;
+    wgrad_mx_body<NT>(x, dy, dw, zeros, g, co0, ci0, co0m, ci0m, cin_t, phase, p_begin, p_end, mine, false, smem);
+}
+
+// The grouped form: ONE launch carries the weight gradients of up to VQK_WGRAD_GROUP_MAX layers (plain 3x3, bf16).  The table
+// travels by value in the kernel arguments (no device copy: a captured graph node keeps it), a block finds its layer by its
+// block index (the layers' block ranges are consecutive, longest blocks first), then its dW tile and patch range inside the layer,
+// and runs the shared body.  Blocks are independent of each other: no waits, no tickets.
+__global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_group_kernel(const vqkd::WgradGroupTable tb, const char* __restrict__ zeros) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int b = (int)blockIdx.x;
+    vqkd::WgradGroupLayer L = tb.layer[0];
+#pragma unroll
+    for (int i = 1; i < VQK_WGRAD_GROUP_MAX; ++i)
+        if (i < tb.n_layers && b >= tb.layer[i].blk0) L = tb.layer[i];
+    const int local = b - L.blk0;
+    const int split = local / L.tiles, tile = local - split * L.tiles;       // tiles fastest: neighbours share the patch range
+    const int tiles_ci = L.cin >> 6;
+    const int tco = tile / tiles_ci, tci = tile - tco * tiles_ci;
+    ConvGeom g = {};
+    g.n = L.n; g.h = g.h_in = L.h; g.w = g.w_in = L.w; g.cin = L.cin; g.cout = L.cout; g.acc_scale = L.scale;
+    const int total_patches = L.n * (L.h >> 3) * (L.w >> 4);
+    const int p_begin = split * L.pps;
+    const int p_end = min(total_patches, p_begin + L.pps);
+    if (p_begin >= p_end) return;
+    wgrad_mx_body<9>((const bf16_raw*)L.x, (const bf16_raw*)L.dy, L.dw, zeros, g, tco * 64, tci * 64, tco * 64, tci * 64, L.cin, 0,
+                     p_begin, p_end, nullptr, L.own != 0, smem);
+}
+
 // dw[(co0 + col) * 9 + t][ci0 + cil] += sum over the splits, in split order, of part[split][tile][(col * 9 + t) * 64 + cil]
 __global__ __launch_bounds__(256) void wgrad_mx_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw, int tiles,
                                                               int splits, int cin) {
@@ -347,6 +405,16 @@ int launch_conv3x3_wgrad_mx(const void* x, const void* dy, float* dw, const void
         if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
     }
     return VQK_OK;
+}
+
+int launch_conv3x3_wgrad_mx_group(const WgradGroupTable& tb, int blocks, const void* zeros, hipStream_t st) {
+    if (tb.n_layers < 1 || tb.n_layers > VQK_WGRAD_GROUP_MAX || blocks < 1) return VQK_ERR_ARG;
+    static const hipError_t attr = hipFuncSetAttribute((const void*)conv3x3_wgrad_mx_group_kernel,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, VQK_WGMX_NST * 40960);
+    if (attr != hipSuccess) return VQK_ERR_LAUNCH;
+    hipLaunchKernelGGL(conv3x3_wgrad_mx_group_kernel, dim3((unsigned)blocks), dim3(512), VQK_WGMX_NST * 40960, st, tb,
+                       (const char*)zeros);
+    return hipGetLastError() == hipSuccess ? VQK_OK : VQK_ERR_LAUNCH;
 }
 
 }  // namespace vqkd

@@ -829,6 +829,103 @@ int vqk_conv2d_wgrad(int dtype, const void* x, const void* dy, float* dw, int n,
                          zeros, stream);
 }
 
+// ---------------------------------------------------------------- grouped 3x3 weight gradients (include/vqk.h)
+// Partition of one launch of <= 16 layers.  Unit of work: one 8x16-pixel patch of one 64 x 64 x 9 dW tile (72 MFMAs per M wave,
+// ~1.8 us at the 0.55 of peak the kernel sustains).  W = sum tiles_i * patches_i; one 120-KiB block per CU, so the even share of
+// the 256 CUs is A = W / 256 patches.  A block of layer i runs patches_i / splits_i patches; blocks start longest first, so the
+// launch ends after at most A + (longest block) patches.  Hence the rule: a layer whose whole K fits the share (patches_i <=
+// A * LOAD_PCT / 100) keeps ONE block per tile -- no split, no atomics, plain adds -- and a longer one is split only down to
+// that length, never below MIN_PPS patches (a block pays a three-stage pipeline fill and a 144-value final pass per lane).
+// A lone 512->512 @16^2 layer (64 tiles x 64 patches, A = 16) is split three ways, as vqk_conv2d_wgrad splits it; of the 16
+// layers the headline step flushes together (A = 216) only the four with 256 patches are, in two.
+// Fit (tools/wgrad_group_bench.py, profiles/wgrad_group_bench.txt; the step's 21 layers, 16 + 5, ms per pass): LOAD_PCT 50 0.955,
+// 75 0.900, 100 0.925, 150 0.886, 200 0.912, never split 1.021; MIN_PPS 4 / 16 at 100: 0.925 / 0.927 (no layer of the step gets
+// that short).  Flat within ~5 % from 75 to 200, 150 the best of two sweeps on two boxes; the per-layer launches take 1.29-1.31.
+static int wgrad_group_plan(const vqk_wgrad_item* it, int n, int* splits, int* pps) {
+    const int load_pct = VQK_TUNE("WGRAD_GROUP_LOAD_PCT", 150), min_pps = VQK_TUNE("WGRAD_GROUP_MIN_PPS", 4);
+    VQK_REQUIRE(load_pct >= 1 && min_pps >= 1, VQK_ERR_ARG);
+    int64_t work = 0;
+    for (int i = 0; i < n; ++i) work += (int64_t)(it[i].cout / 64) * (it[i].cin / 64) * ((int64_t)it[i].n * (it[i].h / 8) * (it[i].w / 16));
+    int64_t len = work * load_pct / (256 * 100);                 // patches per block aimed for
+    if (len < min_pps) len = min_pps;
+    for (int i = 0; i < n; ++i) {
+        const int patches = it[i].n * (it[i].h / 8) * (it[i].w / 16);
+        int s = (int)((patches + len - 1) / len);
+        if (s < 1) s = 1;
+        pps[i] = (patches + s - 1) / s;
+        splits[i] = (patches + pps[i] - 1) / pps[i];
+    }
+    return VQK_OK;
+}
+
+static int wgrad_group_check(const vqk_wgrad_item* items, int n_items) {
+    VQK_REQUIRE(items && n_items >= 1, VQK_ERR_ARG);
+    // the ordered-workspace path of deterministic mode belongs to the one-layer launch; so do the test hook and the A/B slots
+    VQK_REQUIRE(!g_det && g_force_variant != 0 && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
+                && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
+    for (int i = 0; i < n_items; ++i) {
+        const vqk_wgrad_item& q = items[i];
+        VQK_REQUIRE(q.x && q.dy && q.dw, VQK_ERR_ARG);
+        VQK_REQUIRE(q.dtype == VQK_BF16 && q.ksize == 3 && q.ups == 0 && q.n >= 1 && q.h >= 8 && q.w >= 16 && (q.h % 8) == 0
+                    && (q.w % 16) == 0 && q.cin >= 64 && q.cout >= 64 && (q.cin % 64) == 0 && (q.cout % 64) == 0, VQK_ERR_SHAPE);
+        VQK_REQUIRE((int64_t)q.n * q.h * q.w < 0x7fffff00 && (int64_t)q.n * q.h * q.w * (q.cin > q.cout ? q.cin : q.cout) < (1ll << 31),
+                    VQK_ERR_SHAPE);                              // 32-bit byte offsets inside a patch, as in the one-layer launch
+        VQK_REQUIRE(vqk_aligned16(q.x) && vqk_aligned16(q.dy) && vqk_aligned16(q.dw), VQK_ERR_ALIGN);
+    }
+    return VQK_OK;
+}
+
+int vqk_conv3x3_wgrad_group_plan(const vqk_wgrad_item* items, int n_items, int* splits, int* launches) {
+    const int rc = wgrad_group_check(items, n_items);
+    if (rc) return rc;
+    VQK_REQUIRE(splits && launches, VQK_ERR_ARG);
+    *launches = (n_items + VQK_WGRAD_GROUP_MAX - 1) / VQK_WGRAD_GROUP_MAX;
+    int pps[VQK_WGRAD_GROUP_MAX];
+    for (int i0 = 0; i0 < n_items; i0 += VQK_WGRAD_GROUP_MAX) {
+        const int n = n_items - i0 < VQK_WGRAD_GROUP_MAX ? n_items - i0 : VQK_WGRAD_GROUP_MAX;
+        const int rp = wgrad_group_plan(items + i0, n, splits + i0, pps);
+        if (rp) return rp;
+    }
+    return VQK_OK;
+}
+
+int vqk_conv3x3_wgrad_group(const vqk_wgrad_item* items, int n_items, const void* zeros, void* stream) {
+    const int rc = wgrad_group_check(items, n_items);            // every item first: nothing is launched when one is refused
+    if (rc) return rc;
+    VQK_REQUIRE(zeros, VQK_ERR_ARG);
+    VQK_REQUIRE(vqk_aligned16(zeros), VQK_ERR_ALIGN);
+    for (int i0 = 0; i0 < n_items; i0 += VQK_WGRAD_GROUP_MAX) {
+        const vqk_wgrad_item* it = items + i0;
+        const int n = n_items - i0 < VQK_WGRAD_GROUP_MAX ? n_items - i0 : VQK_WGRAD_GROUP_MAX;
+        int splits[VQK_WGRAD_GROUP_MAX], pps[VQK_WGRAD_GROUP_MAX], order[VQK_WGRAD_GROUP_MAX];
+        const int rp = wgrad_group_plan(it, n, splits, pps);
+        if (rp) return rp;
+        for (int i = 0; i < n; ++i) {                            // longest blocks first (stable insertion sort)
+            int j = i;
+            for (; j > 0 && pps[order[j - 1]] < pps[i]; --j) order[j] = order[j - 1];
+            order[j] = i;
+        }
+        vqkd::WgradGroupTable tb = {};
+        tb.n_layers = n;
+        int blocks = 0;
+        for (int k = 0; k < n; ++k) {
+            const int i = order[k];
+            vqkd::WgradGroupLayer& L = tb.layer[k];
+            L.x = it[i].x; L.dy = it[i].dy; L.dw = it[i].dw;
+            L.n = it[i].n; L.h = it[i].h; L.w = it[i].w; L.cin = it[i].cin; L.cout = it[i].cout;
+            L.scale = it[i].scale;
+            L.blk0 = blocks; L.tiles = (it[i].cout / 64) * (it[i].cin / 64); L.pps = pps[i];
+            L.own = splits[i] == 1;
+            for (int j = 0; j < n; ++j)                          // two items onto one target (a shared weight): atomics
+                if (j != i && it[j].dw == it[i].dw) L.own = 0;
+            blocks += L.tiles * splits[i];
+        }
+        const int rl = vqkd::launch_conv3x3_wgrad_mx_group(tb, blocks, zeros, vqk_stream(stream));
+        if (rl) return rl;
+    }
+    return VQK_OK;
+}
+
 int vqk_conv2d_wgrad_x3_f32(const float* x, const float* dy, float* dw, int n, int h_in, int w_in, int cin, int cout, int ups,
                             float scale, void* stream) {
     // split-product weight gradient straight from the fp32 tensors (csrc/conv_x3.hip: conv3x3_wgrad_x3_kernel)

@@ -7,6 +7,7 @@ Tensor convention: activations keep the reference's logical NCHW shape but are p
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import threading
 import weakref
@@ -1666,6 +1667,7 @@ class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, ups: bool, act: int, out_dtype, next_gn: int = 0):
         _require_gpu(x)
+        _forget_stale_wgrads(x.device)
         x = nhwc(x)
         dt = x.dtype
         out_dtype = out_dtype or dt
@@ -1715,6 +1717,8 @@ class Conv2dFn(torch.autograd.Function):
         x, weight, y = ctx.saved_tensors
         k, ups, act, o, i, cin, cout_pad, has_bias, has_res, dt = ctx.cfg
         dy = nhwc(dy)
+        if dy.shape[2] * dy.shape[3] > WGRAD_GROUP_MAX_HW and _WGRAD_PENDING and wgrads_pending(x.device):
+            flush_wgrads(x.device)                               # (as in ResBlockFn.backward)
         if act == 1:
             d2 = torch.empty_like(dy, memory_format=_CL)
             _native.check(_native.lib().vqk_tanh_backward(dcode(dy.dtype), dy.data_ptr(), y.data_ptr(), d2.data_ptr(),
@@ -1747,7 +1751,10 @@ class Conv2dFn(torch.autograd.Function):
                 # the TRUE gradient to the arena -- no zero-filled padded temporary, no slice, no AccumulateGrad pass
                 tgt = direct_grad(ctx.weight_ref)
                 thin = (i if cin != i else o) if tgt is not None else 8
-            dw = raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3)
+            if thin == 8 and wgrad_group_deferrable(x, dyc, tgt, ctx.x3, k, ups):
+                defer_wgrad(x, dyc, tgt)                         # a small map: the stage's grouped launch adds it to the arena
+            else:
+                dw = raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3)
             if tgt is not None:
                 dw = None                                        # already accumulated in the flat arena
             elif padded:
@@ -1840,6 +1847,106 @@ def _wgrad_cap(hw: int) -> int:
     return OVERLAP_WGRAD_BLOCKS_HI if hw >= 65536 else OVERLAP_WGRAD_BLOCKS_MID if hw >= 16384 else OVERLAP_WGRAD_BLOCKS
 
 
+# ---------------------------------------------------------------- deferred weight gradients of the small maps
+# A 3x3 weight gradient on a map of <= 32x32 cannot fill the chip alone (512 -> 512 @16^2: 64 dW tiles): launched per layer it is
+# split over K, pays an fp32-atomic pass per split and a fork + join on the side stream, and none of that is hidden
+# (profiles/round6_small_wgrad_ab.txt).  Only the optimizer reads these gradients, so the backward nodes of the small-map middle
+# APPEND (x, dy, target) here and one grouped launch per 16 layers (vqk_conv3x3_wgrad_group) computes them: hundreds of tiles,
+# little or no split-K.  The list is per DEVICE, not per host thread: the nodes run on the autograd engine's device thread, the
+# end-of-backward callback under the caller's.
+WGRAD_GROUP_MAX_HW = int(_native.switch('VQK_WGRAD_GROUP_MAX_HW', '1024'))     # pixels per image up to which a layer is deferred; 0: off
+_WGRAD_GROUP_ITEMS = 16                                                          # layers per launch (the table in the kernel arguments)
+_WGRAD_PENDING: dict = {}       # device index -> {'items': [(x, dy, target)], 'stream': producer stream, 'task': graph task with a flush queued}
+
+
+def wgrads_pending(device=None) -> int:
+    """deferred weight gradients not yet launched on ``device`` (default: the current one)"""
+    st = _WGRAD_PENDING.get(torch.cuda.current_device() if device is None else torch.device(device).index)
+    return len(st['items']) if st else 0
+
+
+def drop_pending_wgrads(device=None) -> None:
+    """forget deferred items without launching them: what a backward that raised left behind (called at the next forward)"""
+    st = _WGRAD_PENDING.get(torch.cuda.current_device() if device is None else torch.device(device).index)
+    if st:
+        st['items'].clear()
+        st['task'] = -1
+
+
+def _forget_stale_wgrads(device) -> None:
+    """first thing in a forward: outside a backward call the list is empty unless a backward RAISED between a deferral and its
+    end-of-call flush -- that step is gone, its items must not reach the next one's arena"""
+    if _WGRAD_PENDING and torch._C._current_graph_task_id() == -1 and wgrads_pending(device):
+        drop_pending_wgrads(device)
+
+
+def wgrad_group_deferrable(x, dy, target, x3: bool = False, ksize: int = 3, ups: bool = False) -> bool:
+    """may this weight gradient wait for the stage's grouped launch?  bf16, plain 3x3, an arena target, whole 8x16 patches and
+    64-channel tiles, a map of at most WGRAD_GROUP_MAX_HW pixels, not in deterministic / split-product mode"""
+    n, cin, h, w = x.shape
+    return (WGRAD_GROUP_MAX_HW > 0 and target is not None and not x3 and not DETERMINISTIC and _WGMX_ON and ksize == 3 and not ups
+            and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and h * w <= WGRAD_GROUP_MAX_HW and h % 8 == 0
+            and w % 16 == 0 and cin % 64 == 0 and dy.shape[1] % 64 == 0 and tuple(dy.shape[2:]) == (h, w))
+
+
+def defer_wgrad(x, dy, target) -> None:
+    """queue target += wgrad(x, dy) for the next grouped launch; the list keeps the three tensors alive until then"""
+    dev = x.device.index
+    st = _WGRAD_PENDING.get(dev)
+    if st is None:
+        st = _WGRAD_PENDING[dev] = {'items': [], 'stream': None, 'task': -1}
+    st['items'].append((x, dy, target))
+    st['stream'] = torch.cuda.current_stream(x.device)
+    task = torch._C._current_graph_task_id()
+    if task != -1 and st['task'] != task:
+        # once per backward call: the engine runs this after the last node, before .backward() returns
+        st['task'] = task
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: flush_wgrads(dev))
+    if len(st['items']) >= _WGRAD_GROUP_ITEMS:
+        flush_wgrads(dev)
+
+
+def raw_conv_wgrad_group(items, plan_only: bool = False):
+    """[(x, dy, target)] -> target += wgrad(x, dy) for every item, one launch per 16 (vqk_conv3x3_wgrad_group) on the current
+    stream; returns (status, splits per item, launches) -- status ERR_SHAPE: an item is not served, nothing was launched.
+    ``plan_only``: the partition the launcher would use, without launching."""
+    arr = (_native.WgradItem * len(items))()
+    flops = 0.0
+    for q, (x, dy, tgt) in zip(arr, items):
+        n, cin, h, w = x.shape
+        q.x, q.dy, q.dw = x.data_ptr(), dy.data_ptr(), tgt.data_ptr()
+        q.dtype, q.n, q.h, q.w, q.cin, q.cout, q.ksize, q.ups, q.scale = dcode(x.dtype), n, h, w, cin, dy.shape[1], 3, 0, 1.0
+        flops += 2.0 * n * h * w * cin * dy.shape[1] * 9
+    lib = _native.lib()
+    _stream()                                                    # (the thread's library context, deterministic mode included, is current from here on)
+    splits, launches = (_native.c_int * len(items))(), _native.c_int(0)
+    st = lib.vqk_conv3x3_wgrad_group_plan(ctypes.addressof(arr), len(items), ctypes.addressof(splits), ctypes.addressof(launches))
+    if st == 0 and not plan_only:
+        dev = items[0][0].device
+        st = _timed('conv3x3_wgrad_mx_group_kernel<bf16>', flops,
+                    lambda: lib.vqk_conv3x3_wgrad_group(ctypes.addressof(arr), len(items), zero_page(dev).data_ptr(), _stream()),
+                    launches=launches.value)
+    return st, list(splits), launches.value
+
+
+def flush_wgrads(device=None) -> int:
+    """launch the deferred weight gradients of ``device`` on the current stream (behind the stream they were produced on) and
+    clear the list; returns the number of layers launched"""
+    dev = torch.cuda.current_device() if device is None else torch.device(device).index
+    st = _WGRAD_PENDING.get(dev)
+    if not st or not st['items']:
+        return 0
+    items = list(st['items'])
+    st['items'].clear()
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream()
+        if st['stream'] is not None and st['stream'] != cur:
+            cur.wait_stream(st['stream'])
+        status, _, _ = raw_conv_wgrad_group(items)
+        _native.check(status, 'conv3x3_wgrad_group')
+    return len(items)
+
+
 class ResBlockFn(torch.autograd.Function):
     """One pre-activation residual block (autoencoder.py:63-77) as a single autograd node:
     GN+SiLU -> 3x3 -> GN+SiLU -> 3x3 (+ skip, optionally through a 1x1), with a hand-scheduled backward whose last
@@ -1849,6 +1956,7 @@ class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, c1w, n2w, n2b, c2w, scw, groups: int, eps: float, pool: bool = False, next_gn: int = 0):
         _require_gpu(x)
+        _forget_stale_wgrads(x.device)
         ctx.db_param = _claim_bias_colsum(x)                     # x = output of a conv with a bias: its db rides in our backward
         x = nhwc(x)
         dt = x.dtype
@@ -1910,6 +2018,8 @@ class ResBlockFn(torch.autograd.Function):
         dt = x.dtype
         dout = nhwc(dout)
         n, _, h, w = x.shape
+        if h * w > WGRAD_GROUP_MAX_HW and _WGRAD_PENDING and wgrads_pending(x.device):
+            flush_wgrads(x.device)                               # the backward has left the small maps: their grouped launch goes first
         t1, t2 = direct_grad(c1w), direct_grad(c2w)
         tw1, tb1, tw2, tb2 = direct_grad(n1w), direct_grad(n1b), direct_grad(n2w), direct_grad(n2b)
         if (pool and POOLED_BWD and scw is None and dt == torch.bfloat16 and t1 is not None and t2 is not None
@@ -1990,16 +2100,26 @@ class ResBlockFn(torch.autograd.Function):
             lib.vqk_conv_set_block_caps(OVERLAP_STREAM_BLOCKS, _wgrad_cap(h * w))
             try:
                 d_a2 = d_a2_pre if d_a2_pre is not None else conv_bwd(a2, dout, c2w, 3, cout, cout, need_dw=False)[0]
-                _on_side(main, side, lambda: wgrad_c2(t2))           # behind the data gradient: it overlaps the GroupNorm pass only
+                # small maps: both weight gradients wait for the stage's grouped launch (defer_wgrad) instead of forking
+                group = dout_p is None and wgrad_group_deferrable(a2, dout, t2, x3) and wgrad_group_deferrable(a1, dout, t1, x3)
+                if group:
+                    defer_wgrad(a2, dout, t2)
+                else:
+                    _on_side(main, side, lambda: wgrad_c2(t2))       # behind the data gradient: it overlaps the GroupNorm pass only
                 d_r1, dn2w, dn2b = gn_bwd(r1, st2, w2, b2, d_a2, n2w, n2b)
-                main.wait_stream(side)                   # dgrad1 alone on the chip
+                if not group:                            # (nothing forked: no join, no cross-queue edge)
+                    main.wait_stream(side)               # dgrad1 alone on the chip
                 d_a1, _ = conv_bwd(a1, d_r1, c1w, 3, cin, cout, need_dw=False)
-                _on_side(main, side, lambda: raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3))
+                if group:
+                    defer_wgrad(a1, d_r1, t1)
+                else:
+                    _on_side(main, side, lambda: raw_conv_wgrad(a1, d_r1, 3, False, out=t1, x3=x3))
                 dskip, dwsc = dout, None
                 if scw is not None:                      # the 1x1 shortcut stays on the main stream (its weight gradient forked as well: measured +-0)
                     dskip, dwsc = conv_bwd(x, dout, scw, 1, cin, cout)
                 dx, dn1w, dn1b = gn_bwd(x, st1, w1, b1, d_a1, n1w, n1b, add=dskip, colsum_of=ctx.db_param)
-                main.wait_stream(side)
+                if not group:
+                    main.wait_stream(side)
             finally:
                 lib.vqk_conv_set_block_caps(0, 0)
             return dx, dn1w, dn1b, None, dn2w, dn2b, None, dwsc, None, None, None, None

@@ -210,6 +210,12 @@ class MiniTrainer:
         return first, second, third
 
     @staticmethod
+    def _stage_done():
+        """after a stage of the split backward: its deferred small-map weight gradients (ops.defer_wgrad) were launched inside the
+        stage -- inside its capture, in front of the all-reduce of its arena range -- by the backward's own end-of-call flush"""
+        assert ops.wgrads_pending() == 0, 'vqk: a backward stage left deferred weight gradients pending'
+
+    @staticmethod
     def _ranges(opt, n_stages: int):
         """arena ranges whose gradients are complete after each stage of the backward"""
         total = opt.flat_g.numel()
@@ -227,6 +233,7 @@ class MiniTrainer:
         works = []
         for k, (stage, (lo, hi)) in enumerate(zip(stages, self._ranges(opt, len(stages)))):
             stage()
+            self._stage_done()
             if k == len(stages) - 1:
                 self._finish_deferred(model, opt)
             if hi > lo:
@@ -320,18 +327,22 @@ class MiniTrainer:
                     self._static_loss = model.training_step(self._static_in, 0)
                     stages = self._backward_halves(model)
                     stages[0]()
+                    self._stage_done()
                 self._graph2 = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self._graph2, pool=self._graph.pool(), stream=side, capture_error_mode='thread_local'):
                     stages[1]()
+                    self._stage_done()
                 if len(stages) == 3:                      # the encoder's high-resolution head: the deep levels' range is reduced under it
                     self._graph3 = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self._graph3, pool=self._graph.pool(), stream=side, capture_error_mode='thread_local'):
                         stages[2]()
+                        self._stage_done()
             else:
                 with torch.cuda.graph(self._graph, stream=side, capture_error_mode='thread_local'):
                     opt.zero_grad()
                     self._static_loss = model.training_step(self._static_in, 0)
                     self._static_loss.backward()
+                    self._stage_done()
         finally:
             model.defer_usage_accumulation = False
             model.split_backward = False
