@@ -954,6 +954,50 @@ int vqk_scalar_accum(const void* const* src, const int* dtype, const double* wei
 int64_t vqk_arena_stats_ws_bytes(int64_t numel, int ngroups);
 int vqk_arena_stats(const float* g, int64_t numel, const int64_t* seg_end, const int32_t* seg_group, int nseg, int ngroups,
                     float scale, void* ws, int64_t ws_bytes, double* out, double* acc, void* stream);
+/* ---------------------------------------------------------------- PatchGAN discriminator ---------
+ * csrc/patchgan.hip: the layers of the n-layer PatchGAN (Isola et al. 2017): 4x4 convs with zero padding 1 and stride 1 or 2, and
+ * BatchNorm (+ LeakyReLU 0.2).  Activations are NHWC `dtype` tensors whose channel count is a whole 16-byte chunk (4 fp32 / 8 bf16):
+ * x[n][h][w][cin], y / dy[n][ho][wo][co_ld] with ho = (h + 2 - 4) / stride + 1 (floor) and co_ld = cout rounded up to a chunk; the
+ * channels cout .. co_ld - 1 of y are written as zeros.  The weight is the fp32 master w[cout][4][4][cin_w], cin_w <= cin (the
+ * 3-channel image arrives zero-padded to cin = one chunk), read in place: VQK_F32 multiplies exactly (fp32 MFMA), VQK_BF16 rounds
+ * the weights to nearest even as they are staged and multiplies bf16 with fp32 accumulation.  Served: stride in {1, 2}, h, w >= 2,
+ * cin, cout <= 4096, n h w < 2^30 (VQK_ERR_SHAPE otherwise, nothing launched); activations and workspaces 16-byte aligned
+ * (VQK_ERR_ALIGN).  No call allocates or synchronises; no kernel uses float atomics: every output has the same bits on every run.
+ * fprop: y = act(conv(x, w) + bias), bias[cout] fp32 or NULL, lrelu != 0: LeakyReLU(0.2).
+ * dgrad: dx[n][h][w][cin] = conv^T(dy, w): stride 1 as the flipped 4x4 conv, stride 2 as four input-parity phases of 2x2 taps each.
+ *   EVERY element of dx is written (channels cin_w .. cin - 1 and the rows / columns no output pixel reads get zeros).
+ * wgrad: dw[co][kh][kw][ci] (+)= scale * sum_p dy[p][co] x[p s + k - 1][ci] (accumulate != 0: +=).  The pixels are split into
+ *   vqk_conv4x4_wgrad_plan(...) partials (a function of the shape only) kept in ws (>= vqk_conv4x4_wgrad_ws_bytes(...) bytes:
+ *   VQK_ERR_WORKSPACE); a second launch adds them in split order into dw.  Both queries return VQK_ERR_SHAPE for an unserved shape. */
+int vqk_conv4x4_fprop(int dtype, const void* x, const float* w, const float* bias, void* y, int n, int h, int wd, int cin, int cin_w,
+                      int cout, int co_ld, int stride, int lrelu, void* stream);
+int vqk_conv4x4_dgrad(int dtype, const void* dy, const float* w, void* dx, int n, int h, int wd, int cin, int cin_w, int cout, int co_ld,
+                      int stride, void* stream);
+int vqk_conv4x4_wgrad_plan(int n, int h, int wd, int cin, int cin_w, int cout, int stride);
+int64_t vqk_conv4x4_wgrad_ws_bytes(int n, int h, int wd, int cin, int cin_w, int cout, int stride);
+int vqk_conv4x4_wgrad(int dtype, const void* x, const void* dy, float* dw, int n, int h, int wd, int cin, int cin_w, int cout, int co_ld,
+                      int stride, float scale, int accumulate, void* ws, int64_t ws_bytes, void* stream);
+/* bias gradient: db[k] (+)= scale * sum_rows dy[row][k], k < cout, dy[rows][co_ld]; per-block fp64 partials in ws (>=
+ * vqk_bn_ws_bytes(rows, co_ld) bytes) added in block order by a second launch. */
+int vqk_conv4x4_bgrad(int dtype, const void* dy, float* db, int64_t rows, int co_ld, int cout, float scale, int accumulate, void* ws,
+                      int64_t ws_bytes, void* stream);
+/* BatchNorm over x[rows][c] (rows = N H W of an NHWC tensor, c a whole chunk, c / chunk <= 256), gamma / beta / statistics fp32.
+ * forward, training != 0: per-channel mean and biased variance from fp64 sums (per-block partials in ws, added in block order by a
+ * one-pass finish: no atomics), mean[c] and rstd[c] = 1 / sqrt(var + eps) saved; the same launch sequence updates running_mean /
+ * running_var (optional) with `momentum` and the UNBIASED variance, and adds 1 to *num_batches_tracked (optional, device int64), so a
+ * captured graph carries the update.  rows == 1 is VQK_ERR_SHAPE (no variance).  training == 0: running_mean / running_var are used,
+ * nothing is saved or updated, ws is not read.  y = act(gamma xhat + beta), lrelu != 0: LeakyReLU(0.2).
+ * backward (of the training-mode forward): g = dy through the LeakyReLU mask (recomputed from x: the pre-activation's sign);
+ * sum g and sum g xhat per channel in the same ordered two-stage form; dx = gamma rstd (g - mean(g) - xhat mean(g xhat));
+ * dgamma / dbeta (each optional: NULL = not wanted) are written, or added to when accumulate != 0.
+ * ws: >= vqk_bn_ws_bytes(rows, c) bytes (VQK_ERR_SHAPE as a negative size for an unserved shape), serves forward and backward. */
+int64_t vqk_bn_ws_bytes(int64_t rows, int c);
+int vqk_bn_forward(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                   float* running_mean, float* running_var, int64_t* num_batches_tracked, int64_t rows, int c, float eps, float momentum,
+                   int training, int lrelu, void* ws, int64_t ws_bytes, void* stream);
+int vqk_bn_backward(int dtype, const void* x, const void* dy, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                    void* dx, float* dgamma, float* dbeta, int accumulate, int64_t rows, int c, int lrelu, void* ws, int64_t ws_bytes,
+                    void* stream);
 
 #ifdef __cplusplus
 }

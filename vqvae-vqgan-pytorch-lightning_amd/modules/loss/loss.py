@@ -10,6 +10,7 @@ from torch import nn
 
 from ... import ops
 from .discriminator import Discriminator
+from .patchgan import NLayerDiscriminator
 from .lpips import LPIPS
 from ..autoencoder import _to_internal
 
@@ -38,16 +39,54 @@ def discriminator_loss(logits_real: torch.Tensor, logits_fake: torch.Tensor, los
     return ops.GanLossFn.apply(logits_real, logits_fake, _MODE[loss_type], 1)
 
 
+_DISC_KEYS = {'stylegan2': ('type',), 'patchgan': ('type', 'ndf', 'n_layers')}
+
+
+def build_discriminator(image_size: int, adversarial_conf: dict) -> nn.Module:
+    """``adversarial_params.discriminator`` (optional): ``{type: stylegan2}`` -- the default, also when the key is absent -- or
+    ``{type: patchgan, ndf: 64, n_layers: 3}``, the n-layer PatchGAN of the usual VQ-GAN recipes (modules/loss/patchgan.py).  Unknown
+    types or keys raise ValueError; the PatchGAN has no double backward, so ``r1_reg_weight`` must be null with it."""
+    conf = adversarial_conf.get('discriminator')
+    if conf is None:
+        return Discriminator(image_size)
+    if not isinstance(conf, dict):
+        raise ValueError(f'adversarial_params.discriminator must be a mapping with a `type`, got {conf!r}')
+    kind = conf.get('type', 'stylegan2')
+    if kind not in _DISC_KEYS:
+        raise ValueError(f'unknown discriminator type {kind!r}: one of {sorted(_DISC_KEYS)}')
+    unknown = sorted(set(conf) - set(_DISC_KEYS[kind]))
+    if unknown:
+        raise ValueError(f'unknown key(s) {unknown} for discriminator type {kind!r}: it takes {list(_DISC_KEYS[kind])}')
+    if kind == 'stylegan2':
+        return Discriminator(image_size)
+    if adversarial_conf.get('r1_reg_weight') is not None:
+        raise ValueError('discriminator type patchgan: r1_reg_weight must be null (R1 needs a double backward, which is not built '
+                         'for the PatchGAN kernels)')
+    ndf, n_layers = conf.get('ndf', 64), conf.get('n_layers', 3)
+    if not (isinstance(ndf, int) and isinstance(n_layers, int) and ndf >= 1 and n_layers >= 1):
+        raise ValueError(f'discriminator type patchgan: ndf and n_layers must be positive integers, got {ndf!r}, {n_layers!r}')
+    if NLayerDiscriminator.logit_size(int(image_size), n_layers) < 1:
+        raise ValueError(f'discriminator type patchgan: a {image_size}x{image_size} image leaves no patch logit after {n_layers} layers')
+    return NLayerDiscriminator(3, ndf, n_layers)
+
+
 class VQLPIPSWithDiscriminator(nn.Module):
     shared_fake_logits = None                # (class defaults: a criterion assembled without __init__ has them too)
     _shared_for = None
     used_aux_streams = ()
 
+    @property
+    def couples_batch(self) -> bool:
+        """the discriminator normalises over the batch (PatchGAN: BatchNorm): every pass is one of the reference's three -- D(fake)
+        for the generator, then D(real) and D(fake) for the discriminator, each updating the running statistics -- so real and fake
+        are never concatenated into one batch, and the generator half's pass is not shared with the discriminator half"""
+        return isinstance(getattr(self, 'discriminator', None), NLayerDiscriminator)
+
     def __init__(self, image_size: int, l1_weight: float, l2_weight: float, perc_weight: float, adversarial_conf: dict):
         super().__init__()
         self.l1_weight, self.l2_weight, self.perceptual_weight = l1_weight, l2_weight, perc_weight
         self.perceptual_loss = LPIPS(net_type='vgg')
-        self.discriminator = Discriminator(image_size)
+        self.discriminator = build_discriminator(image_size, adversarial_conf)
         self.adversarial_start_epoch = adversarial_conf['start_epoch']
         self.adversarial_loss_type = adversarial_conf['loss_type']
         self.generator_weight = adversarial_conf['g_weight']
@@ -104,7 +143,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
             main.wait_stream(side)
         nll_loss = l1_loss * self.l1_weight + l2_loss * self.l2_weight + p_loss * self.perceptual_weight
         if adversarial:
-            self._share(logits_fake if (SHARE_FAKE_PASS and self.training) else None, reconstructions)
+            self._share(logits_fake if (SHARE_FAKE_PASS and self.training and not self.couples_batch) else None, reconstructions)
             g_loss = generator_loss(logits_fake, loss_type=self.adversarial_loss_type)
             if self.training and self.use_adaptive_g_weight:
                 g_weight = self.calculate_adaptive_weight(p_loss, g_loss, last_layer=last_layer)   # p_loss, as the reference
@@ -161,7 +200,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
                     d_loss = discriminator_loss(logits_real, logits_fake, loss_type=self.adversarial_loss_type)
                     return d_loss + r1_term, d_loss, r1_term
                 logits_real = self.discriminator(images, double_backward=compute_r1)
-            elif BATCHED_DISC and not compute_r1 and images.shape[0] == reconstructions.shape[0] and images.shape[2:] == reconstructions.shape[2:]:
+            elif BATCHED_DISC and not self.couples_batch and not compute_r1 and images.shape[0] == reconstructions.shape[0] and images.shape[2:] == reconstructions.shape[2:]:
                 # real | fake through the discriminator as ONE batch (same logits: only the minibatch-stddev layer couples
                 # samples and it groups inside each half): half the launches, no per-parameter gradient accumulation
                 dt = self.discriminator.compute_dtype

@@ -2283,3 +2283,4 @@ from ._ops_cos import *       # noqa: E402,F401,F403  cosine quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
 from ._ops_attn import *      # noqa: E402,F401,F403  self-attention core
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins
+from ._ops_patchgan import *  # noqa: E402,F401,F403  PatchGAN discriminator: 4x4 convs, BatchNorm
