@@ -27,6 +27,7 @@ pytestmark = pytest.mark.gpu
 
 PKG = 'vqvae-vqgan-pytorch-lightning_amd'
 ops = importlib.import_module(PKG + '.ops')
+native = importlib.import_module(PKG + '._native')
 model_mod = importlib.import_module(PKG + '.model')
 trainer_mod = importlib.import_module(PKG + '.trainer')
 vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
@@ -185,6 +186,40 @@ def test_loss_and_gradients_against_float64(case, dq_name):
             close(f'{tag} loss', g['loss'].item(), loss.item(), *TOL['loss'], scale=bound_scale(kind, 'loss'))
             close(f'{tag} dz', got_dz[kz], dz[kz], *TOL['dz'], scale=bound_scale(kind, 'dz'))
             close(f'{tag} de', got_de[ke], de[ke], *TOL['de'], scale=bound_scale(kind, 'de'))
+
+
+def test_backward_takes_an_out_of_range_token_as_a_zero_code():
+    """vqk_cos_backward_f32 on tokens the forward never writes (outside [0, K)): q = 0 for that row and no code row receives its term
+    -- the float64 closed forms on a codebook extended by a zero row that stands in for such a token.  Default (LDS chains + atomics)
+    and deterministic mode (per-row terms + ordered sums); a ragged last block; the tolerances of part 3."""
+    case = (67, 64, 16, 'scale1')
+    n, k, d, kind = case
+    z, e = C.make_case(*case)
+    zd, ed = dev_case(case)
+    idx = fused(case)['idx'].clone()
+    for row, bad in zip((0, 33, 40, n - 1), (-1, k, 2 ** 40 + 3, -2 ** 62)):
+        idx[row] = bad
+    ok = (idx >= 0) & (idx < k)
+    assert int((~ok).sum()) == 4
+    dq = torch.randn(n, d, generator=torch.Generator().manual_seed(11))
+    _, _, dz_ref, de_ref = C.gradients(z, torch.cat([e, torch.zeros(1, d)]), torch.where(ok, idx, k).cpu(), dq, BETA)
+    lib, s = native.lib(), torch.cuda.current_stream().cuda_stream
+    dqd, gs = dq.to(DEV), torch.ones((), device=DEV)
+    cz, ce = 2.0 * BETA / (n * d), 2.0 / (n * d)
+    ws = ops.cos_prepared(ed)
+    ws2 = torch.empty(lib.vqk_cos_backward_ws_bytes(n, d), dtype=torch.uint8, device=DEV)
+    for deterministic in (False, True):
+        dz, de = torch.empty(n, d, device=DEV), torch.zeros(k, d, device=DEV)
+        ops.set_deterministic(deterministic)
+        try:
+            native.check(lib.vqk_cos_backward_f32(zd.data_ptr(), ws.data_ptr(), idx.data_ptr(), dqd.data_ptr(), ops.F32, n, k, d, cz, ce,
+                                                  gs.data_ptr(), dz.data_ptr(), de.data_ptr(), ws2.data_ptr(), ws2.numel(), s),
+                         'cos_backward')
+            torch.cuda.synchronize()
+        finally:
+            ops.set_deterministic(False)
+        close(f'bad token det {int(deterministic)} dz', dz.cpu(), dz_ref, *TOL['dz'], scale=bound_scale(kind, 'dz'))
+        close(f'bad token det {int(deterministic)} de', de.cpu(), de_ref[:k], *TOL['de'], scale=bound_scale(kind, 'de'))
 
 
 # ---------------------------------------------------------------------------------------------- 4. deterministic mode

@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 PKG = 'vqvae-vqgan-pytorch-lightning_amd'
 ops = importlib.import_module(PKG + '.ops')
+native = importlib.import_module(PKG + '._native')
 model_mod = importlib.import_module(PKG + '.model')
 trainer_mod = importlib.import_module(PKG + '.trainer')
 vqm = importlib.import_module(PKG + '.modules.vector_quantizers')
@@ -187,6 +188,39 @@ def test_decode_has_the_forwards_bits(case):
         codes = quant.vec_to_codes(z)
         assert tuple(codes.shape) == (1, n, depth) and torch.equal(codes[0], f['idx'])
         assert torch.equal(quant.codes_to_vec(codes)[0], f['q32'])
+
+
+def test_backward_takes_an_out_of_range_token_as_a_zero_code():
+    """vqk_rvq_backward_f32 on tokens the forward never writes (outside [0, K)): that stage subtracts nothing and its residual adds to
+    no code row -- the float64 closed forms on a codebook extended by a zero row that stands in for such a token.  Default (LDS
+    chains + atomics) and deterministic mode (residual stack + ordered sums); a ragged last block; the tolerances of part 3."""
+    case = (67, 64, 4, 'scale1')
+    n, k, depth, _ = case
+    z, e = R.make_case(*case)
+    zd, ed = dev_case(case)
+    idx = fused(case)['idx'].clone()
+    for (row, stage), bad in zip(((0, 0), (33, 1), (40, depth - 1), (n - 1, 2)), (-1, k, 2 ** 40 + 3, -2 ** 62)):
+        idx[row, stage] = bad
+    ok = (idx >= 0) & (idx < k)
+    assert int((~ok).sum()) == 4
+    dq = torch.randn(n, R.D, generator=torch.Generator().manual_seed(11))
+    _, _, dz_ref, de_ref = R.gradients(z, torch.cat([e, torch.zeros(1, R.D)]), torch.where(ok, idx, k).cpu(), dq, BETA)
+    lib, s = native.lib(), torch.cuda.current_stream().cuda_stream
+    dqd, gs = dq.to(DEV), torch.ones((), device=DEV)
+    cz, ce = 2.0 * BETA / (n * R.D), 2.0 / (n * R.D)
+    ws = torch.empty(lib.vqk_rvq_backward_ws_bytes(n, R.D, depth), dtype=torch.uint8, device=DEV)
+    for deterministic in (False, True):
+        dz, de = torch.empty(n, R.D, device=DEV), torch.zeros(k, R.D, device=DEV)
+        ops.set_deterministic(deterministic)
+        try:
+            native.check(lib.vqk_rvq_backward_f32(zd.data_ptr(), ed.data_ptr(), idx.data_ptr(), dqd.data_ptr(), ops.F32, n, k, R.D, depth,
+                                                  cz, ce, gs.data_ptr(), dz.data_ptr(), de.data_ptr(), ws.data_ptr(), ws.numel(), s),
+                         'rvq_backward')
+            torch.cuda.synchronize()
+        finally:
+            ops.set_deterministic(False)
+        close(f'bad token det {int(deterministic)} dz', dz.cpu(), dz_ref, rtol=1e-5, atol=1e-7)
+        close(f'bad token det {int(deterministic)} de', de.cpu(), de_ref[:k], rtol=1e-4, atol=1e-7)
 
 
 # ---------------------------------------------------------------------------------------------- 6. deterministic mode

@@ -7,13 +7,11 @@ Definition (include/vqk.h, "cosine quantizer"): zn = nrm(z), en = nrm(e) (l2 nor
 quantizer's argmin on (zn, en); q = en[idx]; loss = (1 + beta) / (N D) sum |q - zn|^2; the straight-through estimator is taken at zn."""
 from __future__ import annotations
 
-import weakref
-
 import torch
 
 from . import _native
 from . import ops as core
-from ._ops_vq import _PREP_TABLES, _VQPrep, vq_assign
+from ._ops_vq import _PREP_TABLES, hist_sse, lookup_backward_frame, nhwc_rows, prepared_ws, rows_image, vq_assign
 
 COS_EPS = 1e-12
 COS_FUSED_DIMS = (8, 16, 32, 64)
@@ -34,23 +32,8 @@ def cos_prepared(codebook) -> torch.Tensor | None:
     rows en [K, D], |en|^2 [K] and 1 / max(|e|, eps) [K].  Built when the codebook CHANGES, not per step: stamped and refreshed
     exactly like :func:`vq_prepared` (``refresh_vq_prepared`` walks both tables), so a captured step holds no prepare launch and a
     replay after an optimizer step sees the new codebook.  None: shape not served (the caller normalises per call)."""
-    k, d = codebook.shape
-    if not (d % 4 == 0 and codebook.dtype == torch.float32 and codebook.is_contiguous() and codebook.is_cuda):
-        return None
-    cb = codebook.detach()
-    ent = _COS_PREP.get(cb.data_ptr())
-    if ent is not None and (ent.wref() is not codebook or ent.k != k or ent.d != d):
-        ent = None
-    stamp = core._pack_stamp(codebook)
-    if ent is None:
-        ent = _VQPrep()
-        ent.wref, ent.k, ent.d, ent.stamp = weakref.ref(codebook), k, d, None
-        ent.ws = torch.empty(_native.lib().vqk_cos_ws_bytes(k, d), dtype=torch.uint8, device=cb.device)
-        _COS_PREP[cb.data_ptr()] = ent
-    if ent.stamp != stamp:
-        _cos_prepare_now(ent, cb)
-        ent.stamp = stamp
-    return ent.ws
+    served = codebook.shape[1] % 4 == 0 and codebook.dtype == torch.float32 and codebook.is_contiguous() and codebook.is_cuda
+    return prepared_ws(codebook, _COS_PREP, served, lambda k, d: _native.lib().vqk_cos_ws_bytes(k, d), _cos_prepare_now)
 
 
 def _ws_views(ws, k: int, d: int):
@@ -103,8 +86,7 @@ def cos_staged(flat_z: torch.Tensor, codebook: torch.Tensor, want_lo: bool = Fal
     en = _ws_views(_cos_ws(codebook), k, d)[0]
     zn, inv_z = l2norm_rows(flat_z, want_inv=True)
     idx = vq_assign(zn, en, 0)
-    zbuf = torch.zeros(k + 1, dtype=torch.int32, device=dev)
-    hist, sse = zbuf[:k], zbuf[k:].view(torch.float32)
+    hist, sse = hist_sse(k, dev)
     q32 = torch.empty((n, d), dtype=torch.float32, device=dev)
     qlo = torch.empty((n, d), dtype=torch.bfloat16, device=dev) if want_lo else None
     det = core.DETERMINISTIC
@@ -126,8 +108,7 @@ def _cos_forward(flat_z, codebook, want_q32: bool, want_lo: bool, want_stats: bo
     ws = cos_prepared(codebook)
     sse = hist = None
     if want_stats:
-        zbuf = torch.zeros(k + 1, dtype=torch.int32, device=dev)              # histogram | loss sum: one fill launch
-        hist, sse = zbuf[:k], zbuf[k:].view(torch.float32)
+        hist, sse = hist_sse(k, dev)
     idx = torch.empty(n, dtype=torch.int64, device=dev)
     q32 = torch.empty((n, d), dtype=torch.float32, device=dev) if want_q32 else None
     qlo = torch.empty((n, d), dtype=torch.bfloat16, device=dev) if want_lo else None
@@ -164,14 +145,12 @@ class CosLookupFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, codebook, beta: float, out_dtype):
         core._require_gpu(z)
-        z = core.nhwc(z.to(torch.float32))
-        b, d, h, w = z.shape
+        z, flat, (b, d, h, w) = nhwc_rows(z)
         n = b * h * w
         k = codebook.shape[0]
-        flat = z.permute(0, 2, 3, 1).reshape(n, d)           # a view: NHWC memory is already [N][D]
         lo = out_dtype == torch.bfloat16
         idx, q32, qlo, sse, hist = _cos_forward(flat, codebook, not lo, lo, True)
-        q = (qlo if lo else q32).view(b, h, w, d).permute(0, 3, 1, 2)         # [B,D,H,W] over NHWC memory
+        q = rows_image(qlo if lo else q32, (b, d, h, w))
         loss = sse.view(()) * ((1.0 + beta) / float(n * d))
         ctx.save_for_backward(z, idx)
         ctx.cfg = (beta, n, k, d)
@@ -185,17 +164,7 @@ class CosLookupFn(torch.autograd.Function):
         z, idx = ctx.saved_tensors
         beta, n, k, d = ctx.cfg
         cbp = ctx.cb_param
-        dz = torch.empty_like(z, memory_format=core._CL)
-        de = de_tgt = None
-        if ctx.needs_input_grad[1]:
-            de_tgt = core.direct_grad(cbp) if cbp.is_contiguous() else None
-            de = de_tgt if de_tgt is not None else torch.zeros((k, d), dtype=torch.float32, device=z.device)
-        gs = dloss.to(torch.float32).contiguous() if dloss is not None else None
-        dqc = core.nhwc(dq) if dq is not None else None
-        if dqc is not None and dqc.dtype not in (torch.float32, torch.bfloat16):
-            dqc = dqc.to(torch.float32)
-        scale = 2.0 / float(n * d) if gs is not None else 0.0
-        cz, ce = beta * scale, scale
+        dz, de, de_tgt, gs, dqc, cz, ce = lookup_backward_frame(ctx, z, dq, dloss, beta, k, ctx.needs_input_grad[1])
         # the codebook is unchanged between forward and backward (the optimizer steps afterwards): the prepared workspace is the forward's
         ws = _cos_ws(cbp)
         if d in COS_FUSED_DIMS:
@@ -231,13 +200,12 @@ class _CosStagedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, codebook, beta: float, out_dtype):
         core._require_gpu(z)
-        z = core.nhwc(z.to(torch.float32))
-        b, d, h, w = z.shape
+        z, flat, (b, d, h, w) = nhwc_rows(z)
         n = b * h * w
         k = codebook.shape[0]
         lo = out_dtype == torch.bfloat16
-        idx, q32, qlo, sse, hist, zn, inv_z = cos_staged(z.permute(0, 2, 3, 1).reshape(n, d), codebook, lo)
-        q = (qlo if lo else q32).view(b, h, w, d).permute(0, 3, 1, 2)
+        idx, q32, qlo, sse, hist, zn, inv_z = cos_staged(flat, codebook, lo)
+        q = rows_image(qlo if lo else q32, (b, d, h, w))
         loss = sse.view(()) * ((1.0 + beta) / float(n * d))
         ctx.save_for_backward(zn, inv_z, idx, q32)
         ctx.cfg = (beta, n, k, d, b, h, w)
@@ -266,4 +234,4 @@ class _CosStagedFn(torch.autograd.Function):
         return dz, de, None, None
 
 
-__all__ = [_n for _n in dir() if not _n.startswith('__') and _n not in ('core', 'annotations', 'vq_assign', 'weakref')]
+__all__ = [_n for _n in dir() if not _n.startswith('__') and _n not in ('core', 'annotations', 'hist_sse', 'lookup_backward_frame', 'nhwc_rows', 'prepared_ws', 'rows_image', 'vq_assign')]

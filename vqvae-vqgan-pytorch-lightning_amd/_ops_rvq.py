@@ -11,7 +11,7 @@ import torch
 
 from . import _native
 from . import ops as core
-from ._ops_vq import vq_assign, vq_prepared
+from ._ops_vq import hist_sse, lookup_backward_frame, nhwc_rows, rows_image, vq_assign, vq_prepared
 
 RVQ_MAX_DEPTH = 8
 _RVQ_WS: dict = {}                  # _wkey() -> the residual stack of the deterministic backward (core.grow_ws)
@@ -42,8 +42,7 @@ def rvq_staged(flat_z: torch.Tensor, codebook: torch.Tensor, depth: int, want_lo
     dev = flat_z.device
     lib, st = _native.lib(), core._stream()
     ws = vq_prepared(codebook) if codebook.is_contiguous() else None
-    zbuf = torch.zeros(depth * k + depth, dtype=torch.int32, device=dev)
-    hist, sse = zbuf[:depth * k].view(depth, k), zbuf[depth * k:].view(torch.float32)
+    hist, sse = hist_sse(k, dev, depth)
     idx = torch.empty((n, depth), dtype=torch.int64, device=dev)
     r = core.f32c(flat_z)
     zhat = None
@@ -75,8 +74,7 @@ def _rvq_forward(flat_z, codebook, depth: int, want_q32: bool, want_lo: bool, wa
     ws = vq_prepared(codebook)
     sse = hist = None
     if want_stats:
-        zbuf = torch.zeros(depth * k + depth, dtype=torch.int32, device=dev)          # histograms | stage sums: one fill launch
-        hist, sse = zbuf[:depth * k].view(depth, k), zbuf[depth * k:].view(torch.float32)
+        hist, sse = hist_sse(k, dev, depth)
     idx = torch.empty((n, depth), dtype=torch.int64, device=dev)
     q32 = torch.empty((n, d), dtype=torch.float32, device=dev) if want_q32 else None
     qlo = torch.empty((n, d), dtype=torch.bfloat16, device=dev) if want_lo else None
@@ -117,15 +115,13 @@ class RVQLookupFn(torch.autograd.Function):
     def forward(ctx, z, codebook, beta: float, depth: int, out_dtype):
         core._require_gpu(z)
         depth = _check_depth(depth)
-        z = core.nhwc(z.to(torch.float32))
-        b, d, h, w = z.shape
+        z, flat, (b, d, h, w) = nhwc_rows(z)
         n = b * h * w
         cb = codebook.detach().contiguous()
         k = cb.shape[0]
-        flat = z.permute(0, 2, 3, 1).reshape(n, d)           # a view: NHWC memory is already [N][D]
         lo = out_dtype == torch.bfloat16
         idx, q32, qlo, sse, depth_hist = _rvq_forward(flat, codebook, depth, not lo, lo, True)
-        q = (qlo if lo else q32).view(b, h, w, d).permute(0, 3, 1, 2)         # [B,D,H,W] over NHWC memory
+        q = rows_image(qlo if lo else q32, (b, d, h, w))
         hist = depth_hist.sum(0, dtype=torch.int32)              # pooled usage: what the model accumulates and re-initialises from
         loss = sse.sum() * ((1.0 + beta) / float(n * d))
         ctx.save_for_backward(z, cb, idx)
@@ -139,17 +135,7 @@ class RVQLookupFn(torch.autograd.Function):
     def backward(ctx, dq, _didx, dloss, _dhist, _ddh, _dsse):
         z, cb, idx = ctx.saved_tensors
         beta, depth, n, k, d = ctx.cfg
-        dz = torch.empty_like(z, memory_format=core._CL)
-        de = de_tgt = None
-        if ctx.needs_input_grad[1]:
-            de_tgt = core.direct_grad(ctx.cb_param) if ctx.cb_param.is_contiguous() else None
-            de = de_tgt if de_tgt is not None else torch.zeros_like(cb)
-        gs = dloss.to(torch.float32).contiguous() if dloss is not None else None
-        dqc = core.nhwc(dq) if dq is not None else None
-        if dqc is not None and dqc.dtype not in (torch.float32, torch.bfloat16):
-            dqc = dqc.to(torch.float32)
-        scale = 2.0 / float(n * d) if gs is not None else 0.0
-        cz, ce = beta * scale, scale
+        dz, de, de_tgt, gs, dqc, cz, ce = lookup_backward_frame(ctx, z, dq, dloss, beta, k, ctx.needs_input_grad[1])
         if d == 256:
             lib = _native.lib()
             ws = core.grow_ws(_RVQ_WS, z.device, lib.vqk_rvq_backward_ws_bytes(n, d, depth)) if (core.DETERMINISTIC and de is not None) else None
@@ -172,4 +158,4 @@ class RVQLookupFn(torch.autograd.Function):
         return dz, (None if de_tgt is not None else de), None, None, None
 
 
-__all__ = [_n for _n in dir() if not _n.startswith('__') and _n not in ('core', 'annotations', 'vq_assign', 'vq_prepared')]
+__all__ = [_n for _n in dir() if not _n.startswith('__') and _n not in ('core', 'annotations', 'hist_sse', 'lookup_backward_frame', 'nhwc_rows', 'rows_image', 'vq_assign', 'vq_prepared')]

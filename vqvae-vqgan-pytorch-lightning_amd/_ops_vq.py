@@ -44,29 +44,79 @@ def _vq_prepare_now(ent, cb) -> None:
 _PREP_TABLES.append((_VQ_PREP, _vq_prepare_now))
 
 
-def vq_prepared(codebook) -> torch.Tensor | None:
-    """Workspace of the filtered assignment for ``codebook`` (a Parameter / tensor [K, 256] fp32, contiguous): the bf16
-    fragment-major copy, |e|^2, the filter margins and max |e|^2 -- everything that depends on the codebook only.  Built
-    when the codebook CHANGES, not per step: the entry is stamped like the packed conv operands (in-place version +
-    generation of the owning FlatAdamW), refreshed by :func:`repack_owned` right after the AdamW kernel and by
-    :func:`ema_apply` after the EMA update, so a captured step holds no prepare launch.  None: shape not served."""
-    k, d = codebook.shape
-    if not (core.VQ_FILTER and core.VQ_FUSED and d == 256 and k % 32 == 0 and codebook.dtype == torch.float32 and codebook.is_contiguous()):
+def prepared_ws(codebook, table: dict, served: bool, ws_bytes, prepare) -> torch.Tensor | None:
+    """The cache frame of :func:`vq_prepared` and ``cos_prepared``: the workspace ``prepare(ent, codebook)`` derives from
+    ``codebook`` [K, D], ``ws_bytes(k, d)`` bytes, kept in ``table`` under the codebook's data_ptr.  Built when the codebook
+    CHANGES, not per step: the entry is stamped like the packed conv operands (in-place version + generation of the owning
+    FlatAdamW), refreshed by :func:`repack_owned` right after the AdamW kernel and by :func:`ema_apply` after the EMA update
+    (``refresh_vq_prepared`` walks every table of ``_PREP_TABLES``), so a captured step holds no prepare launch.
+    None: ``served`` is false."""
+    if not served:
         return None
+    k, d = codebook.shape
     cb = codebook.detach()
-    ent = _VQ_PREP.get(cb.data_ptr())
-    if ent is not None and (ent.wref() is not codebook or ent.k != k):
+    ent = table.get(cb.data_ptr())
+    if ent is not None and (ent.wref() is not codebook or ent.k != k or ent.d != d):
         ent = None
     stamp = core._pack_stamp(codebook)
     if ent is None:
         ent = _VQPrep()
         ent.wref, ent.k, ent.d, ent.stamp = weakref.ref(codebook), k, d, None
-        ent.ws = torch.empty(_native.lib().vqk_vq_filter_ws_bytes(k, d), dtype=torch.uint8, device=cb.device)
-        _VQ_PREP[cb.data_ptr()] = ent
+        ent.ws = torch.empty(ws_bytes(k, d), dtype=torch.uint8, device=cb.device)
+        table[cb.data_ptr()] = ent
     if ent.stamp != stamp:
-        _vq_prepare_now(ent, cb)
+        prepare(ent, cb)
         ent.stamp = stamp
     return ent.ws
+
+
+def vq_prepared(codebook) -> torch.Tensor | None:
+    """Workspace of the filtered assignment for ``codebook`` (a Parameter / tensor [K, 256] fp32, contiguous): the bf16
+    fragment-major copy, |e|^2, the filter margins and max |e|^2 -- everything that depends on the codebook only
+    (:func:`prepared_ws`).  None: shape not served."""
+    k, d = codebook.shape
+    served = core.VQ_FILTER and core.VQ_FUSED and d == 256 and k % 32 == 0 and codebook.dtype == torch.float32 and codebook.is_contiguous()
+    return prepared_ws(codebook, _VQ_PREP, served, lambda k, d: _native.lib().vqk_vq_filter_ws_bytes(k, d), _vq_prepare_now)
+
+
+def hist_sse(k: int, device, depth: int | None = None):
+    """zeroed (hist int32 [K], sse fp32 [1]) -- with ``depth`` ([depth, K], [depth]) -- in one buffer: one fill launch"""
+    m = depth or 1
+    zbuf = torch.zeros(m * k + m, dtype=torch.int32, device=device)
+    hist, sse = zbuf[:m * k], zbuf[m * k:].view(torch.float32)
+    return (hist.view(depth, k) if depth else hist), sse
+
+
+def nhwc_rows(z):
+    """z [B,D,H,W] -> (z as fp32 NHWC, its memory as rows [N, D] -- a view --, (b, d, h, w))"""
+    z = core.nhwc(z.to(torch.float32))
+    b, d, h, w = z.shape
+    return z, z.permute(0, 2, 3, 1).reshape(b * h * w, d), (b, d, h, w)
+
+
+def rows_image(q, shape):
+    """rows [N, D] -> [B,D,H,W] over the same (NHWC) memory"""
+    b, d, h, w = shape
+    return q.view(b, h, w, d).permute(0, 3, 1, 2)
+
+
+def lookup_backward_frame(ctx, z, dq, dloss, beta: float, k: int, want_de: bool, cast_dq: bool = True):
+    """What the backward of every nearest-code lookup sets up before its kernel: (dz, de, de_tgt, gs, dqc, cz, ce).
+    de: where the codebook gradient is accumulated (atomics / ordered adds) -- straight into the optimizer's arena (de_tgt) when
+    ``ctx.cb_param`` has one, else a zeroed [K, D]; None without ``want_de``.  gs: the loss cotangent on the device or None (then
+    cz = ce = 0).  dqc: the upstream gradient as NHWC (``cast_dq``: anything but fp32 / bf16 becomes fp32) or None."""
+    b, d, h, w = z.shape
+    dz = torch.empty_like(z, memory_format=core._CL)
+    de = de_tgt = None
+    if want_de:
+        de_tgt = core.direct_grad(ctx.cb_param) if ctx.cb_param.is_contiguous() else None
+        de = de_tgt if de_tgt is not None else torch.zeros((k, d), dtype=torch.float32, device=z.device)
+    gs = dloss.to(torch.float32).contiguous() if dloss is not None else None
+    dqc = core.nhwc(dq) if dq is not None else None
+    if cast_dq and dqc is not None and dqc.dtype not in (torch.float32, torch.bfloat16):
+        dqc = dqc.to(torch.float32)
+    scale = 2.0 / float(b * h * w * d) if gs is not None else 0.0
+    return dz, de, de_tgt, gs, dqc, beta * scale, scale
 
 
 def refresh_vq_prepared(owner=None, data_ptr: int | None = None) -> int:
@@ -127,16 +177,14 @@ class VQLookupFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, codebook, beta: float, codebook_loss: bool, assoc: int, out_dtype):
         core._require_gpu(z)
-        z = core.nhwc(z.to(torch.float32))
-        b, d, h, w = z.shape
+        z, flat, (b, d, h, w) = nhwc_rows(z)
         n = b * h * w
         # EMA rewrites the codebook in place right after the lookup: backward must see the pre-update rows
         cb = codebook.detach().contiguous() if codebook_loss else codebook.detach().clone()
         k = cb.shape[0]
-        flat = z.permute(0, 2, 3, 1).reshape(n, d)           # a view: NHWC memory is already [N][D]
         qlo = core.empty_nhwc(b, d, h, w, torch.bfloat16, z.device) if out_dtype == torch.bfloat16 else None
-        zbuf = torch.zeros(k + 1, dtype=torch.int32, device=z.device)            # histogram | loss sum: one fill launch
-        hist, sse = zbuf[:k], zbuf[k:].view(torch.float32).view(())
+        hist, sse = hist_sse(k, z.device)
+        sse = sse.view(())
         ws = vq_prepared(codebook) if codebook.is_contiguous() else None
         if ws is not None:
             # ONE kernel: |z|^2, bf16 filter + exact re-rank, gather, sum (q - z)^2, histogram (csrc/vq_filter.hip); the
@@ -164,26 +212,14 @@ class VQLookupFn(torch.autograd.Function):
     def backward(ctx, dq, _didx, dloss, _dhist):
         z, cb, idx = ctx.saved_tensors
         beta, codebook_loss, n, k, d = ctx.cfg
-        dz = torch.empty_like(z, memory_format=core._CL)
-        de = de_tgt = None
-        if codebook_loss and ctx.needs_input_grad[1]:
-            # the codebook gradient is accumulated (atomics / ordered adds) -- straight into the optimizer's arena when there is one
-            de_tgt = core.direct_grad(ctx.cb_param) if ctx.cb_param.is_contiguous() else None
-            de = de_tgt if de_tgt is not None else torch.zeros_like(cb)
-        gs = dloss.to(torch.float32).contiguous() if dloss is not None else None
-        dqc = core.nhwc(dq) if dq is not None else None
-        scale = 2.0 / float(n * d)
+        dz, de, de_tgt, gs, dqc, cz, ce = lookup_backward_frame(ctx, z, dq, dloss, beta, k, codebook_loss and ctx.needs_input_grad[1],
+                                                                cast_dq=False)
         fused = core.VQ_FUSED and d == 256 and not core.DETERMINISTIC       # (deterministic mode: the ordered two-kernel form)
         fn = _native.lib().vqk_vq_backward_fused_f32 if fused else _native.lib().vqk_vq_backward_f32
         _native.check(fn(z.data_ptr(), cb.data_ptr(), idx.data_ptr(), core._p(dqc),
-                         core.dcode(dqc.dtype) if dqc is not None else core.F32, n, k, d,
-                         beta * scale if gs is not None else 0.0,
-                         scale if gs is not None else 0.0, core._p(gs), dz.data_ptr(),
+                         core.dcode(dqc.dtype) if dqc is not None else core.F32, n, k, d, cz, ce, core._p(gs), dz.data_ptr(),
                          core._p(de), core._stream()), 'vq_backward')
         return dz, (None if de_tgt is not None else de), None, None, None, None
-
-
-
 
 
 

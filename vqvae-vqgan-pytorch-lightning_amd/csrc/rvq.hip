@@ -14,29 +14,20 @@
 // Each stage evaluates the fp32 expression sequence of vqk_vq_forward_f32 on the materialised residual followed by an fp32
 // subtraction and addition: the kernel equals that staged formulation bit for bit.
 //
-// DECODE adds the gathered rows with the forward's accumulation function (rvq_accum): the same bits of zhat for the same tokens.
+// DECODE adds the gathered rows with the forward's accumulation function (lk_accum): the same bits of zhat for the same tokens.
 //
 // BACKWARD recomputes the residuals from z, e and idx by the same running subtraction (the same bits; nothing is saved):
 //   dz = dq + s cz sum_q r_q (stage order);   de[k] += -s ce sum_{(row, q): k_q = k} r_q.
 // Default: per stage, the rows of a 32-row block that share a code are summed through an LDS tile, one coalesced fp32 atomic row
-// per distinct (code, block) -- the scheme of vq_backward_fused_kernel.  Deterministic mode: the residual stack
-// R[N * depth][256] is materialised in the workspace and one block per code adds its rows of R in (row, stage) order -- the
-// scheme of vq.hip::ema_stats_ordered_kernel; no atomics, the same bits every run.
+// per distinct (code, block) -- CHAINS of vq_lookup.h.  Deterministic mode: the residual stack R[N * depth][256] is materialised
+// in the workspace and one block per code adds its rows of R in (row, stage) order -- ORDERED SCAN of vq_lookup.h; no atomics,
+// the same bits every run.  The block partials of sse, their ordered sum and the decode kernel are that header's too.
 // ------------------------------------------------------------------------------------------------
 #include "vq_filter.h"
 
 namespace {
 
 constexpr int RVQ_MAX_DEPTH = 8;
-
-// zhat <- zhat + e[k_q]; the first stage assigns (0 + x would turn a -0 into +0)
-__device__ __forceinline__ f32x4 rvq_accum(const f32x4 acc, const f32x4 ev, bool first) {
-    if (first) return ev;
-    f32x4 o;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) o[t] = __fadd_rn(acc[t], ev[t]);
-    return o;
-}
 
 __device__ __forceinline__ f32x4 rvq_sub(const f32x4 r, const f32x4 ev) {
     f32x4 o;
@@ -97,7 +88,7 @@ __global__ __launch_bounds__(256, 1) void rvq_forward_kernel(const float* __rest
 #pragma unroll
                 for (int t = 0; t < 4; ++t) local = __fmaf_rn(rv[t], rv[t], local);
                 if (want_q) {
-                    const f32x4 acc = rvq_accum(q == 0 ? ev[jj] : *reinterpret_cast<const f32x4*>(qr + 32 * jj), ev[jj], q == 0);
+                    const f32x4 acc = lk_accum(q == 0 ? ev[jj] : *reinterpret_cast<const f32x4*>(qr + 32 * jj), ev[jj], q == 0);
                     if (!last) {
                         *reinterpret_cast<f32x4*>(qr + 32 * jj) = acc;
                     } else {
@@ -111,10 +102,7 @@ __global__ __launch_bounds__(256, 1) void rvq_forward_kernel(const float* __rest
                 }
             }
         }
-        if (sse) {
-            local = wave_sum(local);
-            if (lane == 0) sse_s[q][wave] = local;
-        }
+        if (sse) lk_wave_part(local, sse_s[q], lane, wave);
         // histogram of the stage: duplicates inside the block are counted first
         if (hist && tid < 32 && n0 + tid < n) {
             const int me = tid;
@@ -133,45 +121,7 @@ __global__ __launch_bounds__(256, 1) void rvq_forward_kernel(const float* __rest
     if (sse) {
         const int tid = tid_blk;
         __syncthreads();
-        if (tid < depth) {
-            const float part = (sse_s[tid][0] + sse_s[tid][1]) + (sse_s[tid][2] + sse_s[tid][3]);
-            if (sse_part) sse_part[(int64_t)blockIdx.x * depth + tid] = part;      // deterministic mode: added in block order below
-            else atomicAdd(sse + tid, part);
-        }
-    }
-}
-
-// deterministic mode: sse[q] += the blocks' partials in block order (one thread per stage)
-__global__ void rvq_sse_ordered_kernel(const float* __restrict__ part, int blocks, int depth, float* __restrict__ sse) {
-    const int q = threadIdx.x;
-    if (q >= depth) return;
-    float acc = 0.0f;
-    for (int b = 0; b < blocks; ++b) acc += part[(int64_t)b * depth + q];
-    sse[q] += acc;
-}
-
-// one thread per (row, four columns); an index outside [0, K) contributes nothing and reads nothing
-__global__ __launch_bounds__(256) void rvq_decode_kernel(const int64_t* __restrict__ idx, const float* __restrict__ e, int64_t n, int k,
-                                                         int d, int depth, float* __restrict__ q32, bf16_raw* __restrict__ q_lo) {
-    const int d4 = d >> 2;
-    const int64_t total = n * d4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t row = i / d4;
-        const int c = (int)(i - row * d4) * 4;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        bool first = true;
-        for (int q = 0; q < depth; ++q) {
-            const int64_t code = idx[row * depth + q];
-            if (code < 0 || code >= k) continue;
-            acc = rvq_accum(acc, *reinterpret_cast<const f32x4*>(e + code * d + c), first);
-            first = false;
-        }
-        if (q32) *reinterpret_cast<f32x4*>(q32 + row * d + c) = acc;
-        if (q_lo) {
-            typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-            const u32x2 ob = {pack2_bf16(acc[0], acc[1]), pack2_bf16(acc[2], acc[3])};
-            *reinterpret_cast<u32x2*>(q_lo + row * d + c) = ob;
-        }
+        if (tid < depth) lk_sse_emit(sse_s[tid], sse + tid, sse_part, (int64_t)blockIdx.x * depth + tid);
     }
 }
 
@@ -211,51 +161,27 @@ __global__ __launch_bounds__(256) void rvq_backward_kernel(const float* __restri
             for (int jj = 0; jj < 8; ++jj) {
                 const f32x4 ev = ok ? *reinterpret_cast<const f32x4*>(er + 32 * jj) : f32x4{0.f, 0.f, 0.f, 0.f};
                 rv[jj] = rvq_sub(rv[jj], ev);
-                sum[jj] = rvq_accum(sum[jj], rv[jj], q == 0);
+                sum[jj] = lk_accum(sum[jj], rv[jj], q == 0);
                 if (DE == 1) *reinterpret_cast<f32x4*>(tile + row * ALD + sub * 4 + 32 * jj) = rv[jj];
                 if (DE == 2) *reinterpret_cast<f32x4*>(rstack + ((n0 + row) * depth + q) * FD + sub * 4 + 32 * jj) = rv[jj];
             }
         }
         if constexpr (DE == 1) {
             __syncthreads();
-            // rows that share a code form a chain in row order: first_s[r] == r marks the head, next_s the next member
-            if (tid < 32) {
-                const int code = code_s[tid];
-                int first = tid, next = -1;
-                if (code >= 0) {
-                    for (int u = 0; u < tid; ++u)
-                        if (code_s[u] == code) { first = u; break; }
-                    for (int u = tid + 1; u < 32; ++u)
-                        if (code_s[u] == code) { next = u; break; }
-                }
-                first_s[tid] = first; next_s[tid] = next;
-            }
+            if (tid < 32) lk_build_chains(code_s, first_s, next_s, tid);
             __syncthreads();
-            // wave w: heads w, w + 4, ...; lane: columns lane + 64 t.  ONE coalesced fp32 atomic row per distinct code of the block
-            for (int r = wave; r < 32; r += 4) {
-                if (code_s[r] < 0 || first_s[r] != r) continue;      // wave-uniform
-                float a[4] = {0.f, 0.f, 0.f, 0.f};
-                for (int m = r; m >= 0; m = next_s[m]) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) a[t] += tile[m * ALD + t * 64 + lane];
-                }
-                float* drow = de + (int64_t)code_s[r] * FD;
+            lk_chain_rows(tile, ALD, code_s, first_s, next_s, lane, wave, [&](int code, const float (&a)[4], int) {
+                float* drow = de + (int64_t)code * FD;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) atomicAdd(drow + t * 64 + lane, -ce * a[t]);
-            }
+            });
             __syncthreads();                                         // the tile and the chains are rewritten by the next stage
         }
     }
     if (live) {
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
-            f32x4 g;
-            if constexpr (!HAS_DQ) g = f32x4{0.f, 0.f, 0.f, 0.f};
-            else if constexpr (sizeof(TDQ) == 4) g = *reinterpret_cast<const f32x4*>(dq + o + 32 * jj);
-            else {
-                const u16x4 r = *reinterpret_cast<const u16x4*>(dq + o + 32 * jj);
-                g = f32x4{bf16_to_f32(r[0]), bf16_to_f32(r[1]), bf16_to_f32(r[2]), bf16_to_f32(r[3])};
-            }
+            const f32x4 g = lk_load_dq4<TDQ, HAS_DQ>(dq + o + 32 * jj);
             f32x4 out;
 #pragma unroll
             for (int t = 0; t < 4; ++t) out[t] = __fmaf_rn(cz, sum[jj][t], g[t]);
@@ -275,6 +201,7 @@ __global__ __launch_bounds__(256) void rvq_code_grad_ordered_kernel(const float*
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (gs) ce *= *gs;
     float acc = 0.f;
+    // lk_ordered_scan written out: through the helper this kernel is allocated 11 VGPRs instead of 13
     for (int64_t r0 = 0; r0 < rows; r0 += 256) {
         const int64_t r = r0 + tid;
         const unsigned long long m = __ballot(r < rows && idx[r] == code);
@@ -320,13 +247,7 @@ int vqk_rvq_forward_f32(const float* z, const float* e, const void* ws, int64_t 
     constexpr int lds = 2 * 32 * (FD + 4) * 4;                   // residual tile + zhat tile
     const dim3 grid((unsigned)((n + 31) / 32));
     hipStream_t st = vqk_stream(stream);
-    // deterministic mode: the blocks' partials of sse go through the ordered-sum workspace of vqk_set_deterministic, no float atomics
-    float* sse_part = nullptr;
-    if (sse && vqkd::det_state().on) {
-        const vqkd::DetState& det = vqkd::det_state();
-        VQK_REQUIRE(det.ws && det.bytes >= (int64_t)grid.x * depth * 4, VQK_ERR_WORKSPACE);
-        sse_part = det.ws;
-    }
+    LK_SSE_PART(sse_part, sse, (int64_t)grid.x * depth)
 #define RVQ_LAUNCH(C) do { \
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&rvq_forward_kernel<C>), \
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
@@ -337,7 +258,7 @@ int vqk_rvq_forward_f32(const float* z, const float* e, const void* ws, int64_t 
 #undef RVQ_LAUNCH
     VQK_CHECK_LAUNCH();
     if (sse_part) {
-        hipLaunchKernelGGL(rvq_sse_ordered_kernel, dim3(1), dim3(64), 0, st, (const float*)sse_part, (int)grid.x, depth, sse);
+        hipLaunchKernelGGL(lk_sse_ordered_kernel<float>, dim3(1), dim3(64), 0, st, (const float*)sse_part, (int)grid.x, depth, sse);
         VQK_CHECK_LAUNCH();
     }
     return VQK_OK;
@@ -348,7 +269,7 @@ int vqk_rvq_decode_f32(const int64_t* idx, const float* e, int64_t n, int k, int
     VQK_REQUIRE(n >= 0 && k > 0 && d > 0 && (d % 4) == 0 && depth >= 1 && depth <= RVQ_MAX_DEPTH, VQK_ERR_SHAPE);
     VQK_REQUIRE(vqk_aligned16(e) && (!q || vqk_aligned16(q)) && (!q_lo || (reinterpret_cast<uintptr_t>(q_lo) & 7u) == 0), VQK_ERR_ALIGN);
     if (n == 0) return VQK_OK;
-    hipLaunchKernelGGL(rvq_decode_kernel, dim3(vqk_grid_1d(n * (d / 4), 256)), dim3(256), 0, vqk_stream(stream), idx, e, n, k, d, depth, q,
+    hipLaunchKernelGGL(lk_decode_kernel<true>, dim3(vqk_grid_1d(n * (d / 4), 256)), dim3(256), 0, vqk_stream(stream), idx, e, n, k, d, depth, q,
                        reinterpret_cast<bf16_raw*>(q_lo));
     VQK_CHECK_LAUNCH();
     return VQK_OK;
@@ -378,11 +299,7 @@ int vqk_rvq_backward_f32(const float* z, const float* e, const int64_t* idx, con
     float* rstack = ordered ? reinterpret_cast<float*>(ws) : nullptr;
 #define RVB(T, Q, E) hipLaunchKernelGGL((rvq_backward_kernel<T, Q, E>), grid, dim3(256), 0, st, z, e, idx, (const T*)dq, n, k, depth, cz, \
                                        ce, gscale_dev, dz, de, rstack)
-#define RVB_DE(T, Q) do { if (!de) RVB(T, Q, 0); else if (!ordered) RVB(T, Q, 1); else RVB(T, Q, 2); } while (0)
-    if (!dq) RVB_DE(float, false);
-    else if (dq_dtype == VQK_F32) RVB_DE(float, true);
-    else RVB_DE(bf16_raw, true);
-#undef RVB_DE
+    LK_DISPATCH_DQ_DE(RVB, dq, dq_dtype, !de ? 0 : !ordered ? 1 : 2);
 #undef RVB
     VQK_CHECK_LAUNCH();
     if (ordered) {

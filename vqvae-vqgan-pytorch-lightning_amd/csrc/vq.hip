@@ -2,7 +2,7 @@
 // EMA statistics and update.  Restates vqvae/modules/vector_quantizers.py:33-56, :142-172, :337-350
 // of the reference (see include/vqk.h); the arithmetic order of the assignment is the canonical one
 // documented in oracle/vq_oracle.c, so indices are bit-exact against the oracle by construction.
-#include "common.h"
+#include "vq_lookup.h"
 
 // ------------------------------------------------------------------------------------------------
 // |row|^2 : one wavefront per row.  lane l: fma chain over l, l+64, ...; then xor butterfly 32..1.
@@ -648,28 +648,11 @@ __global__ __launch_bounds__(256) void ema_stats_ordered_kernel(const float* __r
                                                                 float* __restrict__ dw) {
     __shared__ unsigned long long masks[4];
     const int64_t code = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (int c0 = 0; c0 < d; c0 += 256) {
         const int c = c0 + tid;
         float acc = 0.f;
-        int cnt = 0;
-        for (int64_t r0 = 0; r0 < n; r0 += 256) {
-            const int64_t r = r0 + tid;
-            const unsigned long long m = __ballot(r < n && idx[r] == code);
-            if (lane == 0) masks[wave] = m;
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                unsigned long long mm = masks[w];          // the same for every thread: no divergence
-                cnt += __popcll(mm);
-                while (mm) {
-                    const int b = __ffsll((long long)mm) - 1;
-                    if (c < d) acc += z[(r0 + w * 64 + b) * d + c];
-                    mm &= mm - 1;
-                }
-            }
-            __syncthreads();
-        }
+        const int cnt = lk_ordered_scan(idx, n, code, masks, true, [&](int64_t r) { if (c < d) acc += z[r * d + c]; });
         if (c < d) dw[code * d + c] += acc;
         if (c0 == 0 && tid == 0) counts[code] += (float)cnt;
     }

@@ -20,10 +20,13 @@
 //   g = dq + s cz (zn - q);  dz = (g - zn (zn.g)) inv_z  (evaluated in float64 from z: the projection cancels);
 //   de[k] += s ce inv_e[k] (en_k (en_k.S_k) - S_k),  S_k = sum_{rows: idx = k} zn  (the per-row term en_k (en_k.zn) - zn is linear).
 // Default: the rows of a 32-row block that share a code are summed through an LDS tile, projected once and sent as ONE coalesced
-// fp32 atomic row per distinct (code, block) -- the scheme of vq_backward_fused_kernel.  Deterministic mode: the per-row terms go to
-// the caller's workspace and one block per code adds its rows in row order -- the scheme of rvq_code_grad_ordered_kernel.
+// fp32 atomic row per distinct (code, block) -- CHAINS of vq_lookup.h (the walk itself is written out here: d <= 64 on a 64-pitch
+// tile with a projection before the atomic).  Deterministic mode: the per-row terms go to the caller's workspace and one block per
+// code adds its rows in row order -- ORDERED SCAN of vq_lookup.h.  The block partial of sse, its ordered sum and the decode kernel
+// (the residual quantizer's at depth 1) are that header's too.
 // ------------------------------------------------------------------------------------------------
 #include "vq_cos.h"
+#include "vq_lookup.h"
 
 namespace {
 
@@ -50,15 +53,9 @@ __device__ __forceinline__ float cos_sse_acc(float local, const f32x4 ev, const 
 
 // the block's partial: waves by butterfly, then (w0 + w1) + (w2 + w3); to the ordered-sum workspace or one atomic
 __device__ __forceinline__ void cos_block_sse(float local, float* part, float* __restrict__ sse, float* __restrict__ sse_part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    local = wave_sum(local);
-    if (lane == 0) part[wave] = local;
+    lk_wave_part(local, part, threadIdx.x & 63, threadIdx.x >> 6);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const float tot = (part[0] + part[1]) + (part[2] + part[3]);
-        if (sse_part) sse_part[blockIdx.x] = tot;
-        else atomicAdd(sse, tot);
-    }
+    if (threadIdx.x == 0) lk_sse_emit(part, sse, sse_part, blockIdx.x);
 }
 
 template <int D>
@@ -211,33 +208,6 @@ __global__ __launch_bounds__(256) void cos_sse_kernel(const float* __restrict__ 
     cos_block_sse(local, part, sse, sse_part);
 }
 
-// deterministic mode: sse += the blocks' partials in block order
-__global__ void cos_sse_ordered_kernel(const float* __restrict__ part, int blocks, float* __restrict__ sse) {
-    if (threadIdx.x != 0) return;
-    float acc = 0.0f;
-    for (int b = 0; b < blocks; ++b) acc += part[b];
-    *sse += acc;
-}
-
-// q = en[tokens]: one thread per (row, four columns); a token outside [0, K) reads nothing and gives a zero row
-__global__ __launch_bounds__(256) void cos_decode_kernel(const int64_t* __restrict__ idx, const float* __restrict__ en, int64_t n, int k,
-                                                         int d, float* __restrict__ q32, bf16_raw* __restrict__ q_lo) {
-    const int d4 = d >> 2;
-    const int64_t total = n * d4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t row = i / d4;
-        const int c = (int)(i - row * d4) * 4;
-        const int64_t code = idx[row];
-        f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-        if (code >= 0 && code < k) ev = *reinterpret_cast<const f32x4*>(en + code * d + c);
-        if (q32) *reinterpret_cast<f32x4*>(q32 + row * d + c) = ev;
-        if (q_lo) {
-            const u16x4 ob = {f32_to_bf16(ev[0]), f32_to_bf16(ev[1]), f32_to_bf16(ev[2]), f32_to_bf16(ev[3])};
-            *reinterpret_cast<u16x4*>(q_lo + row * d + c) = ob;
-        }
-    }
-}
-
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -294,18 +264,7 @@ __global__ __launch_bounds__(256) void cos_backward_kernel(const float* __restri
     }
     if constexpr (DE == 1) {
         __syncthreads();
-        // rows that share a code form a chain in row order: first_s[r] == r marks the head, next_s the next member
-        if (tid < 32) {
-            const int code = code_s[tid];
-            int first = tid, next = -1;
-            if (code >= 0) {
-                for (int u = 0; u < tid; ++u)
-                    if (code_s[u] == code) { first = u; break; }
-                for (int u = tid + 1; u < 32; ++u)
-                    if (code_s[u] == code) { next = u; break; }
-            }
-            first_s[tid] = first; next_s[tid] = next;
-        }
+        if (tid < 32) lk_build_chains(code_s, first_s, next_s, tid);
         __syncthreads();
         // wave w: heads w, w + 4, ...; ONE projected, coalesced fp32 atomic row per distinct code of the block
         for (int r = wave; r < 32; r += 4) {
@@ -327,27 +286,10 @@ __global__ __launch_bounds__(256) void cos_code_grad_ordered_kernel(const float*
                                                                     const float* __restrict__ inv_e, float* __restrict__ de) {
     __shared__ unsigned long long masks[4];
     const int64_t code = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (gs) ce *= *gs;
     float acc = 0.f;
-    for (int64_t r0 = 0; r0 < rows; r0 += 256) {
-        const int64_t r = r0 + tid;
-        const unsigned long long m = __ballot(r < rows && idx[r] == code);
-        if (lane == 0) masks[wave] = m;
-        __syncthreads();
-        if (tid < d) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                unsigned long long mm = masks[w];
-                while (mm) {
-                    const int b = __ffsll((long long)mm) - 1;
-                    acc += contrib[(r0 + w * 64 + b) * d + tid];
-                    mm &= mm - 1;
-                }
-            }
-        }
-        __syncthreads();
-    }
+    lk_ordered_scan(idx, rows, code, masks, tid < d, [&](int64_t r) { acc += contrib[r * d + tid]; });
     if (tid < d) de[code * d + tid] += ce * inv_e[code] * acc;
 }
 
@@ -398,20 +340,14 @@ int vqk_cos_forward_f32(const float* z, const void* ws, int64_t ws_bytes, int64_
     const float* e2 = reinterpret_cast<const float*>(w + cos_off_e2(k, d));
     const dim3 grid((unsigned)((n + 31) / 32));
     hipStream_t st = vqk_stream(stream);
-    // deterministic mode: the blocks' partials of sse go through the ordered-sum workspace of vqk_set_deterministic, no float atomics
-    float* sse_part = nullptr;
-    if (sse && vqkd::det_state().on) {
-        const vqkd::DetState& det = vqkd::det_state();
-        VQK_REQUIRE(det.ws && det.bytes >= (int64_t)grid.x * 4, VQK_ERR_WORKSPACE);
-        sse_part = det.ws;
-    }
+    LK_SSE_PART(sse_part, sse, grid.x)
 #define COS_LAUNCH(DD) hipLaunchKernelGGL((cos_forward_kernel<DD>), grid, dim3(256), 0, st, z, en, e2, n, k, idx, q, \
                                           reinterpret_cast<bf16_raw*>(q_lo), sse, sse_part, hist)
     if (d == 8) COS_LAUNCH(8); else if (d == 16) COS_LAUNCH(16); else if (d == 32) COS_LAUNCH(32); else COS_LAUNCH(64);
 #undef COS_LAUNCH
     VQK_CHECK_LAUNCH();
     if (sse_part) {
-        hipLaunchKernelGGL(cos_sse_ordered_kernel, dim3(1), dim3(64), 0, st, (const float*)sse_part, (int)grid.x, sse);
+        hipLaunchKernelGGL(lk_sse_ordered_kernel<float>, dim3(1), dim3(64), 0, st, (const float*)sse_part, (int)grid.x, 1, sse);
         VQK_CHECK_LAUNCH();
     }
     return VQK_OK;
@@ -424,16 +360,11 @@ int vqk_cos_sse_f32(const float* zn, const float* q, int64_t n, int d, float* ss
     if (n == 0) return VQK_OK;
     const dim3 grid((unsigned)((n + 31) / 32));
     hipStream_t st = vqk_stream(stream);
-    float* sse_part = nullptr;
-    if (vqkd::det_state().on) {
-        const vqkd::DetState& det = vqkd::det_state();
-        VQK_REQUIRE(det.ws && det.bytes >= (int64_t)grid.x * 4, VQK_ERR_WORKSPACE);
-        sse_part = det.ws;
-    }
+    LK_SSE_PART(sse_part, true, grid.x)
     hipLaunchKernelGGL(cos_sse_kernel, grid, dim3(256), 0, st, zn, q, n, d, sse, sse_part);
     VQK_CHECK_LAUNCH();
     if (sse_part) {
-        hipLaunchKernelGGL(cos_sse_ordered_kernel, dim3(1), dim3(64), 0, st, (const float*)sse_part, (int)grid.x, sse);
+        hipLaunchKernelGGL(lk_sse_ordered_kernel<float>, dim3(1), dim3(64), 0, st, (const float*)sse_part, (int)grid.x, 1, sse);
         VQK_CHECK_LAUNCH();
     }
     return VQK_OK;
@@ -446,8 +377,8 @@ int vqk_cos_decode_f32(const int64_t* idx, const void* ws, int64_t ws_bytes, int
     VQK_REQUIRE(vqk_aligned16(ws) && (!q || vqk_aligned16(q)) && (!q_lo || (reinterpret_cast<uintptr_t>(q_lo) & 7u) == 0), VQK_ERR_ALIGN);
     VQK_REQUIRE(ws_bytes >= cos_ws_size(k, d), VQK_ERR_WORKSPACE);
     if (n == 0) return VQK_OK;
-    hipLaunchKernelGGL(cos_decode_kernel, dim3(vqk_grid_1d(n * (d / 4), 256)), dim3(256), 0, vqk_stream(stream), idx,
-                       reinterpret_cast<const float*>(ws), n, k, d, q, reinterpret_cast<bf16_raw*>(q_lo));
+    hipLaunchKernelGGL(lk_decode_kernel<false>, dim3(vqk_grid_1d(n * (d / 4), 256)), dim3(256), 0, vqk_stream(stream), idx,
+                       reinterpret_cast<const float*>(ws), n, k, d, 1, q, reinterpret_cast<bf16_raw*>(q_lo));
     VQK_CHECK_LAUNCH();
     return VQK_OK;
 }
@@ -475,11 +406,7 @@ int vqk_cos_backward_f32(const float* z, const void* ws, const int64_t* idx, con
     float* contrib = ordered ? reinterpret_cast<float*>(ws2) : nullptr;
 #define CSB(T, Q, E) hipLaunchKernelGGL((cos_backward_kernel<T, Q, E>), grid, dim3(256), 0, st, z, en, inv_e, idx, (const T*)dq, n, k, d, \
                                        cz, ce, gscale_dev, dz, de, contrib)
-#define CSB_DE(T, Q) do { if (!de) CSB(T, Q, 0); else if (!ordered) CSB(T, Q, 1); else CSB(T, Q, 2); } while (0)
-    if (!dq) CSB_DE(float, false);
-    else if (dq_dtype == VQK_F32) CSB_DE(float, true);
-    else CSB_DE(bf16_raw, true);
-#undef CSB_DE
+    LK_DISPATCH_DQ_DE(CSB, dq, dq_dtype, !de ? 0 : !ordered ? 1 : 2);
 #undef CSB
     VQK_CHECK_LAUNCH();
     if (ordered) {

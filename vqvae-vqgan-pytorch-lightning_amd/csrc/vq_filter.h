@@ -5,7 +5,7 @@
 // rvq_forward_kernel (rvq.hip: one ranking per stage, the tile holding the running residual).
 // ------------------------------------------------------------------------------------------------
 #pragma once
-#include "common.h"
+#include "vq_lookup.h"
 
 namespace {
 

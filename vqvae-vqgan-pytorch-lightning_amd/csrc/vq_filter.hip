@@ -138,10 +138,7 @@ __global__ __launch_bounds__(256, 1) void vq_assign_filter_kernel(const float* _
             }
         }
     }
-    if (sse) {
-        local = wave_sum(local);
-        if (lane == 0) red_m[wave] = local;
-    }
+    if (sse) lk_wave_part(local, red_m, lane, wave);
     // histogram: duplicates inside the block are counted first (a collapsed codebook puts every row on a few codes)
     if (hist && tid < 32 && n0 + tid < n) {
         const int code = fin[tid];
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(256, 1) void vq_assign_filter_kernel(const float* _
     }
     if (sse) {
         __syncthreads();
-        if (tid == 0) atomicAdd(sse, (red_m[0] + red_m[1]) + (red_m[2] + red_m[3]));
+        if (tid == 0) lk_sse_emit(red_m, sse, nullptr, 0);
     }
 }
 
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(256, 1) void vq_assign_filter_kernel(const float* _
 // vq_code_grad_kernel = 8 + 51 us): block = 32 rows x 256 channels.
 //   dz[row] = dq[row] + s cz (z[row] - e[idx[row]])
 //   dE[k]  += s ce sum_{rows of the block with idx == k} (e[k] - z[row])
-// The rows of a block that share a code are summed through an LDS tile first (chains of equal-code rows), so the
+// The rows of a block that share a code are summed through an LDS tile first (CHAINS of vq_lookup.h), so the
 // block sends ONE coalesced fp32 atomic row per DISTINCT code to dE: a collapsed codebook (every row on a few codes: the
 // state of a fresh model) costs a few atomics per block instead of one per (row, channel), a spread-out assignment at most
 // N x 256 uncontended ones.  Deterministic mode keeps the ordered two-kernel form (vq.hip).
@@ -194,12 +191,7 @@ __global__ __launch_bounds__(256) void vq_backward_fused_kernel(const float* __r
             for (int jj = 0; jj < 8; ++jj) {
                 zv[jj] = *reinterpret_cast<const f32x4*>(z + o + 32 * jj);
                 ev[jj] = *reinterpret_cast<const f32x4*>(er + 32 * jj);
-                if constexpr (!HAS_DQ) g[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
-                else if constexpr (sizeof(TDQ) == 4) g[jj] = *reinterpret_cast<const f32x4*>(dq + o + 32 * jj);
-                else {
-                    const u16x4 r = *reinterpret_cast<const u16x4*>(dq + o + 32 * jj);
-                    g[jj] = f32x4{bf16_to_f32(r[0]), bf16_to_f32(r[1]), bf16_to_f32(r[2]), bf16_to_f32(r[3])};
-                }
+                g[jj] = lk_load_dq4<TDQ, HAS_DQ>(dq + o + 32 * jj);
             }
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) {
@@ -213,33 +205,13 @@ __global__ __launch_bounds__(256) void vq_backward_fused_kernel(const float* __r
     }
     if constexpr (!HAS_DE) return;
     __syncthreads();
-    // rows that share a code form a chain in row order: first_s[r] == r marks the chain's head, next_s the next member
-    // (an LDS float atomic per element was tried first: ds_add_f32 under the 8-way bank conflicts of this layout cost 9 us)
-    if (tid < 32) {
-        const int code = code_s[tid];
-        int first = tid, next = -1;
-        if (code >= 0) {
-            for (int u = 0; u < tid; ++u)
-                if (code_s[u] == code) { first = u; break; }
-            for (int u = tid + 1; u < 32; ++u)
-                if (code_s[u] == code) { next = u; break; }
-        }
-        first_s[tid] = first; next_s[tid] = next;
-    }
+    if (tid < 32) lk_build_chains(code_s, first_s, next_s, tid);
     __syncthreads();
-    // wave w: heads w, w + 4, ...; lane: columns lane + 64 t.  ONE coalesced fp32 atomic row per distinct code of the block,
-    // its members added in row order (the sum inside a block is deterministic; the order of the blocks' atomics is not)
-    for (int r = wave; r < 32; r += 4) {
-        if (code_s[r] < 0 || first_s[r] != r) continue;          // wave-uniform
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int m = r; m >= 0; m = next_s[m]) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) a[t] += diff[m * ALD + t * 64 + lane];
-        }
-        float* drow = de + (int64_t)code_s[r] * FD;
+    lk_chain_rows(diff, ALD, code_s, first_s, next_s, lane, wave, [&](int code, const float (&a)[4], int) {
+        float* drow = de + (int64_t)code * FD;
 #pragma unroll
         for (int t = 0; t < 4; ++t) atomicAdd(drow + t * 64 + lane, ce * a[t]);
-    }
+    });
 }
 
 // EMA statistics (vector_quantizers.py:159-163: counts[k] = #rows on code k, dw[k] = sum of their z) with the same per-block
@@ -266,32 +238,14 @@ __global__ __launch_bounds__(256) void ema_stats_block_kernel(const float* __res
         }
     }
     __syncthreads();
-    if (tid < 32) {
-        const int code = code_s[tid];
-        int first = tid, next = -1;
-        if (code >= 0) {
-            for (int u = 0; u < tid; ++u)
-                if (code_s[u] == code) { first = u; break; }
-            for (int u = tid + 1; u < 32; ++u)
-                if (code_s[u] == code) { next = u; break; }
-        }
-        first_s[tid] = first; next_s[tid] = next;
-    }
+    if (tid < 32) lk_build_chains(code_s, first_s, next_s, tid);
     __syncthreads();
-    for (int r = wave; r < 32; r += 4) {
-        if (code_s[r] < 0 || first_s[r] != r) continue;          // wave-uniform: the chain's head
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        int cnt = 0;
-        for (int m = r; m >= 0; m = next_s[m]) {
-            ++cnt;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) a[t] += tile[m * ALD + t * 64 + lane];
-        }
-        float* drow = dw + (int64_t)code_s[r] * FD;
+    lk_chain_rows(tile, ALD, code_s, first_s, next_s, lane, wave, [&](int code, const float (&a)[4], int cnt) {
+        float* drow = dw + (int64_t)code * FD;
 #pragma unroll
         for (int t = 0; t < 4; ++t) atomicAdd(drow + t * 64 + lane, a[t]);
-        if (lane == 0) atomicAdd(counts + code_s[r], (float)cnt);
-    }
+        if (lane == 0) atomicAdd(counts + code, (float)cnt);
+    });
 }
 
 }  // namespace
@@ -387,15 +341,9 @@ int vqk_vq_backward_fused_f32(const float* z, const float* e, const int64_t* idx
     VQK_REQUIRE(vqk_aligned16(z) && vqk_aligned16(e) && vqk_aligned16(dz) && (!dq || vqk_aligned16(dq)), VQK_ERR_ALIGN);
     if (n == 0) return VQK_OK;
     const dim3 grid((unsigned)((n + 31) / 32));
-#define VQB(T, Q, E) hipLaunchKernelGGL((vq_backward_fused_kernel<T, Q, E>), grid, dim3(256), 0, vqk_stream(stream), z, e, idx, \
+#define VQB(T, Q, E) hipLaunchKernelGGL((vq_backward_fused_kernel<T, Q, (E) != 0>), grid, dim3(256), 0, vqk_stream(stream), z, e, idx, \
                                        (const T*)dq, n, cz, ce, gscale_dev, dz, de)
-    if (dq_dtype == VQK_F32) {
-        if (dq) { if (de) VQB(float, true, true); else VQB(float, true, false); }
-        else { if (de) VQB(float, false, true); else VQB(float, false, false); }
-    } else {
-        if (dq) { if (de) VQB(bf16_raw, true, true); else VQB(bf16_raw, true, false); }
-        else { if (de) VQB(float, false, true); else VQB(float, false, false); }
-    }
+    LK_DISPATCH_DQ_DE(VQB, dq, dq_dtype, de ? 1 : 0);
 #undef VQB
     VQK_CHECK_LAUNCH();
     return VQK_OK;
