@@ -415,10 +415,14 @@ class GumbelVQFn(torch.autograd.Function):
         e_w = core.pack_weights(cb.reshape(-1), dt, k, d, 1, False, 0)                                 # [K][D]
         dyv = core.raw_conv_fprop(dq_img, e_w, None, None, 1, False, 0, dt, k, 0)                      # [N][K]
         gs = dkl.to(torch.float32).contiguous() if dkl is not None else None
+        if gs is None and ctx.sched is not None:
+            # no KL cotangent, but y must still be recomputed at the forward's temperature sched[0]: the kernel takes the schedule
+            # tensor and a zero cotangent (with a schedule tensor it reads its KL coefficient sched[1] / n itself)
+            gs = torch.zeros((), dtype=torch.float32, device=logits.device)
         dlogits = torch.empty_like(logits, memory_format=core._CL)
         _native.check(lib.vqk_gumbel_backward(core.dcode(dt), logits.data_ptr(), noise.data_ptr(), dyv.data_ptr(), n, k, tau,
                                               kl_cost if gs is not None else 0.0, core._p(gs), dlogits.data_ptr(),
-                                              core._p(ctx.sched) if gs is not None else 0, st),
+                                              core._p(ctx.sched), st),
                       'gumbel_backward')
         de = None
         if ctx.needs_input_grad[1]:

@@ -16,6 +16,12 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// log p_ik = -d_ik / T - lse_i in ONE rounding, wherever a kernel forms it.  Written as "-d * inv_t - l" the compiler contracts some
+// sites into an fma and leaves others as a multiply and a subtraction (at T = 0.01 the two differ by an ulp of |d / T| ~ 30, 2e-6 in
+// p): entropy_dd_kernel and entropy_dd_split_kernel then disagreed by up to 5e-4 of an element whose bracket cancels, and the bf16
+// split no longer was the split of the fp32 cotangent.
+__device__ __forceinline__ float ent_logp(float d, float inv_t, float l) { return __fmaf_rn(-d, inv_t, -l); }
+
 // lse_i = logsumexp_k(a_ik), h_i = lse_i - sum_k p_ik a_ik ; hsum += sum_i h_i
 __global__ __launch_bounds__(256) void entropy_rows_kernel(const float* __restrict__ dmat, int64_t n, int k, float inv_t,
                                                            float* __restrict__ lse, float* __restrict__ hrow,
@@ -54,7 +60,7 @@ __global__ __launch_bounds__(256) void entropy_colsum_kernel(const float* __rest
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     const int64_t r1 = min(n, r0 + rows_per_block);
     float acc = 0.f;
-    for (int64_t r = r0; r < r1; ++r) acc += __expf(-dmat[r * k + col] * inv_t - lse[r]);
+    for (int64_t r = r0; r < r1; ++r) acc += __expf(ent_logp(dmat[r * k + col], inv_t, lse[r]));
     atomicAdd(psum + col, acc);
 }
 
@@ -87,10 +93,10 @@ __global__ __launch_bounds__(256) void entropy_dd_kernel(float* __restrict__ dma
     float* dr = dmat + row * k;
     const float l = lse[row], h = hrow[row];
     float ub = 0.f;
-    for (int c = lane; c < k; c += 64) ub = __fmaf_rn(__expf(-dr[c] * inv_t - l), u[c], ub);
+    for (int c = lane; c < k; c += 64) ub = __fmaf_rn(__expf(ent_logp(dr[c], inv_t, l)), u[c], ub);
     ub = wave_sum(ub);
     for (int c = lane; c < k; c += 64) {
-        const float lp = -dr[c] * inv_t - l;
+        const float lp = ent_logp(dr[c], inv_t, l);
         const float p = __expf(lp);
         dr[c] = coef * p * (-(lp + h) + (u[c] - ub));
     }
@@ -109,7 +115,7 @@ __global__ __launch_bounds__(256) void entropy_dd_split_kernel(const float* __re
     const float* dr = dmat + row * k;
     const float l = lse[row], h = hrow[row];
     float ub = 0.f;
-    for (int c = lane; c < k; c += 64) ub = __fmaf_rn(__expf(-dr[c] * inv_t - l), u[c], ub);      // (same order as entropy_dd_kernel)
+    for (int c = lane; c < k; c += 64) ub = __fmaf_rn(__expf(ent_logp(dr[c], inv_t, l)), u[c], ub);      // (same order as entropy_dd_kernel)
     ub = wave_sum(ub);
     unsigned* hr = reinterpret_cast<unsigned*>(hi + row * k);
     unsigned* lr = reinterpret_cast<unsigned*>(lo + row * k);
@@ -117,7 +123,7 @@ __global__ __launch_bounds__(256) void entropy_dd_split_kernel(const float* __re
         float v[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const float lp = -dr[c + e] * inv_t - l;
+            const float lp = ent_logp(dr[c + e], inv_t, l);
             const float pr = __expf(lp);
             v[e] = coef * pr * (-(lp + h) + (u[c + e] - ub));
         }
@@ -162,10 +168,10 @@ __global__ __launch_bounds__(256) void entropy_dd_argmax_kernel(float* __restric
     const float l = lse[row], h = hrow[row];
     const int code = (int)idx[row];
     float ub = 0.f;
-    for (int c = lane; c < k; c += 64) ub = __fmaf_rn(__expf(-dr[c] * inv_t - l), u[c], ub);
+    for (int c = lane; c < k; c += 64) ub = __fmaf_rn(__expf(ent_logp(dr[c], inv_t, l)), u[c], ub);
     ub = wave_sum(ub);
     for (int c = lane; c < k; c += 64) {
-        const float lp = -dr[c] * inv_t - l;
+        const float lp = ent_logp(dr[c], inv_t, l);
         const float p = __expf(lp);
         dr[c] = coef * (p * (-(lp + h) + 1.0f + (u[c] - ub)) - (c == code ? 1.0f : 0.0f));
     }
