@@ -150,6 +150,17 @@ int vqk_vq_backward_f32(const float* z, const float* e, const int64_t* idx, cons
 int vqk_vq_backward_fused_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype,
                               int64_t n, int k, int d, float cz, float ce, const float* gscale_dev, float* dz, float* de,
                               void* stream);
+/* vqk_vq_backward_f32 with the rotation-trick gradient (csrc/vq_rot.hip; Fifty et al., ICLR 2025) in place of the straight-through
+ * copy: per row, nz = max(|z|, 1e-6), nq = max(|q|, 1e-6), zh = z / nz, qh = q / nq, lam = nq / nz, r = (zh + qh) / max(|zh + qh|, 1e-12),
+ *   dz = lam * (dq - 2 r (r . dq) + 2 zh (qh . dq)) + s*cz * (z - q)   ;   de[idx] += s*ce * (q - z)   (as vqk_vq_backward_f32)
+ * in fp32 from five dot products per row, one pass over z, q and dq.  Served: 0 < d <= 1024 (VQK_ERR_SHAPE otherwise), any alignment
+ * (16-byte accesses when d % 4 == 0 and z, e, dq, dz are 16-byte aligned); n == 0 launches nothing.  dq == NULL or a row with
+ * dq = 0: the bits of vqk_vq_backward_f32's dz.  de: d == 256 outside deterministic mode in the same launch (one atomic row per
+ * distinct code and 32-row block, as vqk_vq_backward_fused_f32), otherwise by the launches of vqk_vq_backward_f32 -- in
+ * deterministic mode its ordered form, the same bits.  A zero z, a zero code and z = -q give finite rows. */
+int vqk_vq_backward_rot_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype,
+                            int64_t n, int k, int d, float cz, float ce, const float* gscale_dev, float* dz, float* de,
+                            void* stream);
 /* ---------------------------------------------------------------- finite scalar quantizer ---------
  * Mentzer et al. 2023 (csrc/fsq.hip).  z[N][D] fp32 rows, w_in[d][D], b_in[d], w_out[D][d], b_out[D] fp32; levels: d ints on the HOST
  * (they travel by value in the launch arguments).  u = W_in z + b_in; half_l = (L - 1)(1 + 1e-3) / 2, offset = 0.5 for an even L, shift =

@@ -55,6 +55,7 @@ _PROTOS = {
     'vqk_gumbel_backward': [I, P, P, P, L, I, F, F, P, P, P, P],
     'vqk_vq_gather_f32': [P, P, P, L, I, I, P, P, P, P, P],
     'vqk_vq_backward_f32': [P, P, P, P, I, L, I, I, F, F, P, P, P, P],
+    'vqk_vq_backward_rot_f32': [P, P, P, P, I, L, I, I, F, F, P, P, P, P],
     'vqk_fsq_forward': [P, P, P, P, P, L, I, I, P, P, P, P, P, P, P],
     'vqk_fsq_decode': [P, P, P, L, I, I, P, P, P, P],
     'vqk_fsq_backward': [P, P, P, I, P, P, L, I, I, P, P, P, P, P, P, I, P, L, P],

@@ -172,10 +172,13 @@ class VQLookupFn(torch.autograd.Function):
 
     Standard (vector_quantizers.py:23-61): loss = mse(q, z.detach()) + beta * mse(q.detach(), z), grads to z and E.
     EMA      (vector_quantizers.py:128-180): loss = beta * mse(q.detach(), z), codebook has no grad.
+    ``rotate``: the rotation-trick estimator (Fifty et al., ICLR 2025; csrc/vq_rot.hip) -- the forward is the same call sequence,
+    the backward carries dq to z through the rotation and rescaling that maps z onto q instead of copying it; the commitment
+    term and the codebook gradient are unchanged.  The mode travels on the autograd node.
     Returns (q [B,D,H,W] in out_dtype, idx [B, H*W] int64, loss 0-dim fp32, hist int32 [K])."""
 
     @staticmethod
-    def forward(ctx, z, codebook, beta: float, codebook_loss: bool, assoc: int, out_dtype):
+    def forward(ctx, z, codebook, beta: float, codebook_loss: bool, assoc: int, out_dtype, rotate: bool = False):
         core._require_gpu(z)
         z, flat, (b, d, h, w) = nhwc_rows(z)
         n = b * h * w
@@ -203,6 +206,7 @@ class VQLookupFn(torch.autograd.Function):
         loss = sse * (((1.0 + beta) if codebook_loss else beta) / float(n * d))       # mse + beta * mse | beta * mse: one launch
         ctx.save_for_backward(z, cb, idx)
         ctx.cfg = (beta, codebook_loss, n, k, d)
+        ctx.rotate = bool(rotate)
         ctx.cb_param = codebook
         ctx.mark_non_differentiable(idx, hist)
         q = qlo if qlo is not None else q32
@@ -215,11 +219,14 @@ class VQLookupFn(torch.autograd.Function):
         dz, de, de_tgt, gs, dqc, cz, ce = lookup_backward_frame(ctx, z, dq, dloss, beta, k, codebook_loss and ctx.needs_input_grad[1],
                                                                 cast_dq=False)
         fused = core.VQ_FUSED and d == 256 and not core.DETERMINISTIC       # (deterministic mode: the ordered two-kernel form)
-        fn = _native.lib().vqk_vq_backward_fused_f32 if fused else _native.lib().vqk_vq_backward_f32
+        if ctx.rotate:                                                      # one entry point: it picks the fused / ordered form itself
+            fn = _native.lib().vqk_vq_backward_rot_f32
+        else:
+            fn = _native.lib().vqk_vq_backward_fused_f32 if fused else _native.lib().vqk_vq_backward_f32
         _native.check(fn(z.data_ptr(), cb.data_ptr(), idx.data_ptr(), core._p(dqc),
                          core.dcode(dqc.dtype) if dqc is not None else core.F32, n, k, d, cz, ce, core._p(gs), dz.data_ptr(),
-                         core._p(de), core._stream()), 'vq_backward')
-        return dz, (None if de_tgt is not None else de), None, None, None, None
+                         core._p(de), core._stream()), 'vq_backward_rot' if ctx.rotate else 'vq_backward')
+        return dz, (None if de_tgt is not None else de), None, None, None, None, None
 
 
 

@@ -105,6 +105,9 @@ struct DetState { int on; float* ws; int64_t bytes; };
 DetState& det_state();
 DetState& scratch_state();      // vqk_set_scratch: zero-initialised fp32 scratch of the current stream (split-K partial sums)
 DetState& tile_queue_state();   // vqk_set_tile_queue: the current stream's tile-queue words (conv_geom.h: ConvGeom::tq)
+// the codebook-gradient launches of vqk_vq_backward_f32 (vq.hip), for the rotation backward (vq_rot.hip) beside its own dz kernel
+int vq_code_grad(const float* z, const float* e, const int64_t* idx, int64_t n, int k, int d, float ce, const float* gscale_dev,
+                 float* de, void* stream);
 }
 // launch heuristics that tools/ sweep (include/vqk.h: vqk_set_tuning): process-wide slots, relaxed atomics; a call site
 // resolves its slot once and then reads one int per launch.  The library itself never reads the environment.

@@ -678,6 +678,34 @@ __global__ void ema_weight_kernel(const float* __restrict__ ema_count, float* __
     }
 }
 
+// the codebook-gradient half of vqk_vq_backward_f32: de[idx] += s ce (e[idx] - z) by vq_code_grad_kernel (deterministic mode: rows in
+// row order, the splits through the workspace in split order).  Shared with the rotation backward (vq_rot.hip): the same launches,
+// the same bits.  CALLER: n > 0, d <= 1024.
+int vqkd::vq_code_grad(const float* z, const float* e, const int64_t* idx, int64_t n, int k, int d, float ce, const float* gscale_dev,
+                       float* de, void* stream) {
+    int splits = (int)((n + 255) / 256);              // <= 256 rows per block even when every row hits one code
+    if (splits > 64) splits = 64;
+    vqkd::DetState& dst = vqkd::det_state();
+    const int det = dst.on;
+    float* part = nullptr;
+    if (det) {
+        // deterministic mode: rows of a (code, split) block added in row order, the splits' partial rows through the
+        // workspace in split order; without a workspace that holds them: one block per code
+        if (splits > 32) splits = 32;
+        while (splits > 1 && (int64_t)splits * k * d * 4 > dst.bytes) splits >>= 1;
+        part = (splits > 1 && dst.ws) ? dst.ws : nullptr;
+        if (!part) splits = 1;
+    }
+    const int64_t span = (n + splits - 1) / splits;
+    hipLaunchKernelGGL(vq_code_grad_kernel, dim3((unsigned)k, (unsigned)splits), dim3(256), 0, vqk_stream(stream), z, e,
+                       idx, n, d, span, ce, gscale_dev, de, det, part);
+    if (part)
+        hipLaunchKernelGGL(vq_code_grad_reduce_kernel, dim3((unsigned)(((int64_t)k * d + 255) / 256)), dim3(256), 0,
+                           vqk_stream(stream), (const float*)part, (int64_t)k * d, splits, de);
+    VQK_CHECK_LAUNCH();
+    return VQK_OK;
+}
+
 extern "C" {
 
 int vqk_row_sqnorm_f32(const float* x, int64_t rows, int d, float* out, void* stream) {
@@ -785,27 +813,7 @@ int vqk_vq_backward_f32(const float* z, const float* e, const int64_t* idx, cons
     else if (dq_dtype == VQK_BF16)
         hipLaunchKernelGGL(vq_backward_kernel<bf16_raw>, grid, dim3(256), 0, vqk_stream(stream), z, e, idx, (const bf16_raw*)dq, n, d, cz, gscale_dev, dz);
     else return VQK_ERR_DTYPE;
-    if (de) {
-        int splits = (int)((n + 255) / 256);              // <= 256 rows per block even when every row hits one code
-        if (splits > 64) splits = 64;
-        vqkd::DetState& dst = vqkd::det_state();
-        const int det = dst.on;
-        float* part = nullptr;
-        if (det) {
-            // deterministic mode: rows of a (code, split) block added in row order, the splits' partial rows through the
-            // workspace in split order; without a workspace that holds them: one block per code
-            if (splits > 32) splits = 32;
-            while (splits > 1 && (int64_t)splits * k * d * 4 > dst.bytes) splits >>= 1;
-            part = (splits > 1 && dst.ws) ? dst.ws : nullptr;
-            if (!part) splits = 1;
-        }
-        const int64_t span = (n + splits - 1) / splits;
-        hipLaunchKernelGGL(vq_code_grad_kernel, dim3((unsigned)k, (unsigned)splits), dim3(256), 0, vqk_stream(stream), z, e,
-                           idx, n, d, span, ce, gscale_dev, de, det, part);
-        if (part)
-            hipLaunchKernelGGL(vq_code_grad_reduce_kernel, dim3((unsigned)(((int64_t)k * d + 255) / 256)), dim3(256), 0,
-                               vqk_stream(stream), (const float*)part, (int64_t)k * d, splits, de);
-    }
+    if (de) return vqkd::vq_code_grad(z, e, idx, n, k, d, ce, gscale_dev, de, stream);
     VQK_CHECK_LAUNCH();
     return VQK_OK;
 }

@@ -109,11 +109,16 @@ class VQVAE(BaseVQVAE, _LightningBase):
         # optional `codebook_init` block of the quantizer config: a k-means start from encoder latents (init_codebook_from_batches);
         # absent or empty: the uniform start
         self.codebook_init = self._parse_codebook_init(q_conf.get('codebook_init'), qt, self.cb_size)
+        # optional `gradient` key of the standard and EMA quantizers: 'straight_through' (the default when absent) or 'rotation'
+        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'residual', 'cosine'):
+            raise ValueError(f"quantizer.params.gradient: the gradient estimator is built for the 'standard' and 'ema' quantizers only, "
+                             f'not for {qt!r}')
+        gradient = qp.get('gradient', 'straight_through')
         if qt == 'standard':
-            self.quantizer = VectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']))
+            self.quantizer = VectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']), gradient)
         elif qt == 'ema':
             self.quantizer = EMAVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']),
-                                                float(qp['decay']), float(qp['epsilon']))
+                                                float(qp['decay']), float(qp['epsilon']), gradient)
         elif qt == 'entropy':
             self.quantizer = EntropyVectorQuantizer(self.cb_size, self.latent_dim, float(qp['ent_loss_ratio']),
                                                     float(qp['ent_temperature']), str(qp['ent_loss_type']),

@@ -59,14 +59,28 @@ def _flat_view(z: torch.Tensor):
     return z.permute(0, 2, 3, 1).reshape(b * h * w, d)
 
 
+GRADIENTS = ('straight_through', 'rotation')
+
+
+def check_gradient(gradient: str) -> bool:
+    """``quantizer.params.gradient`` of the standard and EMA quantizers -> the ``rotate`` flag of ``ops.VQLookupFn``:
+    'straight_through' copies the decoder's gradient to the encoder (dz = dq), 'rotation' carries it through the rotation and
+    rescaling that maps z onto its code (the rotation trick, Fifty et al., ICLR 2025; csrc/vq_rot.hip).  The forward values, the
+    losses, the codebook update and the state dict are the same in both modes."""
+    if gradient not in GRADIENTS:
+        raise ValueError(f'quantizer.params.gradient must be one of {GRADIENTS}, got {gradient!r}')
+    return gradient == 'rotation'
+
+
 class VectorQuantizer(BaseVectorQuantizer):
-    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25):
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25, gradient: str = 'straight_through'):
         super().__init__(num_embeddings, embedding_dim)
         self.commitment_cost = commitment_cost
+        self.gradient, self.rotate = gradient, check_gradient(gradient)
 
     def forward(self, x: torch.Tensor):
         q, idx, loss, hist = ops.VQLookupFn.apply(x, self.codebook.weight, self.commitment_cost, True, 0,
-                                                  self.compute_dtype)
+                                                  self.compute_dtype, self.rotate)
         self.last_hist = hist
         return q, idx, loss
 
@@ -78,9 +92,10 @@ class VectorQuantizer(BaseVectorQuantizer):
 
 class EMAVectorQuantizer(BaseVectorQuantizer):
     def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25, decay: float = 0.95,
-                 epsilon: float = 1e-5):
+                 epsilon: float = 1e-5, gradient: str = 'straight_through'):
         super().__init__(num_embeddings, embedding_dim)
         self.commitment_cost = commitment_cost
+        self.gradient, self.rotate = gradient, check_gradient(gradient)
         self.codebook.requires_grad_(False)
         self.register_buffer('ema_count', torch.zeros(num_embeddings))
         self.register_buffer('ema_weight', torch.empty(num_embeddings, embedding_dim).uniform_(-1 / num_embeddings,
@@ -97,7 +112,7 @@ class EMAVectorQuantizer(BaseVectorQuantizer):
 
     def forward(self, x: torch.Tensor):
         q, idx, loss, hist = ops.VQLookupFn.apply(x, self.codebook.weight, self.commitment_cost, False, 0,
-                                                  self.compute_dtype)
+                                                  self.compute_dtype, self.rotate)
         self.last_hist = hist
         if self.training:
             with torch.no_grad():
