@@ -507,11 +507,32 @@ int vqk_conv_pack_weights(const float* w, void* out, int dtype, int cout, int ci
  * arguments.  Issued once per optimizer step (after vqk_adamw) instead of one pack launch per conv call; replaces
  * the per-call weight casts autocast performs in the reference's conv calls (vqvae/modules/autoencoder.py:57-60). */
 int vqk_conv_pack_multi(const int64_t* descs_dev, int ndesc, int blocks_per_desc, void* stream);
-/* test / tuning hook for the fprop kernel choice: -1 automatic, 0 im2col kernel only, 1 halo kernels when
- * eligible, 2 halo kernel with LDS-staged weights (layout 0) instead of register weights, 3 one-tile-per-block
- * register-weight halo kernel instead of the persistent stream kernel (bf16), 4 stream kernel without its half-tile
- * (128-pixel) form for maps with fewer 256-pixel tiles than CUs */
+/* test / tuning hook for the conv kernel choice of the calling thread (csrc/conv_geom.h: ConvVariant):
+ *  -1 automatic;
+ *   0 the general kernels only: im2col forward / data gradient (no halo, thin, matrix-wave or stride-2 form), general weight gradient;
+ *   1 halo kernels when eligible (what the automatic choice does);
+ *   2 vqk_conv_weight_layout answers 0, hence the halo kernel with LDS-staged plain weights instead of register weights;
+ *     vqk_conv2d_fprop_pooled / _gnstats refuse;
+ *   3 bf16 layout-1 convs on the one-tile-per-block register-weight halo kernel instead of the persistent stream and
+ *     matrix/auxiliary-wave kernels; the pooled / gnstats entries refuse;
+ *   4 stream kernel without its half-tile (128-pixel) form for maps with fewer 256-pixel tiles than CUs;
+ *   5 never the matrix/auxiliary-wave kernel (forward, 1x1, phase and stride-2 forms);
+ *   6 that kernel whenever the shape is eligible, below the MX_MIN_TILES tuning slot too. */
 int vqk_conv_set_variant(int variant);
+/* The forward launcher's PLAN for a problem, without launching (no device needed): the kernel form vqk_conv2d_fprop (flags 0 / 1),
+ * vqk_conv2d_fprop_pooled (flag 2: act 0, wlayout 1) or vqk_conv2d_fprop_gnstats (flag 4, with 2 for its pooled form) would launch
+ * under the calling thread's variant, block caps and scratch and the current tuning slots -- a form id >= 0 -- or the negative
+ * status that call would return given valid, aligned pointers.  flags: 1 a residual is added, 2 pooled epilogue, 4 fused GroupNorm
+ * sums (the groups are not checked), 8 a strided, explicitly padded or zero-stuffed conv of vqk_conv2d_general (always the im2col
+ * kernel; the other arguments then only pick the label).  The epilogue gains of vqk_conv2d_general count as 1.  Form ids: 0 fp32 thin-out, 1 fp32 thin-in, 2 matrix/auxiliary-wave,
+ * 3 its 1x1 form, 4 / 5 / 6 stream kernel with thin / half / full tiles, 7 register-weight halo, 8 LDS-weight halo, 9 bf16 thin-in,
+ * 10 im2col, 11 im2col with split-K, 12 split-product (wlayout 5), 13 its 1x1 form.  details (may be NULL): five ints --
+ * patch width log2 (5 / 4, 0: no pixel patches), blocks of the first launch (0: sized by the form's own launcher), split-K parts,
+ * number of launches, 1 when the form is memory-bound (the event statistics report it by bytes, name suffix " (HBM)").
+ * vqk_conv_fprop_form_name: the kernel's name for the event statistics, "?" for an unknown id. */
+int vqk_conv_fprop_plan(int dtype, int out_dtype, int n, int h_in, int w_in, int cin, int cout, int ksize, int ups, int act,
+                        int wlayout, int flags, int* details);
+const char* vqk_conv_fprop_form_name(int form, int dtype);
 /* Deterministic mode (the reference trains with `deterministic=True`, vqvae/train.py:130).  on = 1: the float accumulations of
  * the train step that are otherwise combined with atomics in arrival order -- split-K partials of the weight gradients, column
  * sums (bias gradients), the cross-block sums of the GroupNorm statistics / backward reductions and of d gamma / d beta, the
@@ -565,7 +586,7 @@ const char* vqk_tuning_name(int i);
  * blocks per CU).  256 = one block per CU, leaving room for a kernel that runs concurrently on another stream
  * (the host overlaps a layer's wgrad with its dgrad and GroupNorm backward).  The caps are THREAD-LOCAL: they apply to the
  * launches the calling thread issues afterwards (set, launch, reset in one place), never to another thread or device
- * context.  vqk_conv_set_variant above is a process-wide TEST hook and not meant for product code. */
+ * context.  vqk_conv_set_variant above is a TEST hook, thread-local like the caps, and not meant for product code. */
 int vqk_conv_set_block_caps(int stream_blocks, int wgrad_blocks);
 /* DIAGNOSTIC (tools/comm_probe.py): a stand-in for a collective's kernel -- `blocks` persistent 256-thread blocks stream
  * dst[i] += src[i] over `bytes` (16-byte aligned, a multiple of 16) `passes` times, sleeping `sleep` x 64 cycles between

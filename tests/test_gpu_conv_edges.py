@@ -1,7 +1,7 @@
 """Both sides of the conv launchers' shape guards against float64 torch.
 
-The launchers (csrc/conv.hip::launch_fprop, csrc/conv_wgrad.hip::wgrad_general, vqk_conv2d_wgrad_x3_f32) and their Python
-mirrors in ops.py pick a kernel from the map shape: w % 32, w % 16, h % 8, the 64 KiB LDS bound of the edge-conv kernels,
+The launchers (csrc/conv.hip::launch_fprop, csrc/conv_wgrad.hip::wgrad_general, vqk_conv2d_wgrad_x3_f32) and, for the weight
+gradients, their Python mirrors in ops.py pick a kernel from the map shape: w % 32, w % 16, h % 8, the 64 KiB LDS bound of the edge-conv kernels,
 the 32-bit buffer offsets of the matrix/auxiliary-wave kernel.  Every case below sits just inside or just outside one of those
 guards, runs the product's autograd node (``ops.conv2d``: y, dx, dW) and compares with F.conv2d / its autograd in float64 on
 the same inputs (bf16 mode: on the bf16-rounded inputs).  Where the library chooses internally, the case also runs the general
@@ -360,9 +360,10 @@ def _large(mode, n):
         _check(mode, dxx, rdx, 'dx')
         _check(mode, wd.grad, rdw, 'dW', wgrad=True)
         if mode == 'bf16':
-            # ops' mirror names the matrix/auxiliary-wave kernel for both batch sizes: it does not model the 32-bit offset bound
-            # behind which the library takes the stream kernel (n = 33)
-            assert names.count('conv3x3_mx_kernel<bf16>') == 2, names
+            # the label is the library's own launch plan: the matrix/auxiliary-wave kernel up to its 32-bit offset bound, the
+            # stream kernel behind it (n = 33), forward and data gradient
+            past_2g = n * c * h * w * 2 >= 0x7fffffff
+            assert names.count('conv3x3_stream_kernel<bf16>' if past_2g else 'conv3x3_mx_kernel<bf16>') == 2, names
     finally:
         del xd, wd, y
         torch.cuda.empty_cache()

@@ -139,7 +139,9 @@ def _conv_general_raw(x, wq, bias, residual, cout, k, stride, pad, mode, h_out, 
     n, cin, h, w = x.shape
     y = core.empty_nhwc(n, cout, h_out, w_out, out_dtype, x.device)
     flops = 2.0 * n * h_out * w_out * cout * cin * k * k
-    st = core._timed(core._fprop_kernel_name(x.dtype, wlayout, (n, h_out, w_out, cin, cout, act, out_dtype) if stride == 1 and mode != 2 else None), flops,
+    plain = stride == 1 and mode != 2 and pad == k // 2 and (h_out, w_out) == (h << mode, w << mode)
+    st = core._timed(*core._fprop_event(x, out_dtype, cout, k, mode == 1, act, wlayout, flops,
+                                        (1 if residual is not None else 0) | (0 if plain else 8)),
                 lambda: _native.lib().vqk_conv2d_general(core.dcode(x.dtype), x.data_ptr(), wq.data_ptr(), core._p(bias), core._p(residual),
                                                          y.data_ptr(), core.dcode(out_dtype), n, h, w, cin, cout, k, stride, pad,
                                                          mode, h_out, w_out, act, float(acc_scale), float(out_gain), wlayout,

@@ -1135,8 +1135,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_thin_in_kernel(const bf16_raw*
     }
 }
 
-static thread_local int g_force_variant = -1;   // test hook (per host thread: the library keeps no process-global mutable state): -1 auto, 0 im2col kernel only, 1 halo kernels when eligible,
-                                   // 5 never the matrix/auxiliary-wave kernel, 6 that kernel whenever it is eligible
+static thread_local int g_force_variant = CONV_VARIANT_AUTO;   // test hook (conv_geom.h: ConvVariant), per host thread: the library
+                                                               // keeps no process-global mutable state
 // deterministic mode (vqk_set_deterministic; the reference trains with deterministic=True, vqvae/train.py:130): split-K partials
 // go through this workspace and are summed in a fixed order, kernels without a workspace form run unsplit
 #define g_det (vqkd::det_state().on)
@@ -1145,19 +1145,22 @@ static thread_local int g_force_variant = -1;   // test hook (per host thread: t
 static thread_local int g_stream_blocks = 0;    // persistent-grid caps (0 = default 2 blocks per CU): 256 leaves half of every CU to a
 static thread_local int g_wgrad_blocks = 0;     // kernel running concurrently on another stream (dgrad || wgrad || GroupNorm)
 
-// 1x1 convs (the ResBlock shortcuts, autoencoder.py:52-55): the NTAP = 1 form of the matrix/auxiliary-wave kernel -- bf16, whole
-// 128-cout tiles, at least two 32-channel chunks, 32-bit buffer offsets
-inline bool mx_serves_1x1(const ConvGeom& g) {
-    const int mx_on = VQK_TUNE("MX", 1);
-    const int on = VQK_TUNE("MX_1X1", 1);
-    return mx_on && on && g_force_variant != 5 && (g.cout & 127) == 0 && (g.cpt >> 2) >= 2 && !g.ups &&
+// shapes of the matrix/auxiliary-wave kernel (conv_mx.hip): bf16, whole 128-cout tiles, at least two 32-channel chunks, 32-bit
+// buffer offsets
+inline bool mx_shape_ok(const ConvGeom& g, int variant) {
+    return VQK_TUNE("MX", 1) && variant != CONV_VARIANT_NO_MX && (g.cout & 127) == 0 && (g.cpt >> 2) >= 2 &&
            (int64_t)g.n * g.h_in * g.w_in * g.cin * 2 < 0x7fffffffLL && (int64_t)g.m * g.cout * 2 < 0x7fffffffLL;
 }
 
+// 1x1 convs (the ResBlock shortcuts, autoencoder.py:52-55): the NTAP = 1 form of that kernel
+inline bool mx_serves_1x1(const ConvGeom& g, int variant) {
+    return mx_shape_ok(g, variant) && VQK_TUNE("MX_1X1", 1) && !g.ups;
+}
+
 // 0: not eligible for the halo kernels; 5 / 4: patch width log2 (8x32 / 16x16 pixel patches)
-inline int halo_twlog(const ConvGeom& g) {
-    if ((g.ks != 3 && g.ks != 1) || (g.cpt % 8) != 0 || g_force_variant == 0) return 0;
-    if (g.ks == 1 && !mx_serves_1x1(g)) return 0;                // 1x1: only the matrix/auxiliary-wave kernel has a pixel-tile form
+inline int halo_twlog(const ConvGeom& g, int variant) {
+    if ((g.ks != 3 && g.ks != 1) || (g.cpt % 8) != 0 || variant == CONV_VARIANT_IM2COL) return 0;
+    if (g.ks == 1 && !mx_serves_1x1(g, variant)) return 0;       // 1x1: only the matrix/auxiliary-wave kernel has a pixel-tile form
     const int prefer16 = VQK_TUNE("TW16", 0);      // A/B: 16x16 patches where both fit
     if (prefer16 && (g.w % 16) == 0 && (g.h % 16) == 0) return 4;
     if ((g.w % 32) == 0 && (g.h % 8) == 0) return 5;
@@ -1165,163 +1168,218 @@ inline int halo_twlog(const ConvGeom& g) {
     return 0;
 }
 
-template <typename T, typename TO>
-int launch_fprop(const void* x, const void* w, const float* bias, const void* res, void* y, const void* zeros,
-                 const ConvGeom& g, int act, int wlayout, hipStream_t st) {
-    if constexpr (std::is_same<T, float>::value && std::is_same<TO, float>::value) {
-        // the edge convs in the fp32 modes (conv_thin_f32.hip): 4 channels on one side -- fp32 FMAs at memory speed instead of 7/8 padding
-        // on the matrix pipe
-        if (wlayout == 0 && g.ks == 3 && !g.ups && !g.zs && !g.sub && g.stride == 1 && g.pad == 1 && g.vh == g.h && g.vw == g.w &&
-            g_force_variant != 0) {
-            if (g.cout == 4 && (g.cin % 16) == 0 && (g.h % 8) == 0 && (g.w % 32) == 0)
-                return vqkd::launch_conv3x3_thin_out_f32((const float*)x, (const float*)w, bias, (const float*)res, (float*)y, g.n, g.h, g.w,
-                                                         g.cin, act, g.acc_scale, g.out_gain, st);
-            if (g.cin == 4 && (g.cout == 64 || g.cout == 128 || g.cout == 256) && !res && act == 0 && g.acc_scale == 1.0f &&
-                g.out_gain == 1.0f && g.w >= 4 && (g.w % 4) == 0 && (int64_t)(10) * (g.w + 2) * 16 <= 64 * 1024)
-                return vqkd::launch_conv3x3_thin_in_f32((const float*)x, (const float*)w, bias, (float*)y, g.n, g.h, g.w, g.cout, st);
-        }
+// the fused epilogues (2x2 pooling, GroupNorm sums of the output: vqk_conv2d_fprop_pooled / _gnstats) exist on the fragment-major
+// bf16 kernels with whole 128-cout tiles
+inline bool fused_epilogue_serves(const ConvGeom& g, int variant) {
+    return halo_twlog(g, variant) && (g.cout % 128) == 0 && variant != CONV_VARIANT_BREG && variant != CONV_VARIANT_PLAIN_WEIGHTS;
+}
+
+// the edge convs in the fp32 modes (conv_thin_f32.hip): 4 channels on one side -- fp32 FMAs at memory speed instead of 7/8 padding
+// on the matrix pipe.  Plain 3x3 convs on plain weights
+inline bool thin_f32_plain(const ConvGeom& g, int variant) {
+    return g.ks == 3 && !g.ups && !g.zs && !g.sub && g.stride == 1 && g.pad == 1 && g.vh == g.h && g.vw == g.w &&
+           variant != CONV_VARIANT_IM2COL;
+}
+inline bool thin_out_f32_serves(const ConvGeom& g, int variant) {
+    return thin_f32_plain(g, variant) && g.cout == 4 && (g.cin % 16) == 0 && (g.h % 8) == 0 && (g.w % 32) == 0;
+}
+inline bool thin_in_f32_serves(const ConvGeom& g, int variant, bool has_res, int act) {
+    return thin_f32_plain(g, variant) && g.cin == 4 && (g.cout == 64 || g.cout == 128 || g.cout == 256) && !has_res && act == 0 &&
+           g.acc_scale == 1.0f && g.out_gain == 1.0f && g.w >= 4 && (g.w % 4) == 0 && (int64_t)(10) * (g.w + 2) * 16 <= 64 * 1024;
+}
+
+// ---- the forward / data-gradient dispatch: plan_fprop decides and launches nothing, launch_fprop launches what it decided ----
+// The kernel forms.  The ids are part of the C-ABI (vqk_conv_fprop_plan returns them): append, never renumber.
+enum ConvForm : int {
+    FORM_THIN_OUT_F32 = 0,   // conv_thin_f32.hip: fp32, 4 output channels
+    FORM_THIN_IN_F32,        // conv_thin_f32.hip: fp32, 4 input channels
+    FORM_MX,                 // conv_mx.hip: matrix/auxiliary-wave kernel, 3x3
+    FORM_MX_1X1,             // ... its one-tap form (memory-bound)
+    FORM_STREAM_THIN,        // stream kernel, cout <= 32: one 32-wide cout tile, the waves split the pixels
+    FORM_STREAM_HALF,        // stream kernel, 128-pixel tiles (fewer 256-pixel tiles than CUs)
+    FORM_STREAM_FULL,        // stream kernel, 256-pixel tiles
+    FORM_HALO_BREG,          // register-weight halo kernel (fragment-major weights)
+    FORM_HALO_LDS,           // LDS-weight halo kernel (plain weights)
+    FORM_THIN_IN_BF16,       // bf16, one 16-byte chunk of input channels: one launch per 128 output channels (memory-bound)
+    FORM_IM2COL,             // the general kernel
+    FORM_IM2COL_SPLITK,      // ... with K split through the caller's scratch, then the epilogue kernel
+    FORM_X3,                 // conv_x3.hip: split-product kernel (layout 5; chosen by the caller, launched by conv_general)
+    FORM_X3_1X1,             // ... its one-tap form (memory-bound)
+    FORM_COUNT
+};
+
+struct FpropPlan {
+    int status;     // VQK_OK, or what the launcher returns instead of launching
+    int form;       // ConvForm
+    int tw;         // patch width log2 of the halo forms (5 / 4), else 0
+    int blocks;     // grid of the (first) launch; 0 where the form's own launcher sizes it (conv_mx / conv_x3 / conv_thin_f32.hip)
+    int splits;     // split-K parts (1: unsplit) ...
+    int sps;        // ... and k-steps per part
+    int launches;
+};
+
+// g carries the pooled epilogue / fused GroupNorm sums (g.pool, g.gn_ws) and the general-conv fields; `variant`: the calling
+// thread's hook, or CONV_VARIANT_IM2COL from a caller that needs the general kernel.  Reads the block caps, the tuning slots and
+// the thread's scratch; touches no device.
+FpropPlan plan_fprop(const ConvGeom& g, int dtype, int out_dtype, int act, int wlayout, bool has_res, int variant) {
+    FpropPlan p = {VQK_OK, FORM_IM2COL, 0, 0, 1, 0, 1};
+    auto refuse = [&](int status) { p.status = status; return p; };
+    auto take = [&](int form, int64_t blocks) { p.form = form; p.blocks = (int)blocks; return p; };
+    const bool bf_in = dtype == VQK_BF16, bf_out = out_dtype == VQK_BF16;
+    if (!bf_in && !bf_out && wlayout == 0) {
+        if (thin_out_f32_serves(g, variant)) return take(FORM_THIN_OUT_F32, 0);
+        if (thin_in_f32_serves(g, variant, has_res, act)) return take(FORM_THIN_IN_F32, 0);
     }
-    const int tw = halo_twlog(g);
-    if (wlayout == 1 && sizeof(T) == 2 && g_force_variant != 3) {
-        if (!tw) return VQK_ERR_SHAPE;
-        const int th = 256 >> tw;
-        const int total = g.n * (g.h / th) * (g.w >> tw) * g.tiles_n;
-        const int persist_env = VQK_TUNE("STREAM_BLOCKS", 512);
-        const int persist = g_stream_blocks > 0 ? g_stream_blocks : persist_env;
-        const dim3 grid((unsigned)(total < persist ? total : persist));
-        constexpr int lds = 2 * 28 * 1024;
-        const bool half_ok = tw == 5 ? (g.h % 4) == 0 : (g.h % 8) == 0;
-        if constexpr (sizeof(TO) == 2) {
-            // matrix-wave / auxiliary-wave kernel (conv_mx.hip): whole 128-cout tiles, plain epilogue (bias / residual /
-            // pooling).  The choice must not depend on the batch size (a step on B images has to equal the mean of the steps
-            // on its halves to bf16 noise -- the two kernels round differently), hence no tile-count threshold by default
-            const int mx_on = VQK_TUNE("MX", 1);
-            const int mx_min = VQK_TUNE("MX_MIN_TILES", 1);
-            // (bias / residual / pooling; relu or leaky relu with the StyleGAN2 gains: the VGG and discriminator convs)
-            const bool plain = (act == 0 || ((act == 2 || act == 3) && !g.pool && !g.gn_ws)) && (g.cout & 127) == 0;
-            const bool fits32 = (int64_t)g.n * g.h_in * g.w_in * g.cin * 2 < 0x7fffffffLL && (int64_t)g.m * g.cout * 2 < 0x7fffffffLL;
-            if (mx_on && g_force_variant != 5 && plain && fits32 && (g.cpt >> 2) >= 2 && (total >= mx_min || g_force_variant == 6 || g.ks == 1)) {
-                ConvGeom ga = g;
-                ga.act = act;
-                return vqkd::launch_conv3x3_mx(x, w, bias, res, y, zeros, ga, tw, st);
-            }
+    const int tw = p.tw = halo_twlog(g, variant);
+    const int tiles = tw ? g.n * (g.h / (256 >> tw)) * (g.w >> tw) * g.tiles_n : 0;      // 256-pixel patches x cout tiles
+    if (wlayout == 1 && bf_in && variant != CONV_VARIANT_BREG) {
+        if (!tw) return refuse(VQK_ERR_SHAPE);
+        // matrix-wave / auxiliary-wave kernel (conv_mx.hip): whole 128-cout tiles, plain epilogue (bias / residual / pooling;
+        // relu or leaky relu with the StyleGAN2 gains: the VGG and discriminator convs).  The choice must not depend on the
+        // batch size (a step on B images has to equal the mean of the steps on its halves to bf16 noise -- the two kernels
+        // round differently), hence no tile-count threshold by default
+        const bool plain = act == 0 || ((act == 2 || act == 3) && !g.pool && !g.gn_ws);
+        if (bf_out && plain && mx_shape_ok(g, variant) &&
+            (tiles >= VQK_TUNE("MX_MIN_TILES", 1) || variant == CONV_VARIANT_MX || g.ks == 1)) {
+            if (g.ks == 1 && g.pool) return refuse(VQK_ERR_ARG);    // (the one-tap form has no pooled drain)
+            return take(g.ks == 1 ? FORM_MX_1X1 : FORM_MX, 0);
         }
-        if (g.gn_ws || g.ks == 1) return VQK_ERR_SHAPE;          // fused statistics / 1x1 tiles exist on the matrix/auxiliary-wave kernel only
-        if (g.cout <= 32) {                                      // thin head: 32-wide cout tiles, waves split the pixels
-            ConvGeom gt = g;
-            gt.tiles_n = 1;
-            if (tw == 5)
-                hipLaunchKernelGGL((conv3x3_stream_kernel<TO, 5, 1>), grid, dim3(256), lds, st, (const bf16_raw*)x, (const bf16_raw*)w,
-                                   bias, (const TO*)res, (TO*)y, (const char*)zeros, gt, act);
-            else
-                hipLaunchKernelGGL((conv3x3_stream_kernel<TO, 4, 1>), grid, dim3(256), lds, st, (const bf16_raw*)x, (const bf16_raw*)w,
-                                   bias, (const TO*)res, (TO*)y, (const char*)zeros, gt, act);
-        } else if (total < 256 && half_ok && !g.pool && sizeof(TO) == 2 && g_force_variant != 4) {
-            // fewer 256-pixel tiles than CUs: 128-pixel tiles
-            const dim3 hgrid((unsigned)(2 * total < persist ? 2 * total : persist));
-            if (tw == 5)
-                hipLaunchKernelGGL((conv3x3_stream_kernel<TO, 5, 2>), hgrid, dim3(256), lds, st, (const bf16_raw*)x, (const bf16_raw*)w,
-                                   bias, (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-            else
-                hipLaunchKernelGGL((conv3x3_stream_kernel<TO, 4, 2>), hgrid, dim3(256), lds, st, (const bf16_raw*)x, (const bf16_raw*)w,
-                                   bias, (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        } else if (tw == 5)
-            hipLaunchKernelGGL((conv3x3_stream_kernel<TO, 5, 0>), grid, dim3(256), lds, st, (const bf16_raw*)x, (const bf16_raw*)w,
-                               bias, (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        else
-            hipLaunchKernelGGL((conv3x3_stream_kernel<TO, 4, 0>), grid, dim3(256), lds, st, (const bf16_raw*)x, (const bf16_raw*)w,
-                               bias, (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
-        return VQK_OK;
+        if (g.gn_ws || g.ks == 1) return refuse(VQK_ERR_SHAPE);     // fused statistics / 1x1 tiles exist on the matrix/auxiliary-wave kernel only
+        const int persist = g_stream_blocks > 0 ? g_stream_blocks : VQK_TUNE("STREAM_BLOCKS", 512);
+        const bool half_ok = tw == 5 ? (g.h % 4) == 0 : (g.h % 8) == 0;
+        if (g.cout <= 32) return take(FORM_STREAM_THIN, tiles < persist ? tiles : persist);
+        if (tiles < 256 && half_ok && !g.pool && bf_out && variant != CONV_VARIANT_NO_HALF)
+            return take(FORM_STREAM_HALF, 2 * tiles < persist ? 2 * tiles : persist);
+        return take(FORM_STREAM_FULL, tiles < persist ? tiles : persist);
     }
     if (wlayout == 1) {
-        if (!tw || g.ks == 1) return VQK_ERR_SHAPE;          // fragment-major weights need a halo-eligible shape
-        constexpr int lds = 11 * 4096;
-        const int th = 256 >> tw;
-        const dim3 grid((unsigned)(g.n * (g.h / th) * (g.w >> tw) * g.tiles_n));
-        if (tw == 5)
-            hipLaunchKernelGGL((conv3x3_halo_breg_kernel<T, TO, 5>), grid, dim3(256), lds, st, (const T*)x, (const T*)w,
-                               bias, (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        else
-            hipLaunchKernelGGL((conv3x3_halo_breg_kernel<T, TO, 4>), grid, dim3(256), lds, st, (const T*)x, (const T*)w,
-                               bias, (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
-        return VQK_OK;
+        if (!tw || g.ks == 1) return refuse(VQK_ERR_SHAPE);         // fragment-major weights need a halo-eligible shape
+        return take(FORM_HALO_BREG, tiles);
     }
-    if (tw && g.ks == 3) {
-        constexpr int lds = 11 * 4096 + 32768;
-        const int th = 256 >> tw;
-        const dim3 grid((unsigned)(g.n * (g.h / th) * (g.w >> tw) * g.tiles_n));
-        if (tw == 5) {
-            static const hipError_t attr5 = hipFuncSetAttribute((const void*)conv3x3_halo_kernel<T, TO, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)attr5;
-            hipLaunchKernelGGL((conv3x3_halo_kernel<T, TO, 5>), grid, dim3(256), lds, st, (const T*)x, (const T*)w, bias,
-                               (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        } else {
-            static const hipError_t attr4 = hipFuncSetAttribute((const void*)conv3x3_halo_kernel<T, TO, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)attr4;
-            hipLaunchKernelGGL((conv3x3_halo_kernel<T, TO, 4>), grid, dim3(256), lds, st, (const T*)x, (const T*)w, bias,
-                               (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-        }
-        if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
-        return VQK_OK;
+    if (tw && g.ks == 3) return take(FORM_HALO_LDS, tiles);
+    p.tw = 0;
+    if (bf_in && bf_out && wlayout == 0 && g.ks == 3 && g.cpt == 1 && !has_res && !g.ups && !g.zs && g.stride == 1 && g.pad == 1 &&
+        (g.w % 32) == 0 && (g.cout % 8) == 0 && g.vh == g.h && g.vw == g.w && variant != CONV_VARIANT_IM2COL) {
+        const int waves = g.n * g.h * (g.w >> 5);
+        p.launches = (g.cout + 127) / 128;
+        return take(FORM_THIN_IN_BF16, (waves + 3) / 4 > 1024 ? 1024 : (waves + 3) / 4);
     }
-    if (sizeof(T) == 2 && sizeof(TO) == 2 && wlayout == 0 && g.ks == 3 && g.cpt == 1 && !res && !g.ups && !g.zs &&
-        g.stride == 1 && g.pad == 1 && (g.w % 32) == 0 && (g.cout % 8) == 0 && g.vh == g.h && g.vw == g.w &&
-        g_force_variant != 0) {
-        const int total = g.n * g.h * (g.w >> 5);
-        int blocks = (total + 3) / 4; if (blocks > 1024) blocks = 1024;
+    // split-K through the caller's scratch (vqk_set_scratch) when the tile grid leaves most of the chip idle
+    // (this kernel runs one k-step at a time per block: below ~4 blocks per CU nothing hides its load -> LDS -> MFMA latency)
+    const vqkd::DetState& sc = vqkd::scratch_state();
+    const int grid = g.tiles_m * g.tiles_n, ksteps = (g.kchunks + 7) >> 3;
+    const int64_t out_elems = (int64_t)g.m * g.cout;
+    const int sk_blocks = VQK_TUNE("SK_BLOCKS", 2048), sk_minsteps = VQK_TUNE("SK_MINSTEPS", 4), sk_maxmb = VQK_TUNE("SK_MAXMB", 32);
+    int splits = grid * 2 <= sk_blocks ? sk_blocks / grid : 1;
+    if (splits > ksteps / sk_minsteps) splits = ksteps / sk_minsteps;
+    if ((int64_t)splits * out_elems * 4 > ((int64_t)sk_maxmb << 20)) splits = (int)(((int64_t)sk_maxmb << 20) / (out_elems * 4));
+    if (sc.ws && (int64_t)splits * out_elems * 4 > sc.bytes) splits = (int)(sc.bytes / (out_elems * 4));
+    if (VQK_TUNE("FPROP_SPLITK", 1) && sc.ws && (g.cout & 3) == 0 && splits >= 2) {
+        p.sps = (ksteps + splits - 1) / splits;
+        p.splits = (ksteps + p.sps - 1) / p.sps;
+        p.launches = 2;
+        return take(FORM_IM2COL_SPLITK, grid);
+    }
+    return take(FORM_IM2COL, grid);
+}
+
+// one helper per kernel template: the plan's patch width (or the whole-chunk flag of the im2col kernel) picks the instantiation
+template <typename TO, int MODE>
+void launch_stream(const FpropPlan& p, hipStream_t st, const void* x, const void* w, const float* bias, const void* res, void* y,
+                   const void* zeros, const ConvGeom& g, int act) {
+    auto kernel = p.tw == 5 ? conv3x3_stream_kernel<TO, 5, MODE> : conv3x3_stream_kernel<TO, 4, MODE>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.blocks), dim3(256), 2 * 28 * 1024, st, (const bf16_raw*)x, (const bf16_raw*)w, bias,
+                       (const TO*)res, (TO*)y, (const char*)zeros, g, act);
+}
+
+template <typename T, typename TO>
+void launch_halo_breg(const FpropPlan& p, hipStream_t st, const void* x, const void* w, const float* bias, const void* res, void* y,
+                      const void* zeros, const ConvGeom& g, int act) {
+    auto kernel = p.tw == 5 ? conv3x3_halo_breg_kernel<T, TO, 5> : conv3x3_halo_breg_kernel<T, TO, 4>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.blocks), dim3(256), 11 * 4096, st, (const T*)x, (const T*)w, bias, (const TO*)res,
+                       (TO*)y, (const char*)zeros, g, act);
+}
+
+template <typename T, typename TO, int TW>
+void launch_halo_lds(const FpropPlan& p, hipStream_t st, const void* x, const void* w, const float* bias, const void* res, void* y,
+                     const void* zeros, const ConvGeom& g, int act) {
+    constexpr int lds = 11 * 4096 + 32768;
+    static const hipError_t attr = hipFuncSetAttribute((const void*)conv3x3_halo_kernel<T, TO, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)attr;
+    hipLaunchKernelGGL((conv3x3_halo_kernel<T, TO, TW>), dim3((unsigned)p.blocks), dim3(256), lds, st, (const T*)x, (const T*)w, bias,
+                       (const TO*)res, (TO*)y, (const char*)zeros, g, act);
+}
+
+template <typename T, typename TO>
+void launch_im2col(const FpropPlan& p, hipStream_t st, const void* x, const void* w, const float* bias, const void* res, void* y,
+                   const void* zeros, const ConvGeom& g, int act, float* skws) {
+    auto kernel = (g.cpt % 8) == 0 ? conv_fprop_kernel<T, TO, true> : conv_fprop_kernel<T, TO, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)p.blocks, (unsigned)p.splits), dim3(256), 32768, st, (const T*)x, (const T*)w, bias,
+                       (const TO*)res, (TO*)y, (const char*)zeros, g, act, skws, p.sps);
+}
+
+template <typename T, typename TO>
+int launch_fprop(const void* x, const void* w, const float* bias, const void* res, void* y, const void* zeros,
+                 const ConvGeom& g, int act, int wlayout, int variant, hipStream_t st) {
+    const FpropPlan p = plan_fprop(g, sizeof(T) == 2 ? VQK_BF16 : VQK_F32, sizeof(TO) == 2 ? VQK_BF16 : VQK_F32, act, wlayout,
+                                   res != nullptr, variant);
+    if (p.status != VQK_OK) return p.status;
+    switch (p.form) {
+    case FORM_THIN_OUT_F32:
+        return vqkd::launch_conv3x3_thin_out_f32((const float*)x, (const float*)w, bias, (const float*)res, (float*)y, g.n, g.h, g.w,
+                                                 g.cin, act, g.acc_scale, g.out_gain, st);
+    case FORM_THIN_IN_F32:
+        return vqkd::launch_conv3x3_thin_in_f32((const float*)x, (const float*)w, bias, (float*)y, g.n, g.h, g.w, g.cout, st);
+    case FORM_MX:
+    case FORM_MX_1X1: {
+        ConvGeom ga = g;
+        ga.act = act;
+        return vqkd::launch_conv3x3_mx(x, w, bias, res, y, zeros, ga, p.tw, st);
+    }
+    case FORM_STREAM_THIN: {
+        ConvGeom gt = g;
+        gt.tiles_n = 1;
+        launch_stream<TO, 1>(p, st, x, w, bias, res, y, zeros, gt, act);
+        break;
+    }
+    case FORM_STREAM_HALF: launch_stream<TO, 2>(p, st, x, w, bias, res, y, zeros, g, act); break;
+    case FORM_STREAM_FULL: launch_stream<TO, 0>(p, st, x, w, bias, res, y, zeros, g, act); break;
+    case FORM_HALO_BREG: launch_halo_breg<T, TO>(p, st, x, w, bias, res, y, zeros, g, act); break;
+    case FORM_HALO_LDS:
+        if (p.tw == 5) launch_halo_lds<T, TO, 5>(p, st, x, w, bias, res, y, zeros, g, act);
+        else launch_halo_lds<T, TO, 4>(p, st, x, w, bias, res, y, zeros, g, act);
+        break;
+    case FORM_THIN_IN_BF16:
         for (int cb = 0; cb < g.cout; cb += 128) {
             if (g.cout - cb > 64)
-                hipLaunchKernelGGL((conv3x3_thin_in_kernel<4>), dim3((unsigned)blocks), dim3(256), 4 * 32 * (4 * 64 + 8) + 4 * 128, st,
+                hipLaunchKernelGGL((conv3x3_thin_in_kernel<4>), dim3((unsigned)p.blocks), dim3(256), 4 * 32 * (4 * 64 + 8) + 4 * 128, st,
                                    (const bf16_raw*)x, (const bf16_raw*)w, bias, (bf16_raw*)y, g, act, cb);
             else
-                hipLaunchKernelGGL((conv3x3_thin_in_kernel<2>), dim3((unsigned)blocks), dim3(256), 4 * 32 * (2 * 64 + 8) + 4 * 64, st,
+                hipLaunchKernelGGL((conv3x3_thin_in_kernel<2>), dim3((unsigned)p.blocks), dim3(256), 4 * 32 * (2 * 64 + 8) + 4 * 64, st,
                                    (const bf16_raw*)x, (const bf16_raw*)w, bias, (bf16_raw*)y, g, act, cb);
         }
-        if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
-        return VQK_OK;
+        break;
+    case FORM_IM2COL: launch_im2col<T, TO>(p, st, x, w, bias, res, y, zeros, g, act, nullptr); break;
+    case FORM_IM2COL_SPLITK: {
+        float* skws = vqkd::scratch_state().ws;
+        launch_im2col<T, TO>(p, st, x, w, bias, res, y, zeros, g, act, skws);
+        hipLaunchKernelGGL(conv_splitk_epilogue_kernel<TO>, dim3((unsigned)(((int64_t)g.m * g.cout / 4 + 255) / 256)), dim3(256), 0, st,
+                           skws, bias, (const TO*)res, (TO*)y, g, act, p.splits);
+        break;
     }
-    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
-    const bool fastk = (g.cpt % 8) == 0;
-    {
-        // split-K through the caller's scratch (vqk_set_scratch) when the tile grid leaves most of the chip idle
-        vqkd::DetState& sc = vqkd::scratch_state();
-        const int tiles = g.tiles_m * g.tiles_n, ksteps = (g.kchunks + 7) >> 3;
-        const int64_t out_elems = (int64_t)g.m * g.cout;
-        const int sk_on = VQK_TUNE("FPROP_SPLITK", 1);
-        // (this kernel runs one k-step at a time per block: below ~4 blocks per CU nothing hides its load -> LDS -> MFMA latency)
-        const int sk_blocks = VQK_TUNE("SK_BLOCKS", 2048);
-        const int sk_minsteps = VQK_TUNE("SK_MINSTEPS", 4);
-        const int sk_maxmb = VQK_TUNE("SK_MAXMB", 32);
-        int splits = tiles * 2 <= sk_blocks ? sk_blocks / tiles : 1;
-        if (splits > ksteps / sk_minsteps) splits = ksteps / sk_minsteps;
-        if ((int64_t)splits * out_elems * 4 > ((int64_t)sk_maxmb << 20)) splits = (int)(((int64_t)sk_maxmb << 20) / (out_elems * 4));
-        if (sc.ws && (int64_t)splits * out_elems * 4 > sc.bytes) splits = (int)(sc.bytes / (out_elems * 4));
-        if (sk_on && sc.ws && (g.cout & 3) == 0 && splits >= 2) {
-            const int sps = (ksteps + splits - 1) / splits;
-            splits = (ksteps + sps - 1) / sps;
-            const dim3 sgrid((unsigned)tiles, (unsigned)splits);
-            if (fastk)
-                hipLaunchKernelGGL((conv_fprop_kernel<T, TO, true>), sgrid, dim3(256), 32768, st, (const T*)x, (const T*)w, bias,
-                                   (const TO*)res, (TO*)y, (const char*)zeros, g, act, sc.ws, sps);
-            else
-                hipLaunchKernelGGL((conv_fprop_kernel<T, TO, false>), sgrid, dim3(256), 32768, st, (const T*)x, (const T*)w, bias,
-                                   (const TO*)res, (TO*)y, (const char*)zeros, g, act, sc.ws, sps);
-            hipLaunchKernelGGL(conv_splitk_epilogue_kernel<TO>, dim3((unsigned)((out_elems / 4 + 255) / 256)), dim3(256), 0, st, sc.ws, bias,
-                               (const TO*)res, (TO*)y, g, act, splits);
-            if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
-            return VQK_OK;
-        }
+    default: return VQK_ERR_ARG;
     }
-    if (fastk)
-        hipLaunchKernelGGL((conv_fprop_kernel<T, TO, true>), grid, dim3(256), 32768, st, (const T*)x, (const T*)w, bias,
-                           (const TO*)res, (TO*)y, (const char*)zeros, g, act);
-    else
-        hipLaunchKernelGGL((conv_fprop_kernel<T, TO, false>), grid, dim3(256), 32768, st, (const T*)x, (const T*)w, bias,
-                           (const TO*)res, (TO*)y, (const char*)zeros, g, act);
     if (hipGetLastError() != hipSuccess) return VQK_ERR_LAUNCH;
     return VQK_OK;
+}
+
+// the (dtype, out_dtype) pairs the kernels exist for
+int launch_fprop_any(int dtype, int out_dtype, const void* x, const void* w, const float* bias, const void* res, void* y,
+                     const void* zeros, const ConvGeom& g, int act, int wlayout, int variant, hipStream_t st) {
+    if (dtype == VQK_F32 && out_dtype == VQK_F32) return launch_fprop<float, float>(x, w, bias, res, y, zeros, g, act, wlayout, variant, st);
+    if (dtype == VQK_BF16 && out_dtype == VQK_BF16) return launch_fprop<bf16_raw, bf16_raw>(x, w, bias, res, y, zeros, g, act, wlayout, variant, st);
+    if (dtype == VQK_BF16 && out_dtype == VQK_F32) return launch_fprop<bf16_raw, float>(x, w, bias, res, y, zeros, g, act, wlayout, variant, st);
+    return VQK_ERR_DTYPE;
 }
 
 int make_geom(ConvGeom& g, int dtype, int n, int h_in, int w_in, int cin, int cout, int ksize, int ups) {
@@ -1364,7 +1422,7 @@ int& conv_wgrad_blocks() { return g_wgrad_blocks; }
 
 extern "C" {
 
-/* test / tuning hook: -1 automatic choice, 0 force the im2col kernel, 1 prefer the halo kernel */
+/* test / tuning hook: the values are conv_geom.h's ConvVariant (documented in include/vqk.h) */
 int vqk_conv_set_variant(int v) { g_force_variant = v; return VQK_OK; }
 int vqk_conv_set_block_caps(int stream_blocks, int wgrad_blocks) {
     g_stream_blocks = stream_blocks; g_wgrad_blocks = wgrad_blocks;
@@ -1406,10 +1464,8 @@ static int conv_general(int dtype, const void* x, const void* w, const float* bi
         VQK_REQUIRE(vqk_aligned16(y) && (!residual || vqk_aligned16(residual)), VQK_ERR_ALIGN);
         return vqkd::launch_conv3x3_x3(x, w, bias, residual, y, zeros, g, act, g_stream_blocks, st);
     }
-    if (mode == 2 && stride == 1 && g_force_variant != 5) {
-        // zero-stuffed input: one launch per output-parity class, each visiting only the taps that hit real samples
-        const int saved = g_force_variant;
-        g_force_variant = 0;
+    if (mode == 2 && stride == 1 && g_force_variant != CONV_VARIANT_NO_MX) {
+        // zero-stuffed input: one im2col launch per output-parity class, each visiting only the taps that hit real samples
         int r = VQK_OK;
         for (int py = 0; py < 2 && r == VQK_OK; ++py)
             for (int px = 0; px < 2 && r == VQK_OK; ++px) {
@@ -1426,24 +1482,13 @@ static int conv_general(int dtype, const void* x, const void* w, const float* bi
                 else gs.kchunks = gs.nkh * gs.nkw * gs.cpt;
                 gs.m = n * gs.sub_h * gs.sub_w;
                 gs.tiles_m = (gs.m + 127) / 128;
-                if (dtype == VQK_F32 && out_dtype == VQK_F32) r = launch_fprop<float, float>(x, w, bias, residual, y, zeros, gs, act, 0, st);
-                else if (dtype == VQK_BF16 && out_dtype == VQK_BF16) r = launch_fprop<bf16_raw, bf16_raw>(x, w, bias, residual, y, zeros, gs, act, 0, st);
-                else if (dtype == VQK_BF16 && out_dtype == VQK_F32) r = launch_fprop<bf16_raw, float>(x, w, bias, residual, y, zeros, gs, act, 0, st);
-                else r = VQK_ERR_DTYPE;
+                r = launch_fprop_any(dtype, out_dtype, x, w, bias, residual, y, zeros, gs, act, 0, CONV_VARIANT_IM2COL, st);
             }
-        g_force_variant = saved;
         return r;
     }
-    const int fv = plain ? -1 : 0;
-    const int saved = g_force_variant;
-    if (!plain) g_force_variant = 0;                        // force the general im2col kernel
-    int r = VQK_ERR_DTYPE;
-    if (dtype == VQK_F32 && out_dtype == VQK_F32) r = launch_fprop<float, float>(x, w, bias, residual, y, zeros, g, act, wlayout, st);
-    else if (dtype == VQK_BF16 && out_dtype == VQK_BF16) r = launch_fprop<bf16_raw, bf16_raw>(x, w, bias, residual, y, zeros, g, act, wlayout, st);
-    else if (dtype == VQK_BF16 && out_dtype == VQK_F32) r = launch_fprop<bf16_raw, float>(x, w, bias, residual, y, zeros, g, act, wlayout, st);
-    (void)fv;
-    g_force_variant = saved;
-    return r;
+    // strided / explicitly padded convs: the general im2col kernel
+    return launch_fprop_any(dtype, out_dtype, x, w, bias, residual, y, zeros, g, act, wlayout,
+                            plain ? g_force_variant : (int)CONV_VARIANT_IM2COL, st);
 }
 
 int vqk_conv2d_fprop(int dtype, const void* x, const void* w, const float* bias, const void* residual, void* y,
@@ -1464,9 +1509,9 @@ int vqk_conv2d_fprop_pooled(int dtype, const void* x, const void* w, const float
     ConvGeom g;
     const int rc = make_geom(g, dtype, n, h_in, w_in, cin, cout, ksize, ups);
     if (rc) return rc;
-    VQK_REQUIRE(halo_twlog(g) && (cout % 128) == 0 && g_force_variant != 3 && g_force_variant != 2, VQK_ERR_SHAPE);
+    VQK_REQUIRE(fused_epilogue_serves(g, g_force_variant), VQK_ERR_SHAPE);
     g.pool = 1; g.pool_scale = pool_scale;
-    return launch_fprop<bf16_raw, bf16_raw>(x, w, bias, residual, y, zeros, g, 0, 1, vqk_stream(stream));
+    return launch_fprop<bf16_raw, bf16_raw>(x, w, bias, residual, y, zeros, g, 0, 1, g_force_variant, vqk_stream(stream));
 }
 
 int vqk_conv2d_fprop_gnstats(int dtype, const void* x, const void* w, const float* bias, const void* residual, void* y,
@@ -1480,11 +1525,11 @@ int vqk_conv2d_fprop_gnstats(int dtype, const void* x, const void* w, const floa
     ConvGeom g;
     const int rc = make_geom(g, dtype, n, h_in, w_in, cin, cout, ksize, ups);
     if (rc) return rc;
-    VQK_REQUIRE(halo_twlog(g) && (cout % 128) == 0 && g_force_variant != 3 && g_force_variant != 2, VQK_ERR_SHAPE);
+    VQK_REQUIRE(fused_epilogue_serves(g, g_force_variant), VQK_ERR_SHAPE);
     g.pool = pool; g.pool_scale = pool ? pool_scale : 1.0f;
     g.gn_ws = gn_ws; g.gn_cpg = cout / groups;
     if (g_det) g.gn_part_nblk = (g.h * g.w) / 256;          // deterministic mode: one slot per 256-pixel tile of the image
-    return launch_fprop<bf16_raw, bf16_raw>(x, w, bias, residual, y, zeros, g, 0, 1, vqk_stream(stream));
+    return launch_fprop<bf16_raw, bf16_raw>(x, w, bias, residual, y, zeros, g, 0, 1, g_force_variant, vqk_stream(stream));
 }
 
 int vqk_conv2d_fprop_x3_gnstats(const float* x, const void* w5, const float* bias, const float* residual, float* y, int n, int h_in,
@@ -1512,7 +1557,7 @@ int vqk_conv2d_thin_in_gnstats(int dtype, const void* x, const void* w, const fl
     VQK_REQUIRE(n > 0 && h > 0 && wd > 0, VQK_ERR_SHAPE);
     // served: 128 output channels in 32 groups (4 channels per group), whole 32-pixel row segments, not in deterministic mode
     // (its per-tile slots exist on the role-split kernel only), and a wave count that splits evenly over images and over an image's tiles
-    VQK_REQUIRE(cout == 128 && groups == 32 && (wd % 32) == 0 && !g_det && g_force_variant != 0, VQK_ERR_SHAPE);
+    VQK_REQUIRE(cout == 128 && groups == 32 && (wd % 32) == 0 && !g_det && g_force_variant != CONV_VARIANT_IM2COL, VQK_ERR_SHAPE);
     ConvGeom g;
     const int rc = make_geom(g, dtype, n, h, wd, 8, cout, 3, 0);
     if (rc) return rc;
@@ -1587,10 +1632,10 @@ static int ups_phase_impl(int dtype, const void* x, const void* w4, const float*
     ConvGeom g;
     const int rc = make_geom(g, dtype, n, h, w, cin, cout, 3, 0);            // tiles over the LOW-resolution h x w grid
     if (rc) return rc;
-    const int tw = halo_twlog(g);
+    const int tw = halo_twlog(g, g_force_variant);
     const int mx_on = VQK_TUNE("MX", 1);
     const int ph_on = VQK_TUNE("UPS_PHASE", 1);
-    VQK_REQUIRE(tw && mx_on && ph_on && (cout % 128) == 0 && (g.cpt >> 2) >= 2 && g_force_variant != 5, VQK_ERR_SHAPE);
+    VQK_REQUIRE(tw && mx_on && ph_on && (cout % 128) == 0 && (g.cpt >> 2) >= 2 && g_force_variant != CONV_VARIANT_NO_MX, VQK_ERR_SHAPE);
     VQK_REQUIRE((int64_t)4 * g.m * (backward ? cin : cout) * 2 < 0x7fffffffLL && (int64_t)g.m * (backward ? cout : cin) * 2 < 0x7fffffffLL,
                 VQK_ERR_SHAPE);
     g.ntap = 4;
@@ -1646,7 +1691,7 @@ static int s2_twlog(int h_out, int w_out, int pix) {
 
 int vqk_conv2d_s2_supported(int dtype, int n, int h_out, int w_out, int cin, int cout, int backward) {
     if (dtype != VQK_BF16 || n <= 0 || h_out <= 0 || w_out <= 0 || cin <= 0 || cout <= 0) return 0;
-    if (!VQK_TUNE("MX", 1) || !VQK_TUNE("MX_S2", 1) || g_force_variant == 0 || g_force_variant == 5) return 0;
+    if (!VQK_TUNE("MX", 1) || !VQK_TUNE("MX_S2", 1) || g_force_variant == CONV_VARIANT_IM2COL || g_force_variant == CONV_VARIANT_NO_MX) return 0;
     const int64_t big = (int64_t)n * (2 * h_out + 1) * (2 * w_out + 1) * cin * 2, small = (int64_t)n * h_out * w_out * cout * 2;
     if (big >= 0x7fffffffLL || small >= 0x7fffffffLL) return 0;
     if (!backward) return (cin % 64) == 0 && (cout % 128) == 0 && s2_twlog(h_out, w_out, 128) != 0;
@@ -1703,8 +1748,6 @@ int vqk_conv2d_s2_dgrad(int dtype, const void* dy, const void* w3, const void* w
     e.zs = 1; e.vh = 2 * h_out - 1; e.vw = 2 * w_out - 1; e.stride = 1; e.pad = 2;
     e.h = H; e.w = W; e.m = n * H * W; e.tiles_m = (e.m + 127) / 128;
     e.acc_scale = acc_scale;
-    const int saved = g_force_variant;
-    g_force_variant = 0;
     const int edge[4][4] = {{2 * h_out, 1, 0, w_out + 1},        // {sub_py, sub_h, sub_px, sub_w}: row 2h, every even column
                             {0, h_out, 2 * w_out, 1},            // column 2w, the even rows above the corner
                             {2 * h_out, 1, 1, w_out},            // row 2h, odd columns
@@ -1720,9 +1763,8 @@ int vqk_conv2d_s2_dgrad(int dtype, const void* dy, const void* w3, const void* w
         gs.kchunks = gs.nkh * gs.nkw * gs.cpt;
         gs.m = n * gs.sub_h * gs.sub_w;
         gs.tiles_m = (gs.m + 127) / 128;
-        rc = launch_fprop<bf16_raw, bf16_raw>(dy, wt0, nullptr, nullptr, dx, zeros, gs, 0, 0, st);
+        rc = launch_fprop<bf16_raw, bf16_raw>(dy, wt0, nullptr, nullptr, dx, zeros, gs, 0, 0, CONV_VARIANT_IM2COL, st);
     }
-    g_force_variant = saved;
     return rc;
 }
 
@@ -1739,9 +1781,67 @@ int vqk_conv_weight_layout(int dtype, int n, int h_in, int w_in, int cin, int co
     const int rc = make_geom(g, dtype, n, h_in, w_in, cin, cout, ksize, ups);
     if (rc) return rc;
     if (ksize == 1 && dtype != VQK_BF16) return 0;
-    if (dtype == VQK_F32 && cout == 4 && ksize == 3 && !ups && (cin % 16) == 0 && (g.h % 8) == 0 && (g.w % 32) == 0 && g_force_variant != 0)
+    if (dtype == VQK_F32 && thin_out_f32_serves(g, g_force_variant))
         return 0;                                                // the 3-channel head in the fp32 modes: conv_thin_f32.hip (plain weights)
-    return (halo_twlog(g) && g_force_variant != 2) ? 1 : 0;
+    return (halo_twlog(g, g_force_variant) && g_force_variant != CONV_VARIANT_PLAIN_WEIGHTS) ? 1 : 0;
+}
+
+int vqk_conv_fprop_plan(int dtype, int out_dtype, int n, int h_in, int w_in, int cin, int cout, int ksize, int ups, int act,
+                        int wlayout, int flags, int* details) {
+    VQK_REQUIRE(act >= 0 && act <= 3 && (wlayout == 0 || wlayout == 1 || wlayout == 5) && (ups == 0 || ups == 1) &&
+                flags >= 0 && flags < 16, VQK_ERR_ARG);
+    const bool has_res = flags & 1, pool = flags & 2, gnstats = flags & 4, general = flags & 8;
+    if (pool || gnstats) {                                       // vqk_conv2d_fprop_pooled / _gnstats
+        VQK_REQUIRE(dtype == VQK_BF16 && out_dtype == VQK_BF16, VQK_ERR_DTYPE);
+        VQK_REQUIRE(act == 0 && wlayout == 1 && !general, VQK_ERR_ARG);
+        VQK_REQUIRE(!gnstats || ksize == 3, VQK_ERR_SHAPE);
+    }
+    ConvGeom g;
+    const int rc = make_geom(g, dtype, n, h_in, w_in, cin, cout, ksize, ups);
+    if (rc) return rc;
+    FpropPlan p = {VQK_OK, FORM_X3, 0, 0, 1, 0, 1};
+    if (wlayout == 5) {                                          // conv_general: the split-product kernel, plain convs only
+        VQK_REQUIRE(!general && dtype == VQK_F32 && out_dtype == VQK_F32, VQK_ERR_ARG);
+        VQK_REQUIRE(vqkd::conv3x3_x3_serves(g), VQK_ERR_SHAPE);
+        if (ksize == 1) p.form = FORM_X3_1X1;
+    } else {
+        VQK_REQUIRE(!general || wlayout == 0, VQK_ERR_ARG);
+        VQK_REQUIRE(out_dtype == VQK_F32 || (out_dtype == VQK_BF16 && dtype == VQK_BF16), VQK_ERR_DTYPE);
+        if (pool || gnstats) {
+            VQK_REQUIRE(fused_epilogue_serves(g, g_force_variant), VQK_ERR_SHAPE);
+            g.pool = pool;
+            if (gnstats) g.gn_ws = reinterpret_cast<double*>(sizeof(double));   // "present": a plan never dereferences it
+        }
+        p = plan_fprop(g, dtype, out_dtype, act, wlayout, has_res, general ? (int)CONV_VARIANT_IM2COL : g_force_variant);
+        if (p.status != VQK_OK) return p.status;
+    }
+    if (details) {
+        const bool membound = p.form == FORM_THIN_OUT_F32 || p.form == FORM_THIN_IN_F32 || p.form == FORM_MX_1X1 ||
+                              p.form == FORM_THIN_IN_BF16 || p.form == FORM_X3_1X1;
+        details[0] = p.tw; details[1] = p.blocks; details[2] = p.splits; details[3] = p.launches; details[4] = membound;
+    }
+    return p.form;
+}
+
+const char* vqk_conv_fprop_form_name(int form, int dtype) {
+    static const char* const names[FORM_COUNT][2] = {
+        {"conv3x3_thin_out_f32_kernel (HBM)", "conv3x3_thin_out_f32_kernel (HBM)"},
+        {"conv3x3_thin_in_f32_kernel (HBM)", "conv3x3_thin_in_f32_kernel (HBM)"},
+        {"conv3x3_mx_kernel<bf16>", "conv3x3_mx_kernel<bf16>"},
+        {"conv1x1_mx_kernel<bf16> (HBM)", "conv1x1_mx_kernel<bf16> (HBM)"},
+        {"conv3x3_stream_kernel<bf16>", "conv3x3_stream_kernel<bf16>"},
+        {"conv3x3_stream_kernel<bf16>", "conv3x3_stream_kernel<bf16>"},
+        {"conv3x3_stream_kernel<bf16>", "conv3x3_stream_kernel<bf16>"},
+        {"conv3x3_halo_breg_kernel<f32>", "conv3x3_halo_breg_kernel<bf16>"},
+        {"conv3x3_halo_kernel<f32>", "conv3x3_halo_kernel<bf16>"},
+        {"conv3x3_thin_in_kernel<bf16> (HBM)", "conv3x3_thin_in_kernel<bf16> (HBM)"},
+        {"conv_fprop_kernel<f32>", "conv_fprop_kernel<bf16>"},
+        {"conv_fprop_kernel<f32>", "conv_fprop_kernel<bf16>"},
+        {"conv3x3_x3_kernel<f32 as 3 x bf16>", "conv3x3_x3_kernel<f32 as 3 x bf16>"},
+        {"conv1x1_x3_kernel<f32 as 3 x bf16> (HBM)", "conv1x1_x3_kernel<f32 as 3 x bf16> (HBM)"},
+    };
+    if (form < 0 || form >= FORM_COUNT || (dtype != VQK_F32 && dtype != VQK_BF16)) return "?";
+    return names[form][dtype == VQK_BF16];
 }
 
 }  // extern "C"

@@ -89,10 +89,24 @@ int launch_conv3x3_mx(const void* x, const void* w, const float* bias, const voi
 // conv.hip <-> conv_wgrad.hip: the geometry builder and the per-host-thread launch state (test hook vqk_conv_set_variant, the
 // weight-gradient grid cap of vqk_conv_set_block_caps)
 int conv_make_geom(ConvGeom& g, int dtype, int n, int h_in, int w_in, int cin, int cout, int ksize, int ups);
+}  // namespace vqkd
+// the values of vqk_conv_set_variant (include/vqk.h): what each one forces on the calling thread's conv launches
+enum ConvVariant : int {
+    CONV_VARIANT_AUTO = -1,          // nothing: the launchers' own choice
+    CONV_VARIANT_IM2COL = 0,         // the general kernels only: im2col forward / data gradient, general weight gradient
+    CONV_VARIANT_HALO = 1,           // the halo kernels where eligible (what the automatic choice does)
+    CONV_VARIANT_PLAIN_WEIGHTS = 2,  // the layout query answers 0: LDS-weight halo kernel, no fused pooling / GroupNorm sums
+    CONV_VARIANT_BREG = 3,           // bf16 layout-1 convs on the register-weight halo kernel, not the stream / matrix-wave kernels
+    CONV_VARIANT_NO_HALF = 4,        // stream kernel without its 128-pixel half-tile form
+    CONV_VARIANT_NO_MX = 5,          // never the matrix/auxiliary-wave kernel (nor its 1x1, phase and stride-2 forms)
+    CONV_VARIANT_MX = 6,             // that kernel whenever the shape is eligible, below MX_MIN_TILES too
+};
+namespace vqkd {
 int& conv_force_variant();
 int& conv_wgrad_blocks();
 
 // split-product 3x3 conv (conv_x3.hip): fp32 in / out, three bf16 products per multiply-add; weights in layout 5
+bool conv3x3_x3_serves(const ConvGeom& g);   // the shapes the launcher takes (the rest: VQK_ERR_SHAPE)
 int launch_conv3x3_x3(const void* x, const void* w, const float* bias, const void* res, void* y, const void* zeros,
                       const ConvGeom& g, int act, int blocks_cap, hipStream_t st);
 // ... and its weight gradient straight from the fp32 tensors (no pair tensors): fp32 atomics into dw

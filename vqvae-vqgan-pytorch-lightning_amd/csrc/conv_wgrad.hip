@@ -658,7 +658,7 @@ __global__ __launch_bounds__(256) void wgrad_split_reduce_kernel(const float* __
 }
 
 // per-thread launch state shared with conv.hip (test hook, deterministic mode, grid cap beside a concurrent kernel)
-#define g_force_variant (vqkd::conv_force_variant())
+#define g_general_only (vqkd::conv_force_variant() == CONV_VARIANT_IM2COL)   // vqk_conv_set_variant(0): no fast path
 #define g_wgrad_blocks (vqkd::conv_wgrad_blocks())
 #define g_det (vqkd::det_state().on)
 #define g_det_ws (vqkd::det_state().ws)
@@ -695,10 +695,10 @@ static int wgrad_general(int dtype, const void* x, const void* dy, float* dw, in
     if (fold) {
         // (hi | lo) pair operands of the split-product mode: only the matrix/auxiliary-wave kernel has the folded tile classes
         VQK_REQUIRE(plain && dtype == VQK_BF16 && ksize == 3 && (g.h % 8) == 0 && (g.w % 16) == 0 && (cin % 128) == 0 && (cout % 128) == 0
-                    && !dy_pool && !g_det && g_force_variant != 0 && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
+                    && !dy_pool && !g_det && !g_general_only && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
                     && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
     }
-    if (plain && dtype == VQK_BF16 && ksize == 3 && (g.h % 8) == 0 && (g.w % 8) == 0 && g_force_variant != 0) {
+    if (plain && dtype == VQK_BF16 && ksize == 3 && (g.h % 8) == 0 && (g.w % 8) == 0 && !g_general_only) {
         const int tiles = fold ? 3 * (cout / 128) * (cin / 128) : ((cout + 63) / 64) * ((cin + 63) / 64);
         const bool no_pw16 = VQK_TUNE("WGRAD_NO_PW16", 0) != 0;
         const bool pw16 = (g.w % 16) == 0 && !no_pw16;
@@ -767,7 +767,7 @@ static int wgrad_general(int dtype, const void* x, const void* dy, float* dw, in
         VQK_CHECK_LAUNCH();
         return VQK_OK;
     }
-    if (plain && dtype == VQK_F32 && ksize == 3 && mode == 0 && !g_det && !dy_pool && g_force_variant != 0 && (g.w % 4) == 0 &&
+    if (plain && dtype == VQK_F32 && ksize == 3 && mode == 0 && !g_det && !dy_pool && !g_general_only && (g.w % 4) == 0 &&
         vqkd::thin_wgrad_rows(g.h, g.w) > 0) {
         // the edge convs' weight gradients in the fp32 modes (conv_thin_f32.hip); maps too wide for one staged row in LDS take the
         // general kernel below
@@ -861,7 +861,7 @@ static int wgrad_group_plan(const vqk_wgrad_item* it, int n, int* splits, int* p
 static int wgrad_group_check(const vqk_wgrad_item* items, int n_items) {
     VQK_REQUIRE(items && n_items >= 1, VQK_ERR_ARG);
     // the ordered-workspace path of deterministic mode belongs to the one-layer launch; so do the test hook and the A/B slots
-    VQK_REQUIRE(!g_det && g_force_variant != 0 && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
+    VQK_REQUIRE(!g_det && !g_general_only && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
                 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
     for (int i = 0; i < n_items; ++i) {
         const vqk_wgrad_item& q = items[i];
@@ -932,7 +932,7 @@ int vqk_conv2d_wgrad_x3_f32(const float* x, const float* dy, float* dw, int n, i
     VQK_REQUIRE(x && dy && dw, VQK_ERR_ARG);
     VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy), VQK_ERR_ALIGN);
     VQK_REQUIRE(ups == 0 || ups == 1 || ups == 2, VQK_ERR_ARG);
-    VQK_REQUIRE(!g_det && g_force_variant != 0, VQK_ERR_SHAPE);      // atomics only: deterministic mode keeps the exact-fp32 kernel
+    VQK_REQUIRE(!g_det && !g_general_only, VQK_ERR_SHAPE);      // atomics only: deterministic mode keeps the exact-fp32 kernel
     ConvGeom g;
     if (ups == 2 || (ups == 1 && VQK_TUNE("X3_WGRAD_PHASE", 1) && (h_in % 8) == 0 && (w_in % 8) == 0)) {
         // the 2x2-resampling convs in phase form (4/9 of the MFMAs): patches over the LOW-resolution grid.  ups = 1: x [n][h_in][w_in] is
@@ -964,7 +964,7 @@ int vqk_conv2d_wgrad_pooled_dy(int dtype, const void* x, const void* dy_pooled, 
                                int cout, float scale, const void* zeros, void* stream) {
     VQK_REQUIRE(dtype == VQK_BF16 && (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
     const int wgmx = VQK_TUNE("WGMX", 1);
-    VQK_REQUIRE(wgmx && g_force_variant != 0 && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
+    VQK_REQUIRE(wgmx && !g_general_only && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
     return wgrad_general(dtype, x, dy_pooled, dw, n, h, w, cin, cout, 3, 1, 1, 0, h, w, zeros, stream, 1, scale);
 }
 
@@ -972,7 +972,7 @@ int vqk_conv2d_wgrad_ups_phase(int dtype, const void* x, const void* dy, float* 
                                 float scale, const void* zeros, void* stream) {
     VQK_REQUIRE(dtype == VQK_BF16 && (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
     const int wgmx = VQK_TUNE("WGMX", 1);
-    VQK_REQUIRE(wgmx && g_force_variant != 0 && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0 && !g_det,
+    VQK_REQUIRE(wgmx && !g_general_only && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0 && !g_det,
                 VQK_ERR_SHAPE);
     if (VQK_TUNE("UPS_MERGE", 1))                                // the four output phases as ONE launch (phase = a dimension of the grid)
         return wgrad_general(dtype, x, dy, dw, n, h, w, cin, cout, 3, 1, 1, 0, h, w, zeros, stream, 6, scale);
@@ -990,7 +990,7 @@ int vqk_conv2d_wgrad_pooled_dy_phase(int dtype, const void* x, const void* dy_po
     // channels), its phase-gathered "dy" operand is x (cin channels); h, w: the POOLED grid.
     VQK_REQUIRE(dtype == VQK_BF16 && (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
     const int wgmx = VQK_TUNE("WGMX", 1);
-    VQK_REQUIRE(wgmx && g_force_variant != 0 && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0 && !g_det &&
+    VQK_REQUIRE(wgmx && !g_general_only && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0 && !g_det &&
                 VQK_TUNE("UPS_MERGE", 1) != 0, VQK_ERR_SHAPE);
     return wgrad_general(dtype, dy_pooled, x, dw, n, h, w, cout, cin, 3, 1, 1, 0, h, w, zeros, stream, 7, scale);
 }

@@ -606,9 +606,13 @@ __global__ __launch_bounds__(256) void split_pair_kernel(const float* __restrict
 namespace vqkd {
 
 // x fp32 [N, h_in, w_in, Cin], w: layout 5, y fp32 [N, h, w, Cout]; Cin % 32 == 0, h % 8 == 0, w % 16 == 0
+bool conv3x3_x3_serves(const ConvGeom& g) {
+    return (g.ks == 3 || g.ks == 1) && !(g.cin & 31) && !(g.h & 7) && !(g.w & 15) && !(g.cout & 3) && !(g.ks == 1 && g.ups);
+}
+
 int launch_conv3x3_x3(const void* x, const void* w, const float* bias, const void* res, void* y, const void* zeros,
                       const ConvGeom& g, int act, int blocks_cap, hipStream_t st) {
-    if ((g.ks != 3 && g.ks != 1) || (g.cin & 31) || (g.h & 7) || (g.w & 15) || (g.cout & 3) || (g.ks == 1 && g.ups)) return VQK_ERR_SHAPE;
+    if (!conv3x3_x3_serves(g)) return VQK_ERR_SHAPE;
     const int total = g.n * (g.h / 8) * (g.w / 16) * g.tiles_n * ((g.ntap == 4 && g.phase_mode == 1) ? 4 : 1);
     const int cap = blocks_cap > 0 ? blocks_cap : 512;
     const dim3 grid((unsigned)(total < cap ? total : cap));

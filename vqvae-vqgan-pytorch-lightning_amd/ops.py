@@ -231,33 +231,33 @@ def _timed(name: str, flops: float, launch, nbytes: float = 0.0, launches: int =
 
 _MX_ON = _native.switch('VQK_MX', '1') != '0'
 _THIN_OUT = _native.switch('VQK_THIN_OUT', '1') != '0'
-_MX_MIN_TILES = int(_native.switch('VQK_MX_MIN_TILES', '1'))
 _WGMX_ON = _native.switch('VQK_WGMX', '1') != '0'
 _UPS_MERGE = _native.switch('VQK_UPS_MERGE', '1') != '0'      # (the library's tuning slot of the same name: one launch per phase-form conv)
 
 
-def _fprop_kernel_name(dtype, wlayout: int, shape=None) -> str:
-    """the kernel symbol the launcher picks (csrc/conv.hip::launch_fprop), for the per-kernel event statistics;
-    shape = (n, h_out, w_out, cin, cout, act, out_dtype) lets it tell the matrix/auxiliary-wave kernel from the stream kernel"""
-    name = _fprop_kernel_name0(dtype, wlayout, shape)
-    if _EVENT_SHAPES and shape is not None:                      # tooling (tools/per_shape.py): one line per layer shape
-        name += f' {shape[3]}->{shape[4]}@{shape[1]}x{shape[2]}'
-    return name
+_X3_NAME = 'conv3x3_x3_kernel<f32 as 3 x bf16>'      # the split-product entry points that launch no other kernel (csrc/conv_x3.hip)
 
 
-def _fprop_kernel_name0(dtype, wlayout: int, shape=None) -> str:
-    if wlayout == 5:
-        return 'conv3x3_x3_kernel<f32 as 3 x bf16>'
-    if wlayout == 1:
-        if dtype != torch.bfloat16:
-            return 'conv3x3_halo_breg_kernel<f32>'
-        if shape is not None and _MX_ON:
-            n, ho, wo, cin, cout, act, odt = shape
-            if (act in (0, 2, 3) and odt == torch.bfloat16 and cout % 128 == 0 and cin >= 64
-                    and n * ho * wo // 256 * (cout // 128) >= _MX_MIN_TILES):
-                return 'conv3x3_mx_kernel<bf16>'
-        return 'conv3x3_stream_kernel<bf16>'
-    return f'conv_fprop_kernel<{"f32" if dtype == torch.float32 else "bf16"}>'
+def _fprop_event(x, out_dtype, cout: int, ksize: int, ups, act: int, wlayout: int, flops: float, flags: int = 0):
+    """(label, FLOPs) of a forward / data-gradient conv for the per-kernel event statistics: the kernel the library's own launch
+    plan names (vqk_conv_fprop_plan; flags: 1 residual, 2 pooled, 4 GroupNorm sums, 8 strided / zero-stuffed), a memory-bound
+    form with 0 FLOPs (reported by its bytes).  Nothing is asked or formatted unless events are being recorded."""
+    if KERNEL_EVENTS is None:
+        return '', flops
+    n, cin, h, w = x.shape
+    details = (ctypes.c_int * 5)()
+    form = _native.lib().vqk_conv_fprop_plan(dcode(x.dtype), dcode(out_dtype), n, h, w, cin, cout, ksize, int(ups), act, wlayout,
+                                             flags, details)
+    name = _native.lib().vqk_conv_fprop_form_name(form, dcode(x.dtype)).decode()
+    if _EVENT_SHAPES and not flags & 8:                          # tooling (tools/per_shape.py): one line per layer shape
+        name += f' {cin}->{cout}@{h << int(ups)}x{w << int(ups)}'
+    return name, (0.0 if details[4] else flops)
+
+
+def _thin_out_bf16(dtype, out_dtype, cin, cout, ksize, ups, h, w) -> bool:
+    """the decoder's last conv: 8 output channels on 16x16x32 MFMAs (vqk_conv2d_thin_out, csrc/conv_edge.hip; plain weights)"""
+    return (_THIN_OUT and ksize == 3 and not ups and dtype == torch.bfloat16 and out_dtype in (None, torch.bfloat16)
+            and cin == 128 and cout == 8 and h % 8 == 0 and w % 32 == 0)
 
 
 
@@ -269,9 +269,8 @@ def weight_layout(dtype, n, h_in, w_in, cin, cout, ksize, ups, out_dtype=None, x
         return 5                                   # split products on the bf16 matrix pipe (csrc/conv_x3.hip)
     if ksize == 1 and (dtype != torch.bfloat16 or (out_dtype is not None and out_dtype != torch.bfloat16)):
         return 0
-    if (_THIN_OUT and ksize == 3 and not ups and dtype == torch.bfloat16 and out_dtype in (None, torch.bfloat16)
-            and cin == 128 and cout == 8 and h_in % 8 == 0 and w_in % 32 == 0):
-        return 0                                   # the decoder's last conv: plain weights for vqk_conv2d_thin_out
+    if _thin_out_bf16(dtype, out_dtype, cin, cout, ksize, ups, h_in, w_in):
+        return 0                                   # plain weights for vqk_conv2d_thin_out
     r = _native.lib().vqk_conv_weight_layout(dcode(dtype), n, h_in, w_in, cin, cout, ksize, int(ups))
     if r < 0:
         _native.check(r, 'conv_weight_layout')
@@ -522,28 +521,14 @@ def raw_conv_fprop(x, wq, bias, residual, ksize: int, ups: bool, act: int, out_d
     flops = 2.0 * n * h * s * w * s * cout * cin * ksize * ksize
     nbytes = (x.numel() * x.element_size() + y.numel() * y.element_size() * (2 if residual is not None else 1)
               + cout * cin * ksize * ksize * x.element_size())
-    if (_THIN_OUT and x.dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and ksize == 3 and not ups and wlayout == 0
-            and residual is None and act in (0, 1) and cin == 128 and cout == 8 and h % 8 == 0 and w % 32 == 0):
-        # the decoder's last conv: 8 output channels on 16x16x32 MFMAs (csrc/conv_edge.hip)
+    if _thin_out_bf16(x.dtype, out_dtype, cin, cout, ksize, ups, h, w) and wlayout == 0 and residual is None and act in (0, 1):
         st = _timed('conv3x3_thin_out_kernel<bf16> (HBM)' + (f' {cin}->{cout}@{h}x{w}' if _EVENT_SHAPES else ''), 0.0,
                     lambda: _native.lib().vqk_conv2d_thin_out(dcode(x.dtype), x.data_ptr(), wq.data_ptr(), _p(bias), y.data_ptr(),
                                                               n, h, w, cin, cout, act, zero_page(x.device).data_ptr(), _stream()),
                     x.numel() * 2 + y.numel() * 2)
         _native.check(st, 'conv2d_thin_out')
         return y
-    kname = _fprop_kernel_name(x.dtype, wlayout, (n, h * s, w * s, cin, cout, act, out_dtype))
-    if (x.dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and wlayout == 0 and ksize == 3 and cin == 8 and residual is None
-            and not ups and w % 32 == 0 and cout % 8 == 0):
-        # one 16-byte chunk of input channels (the padded 3-channel image): csrc/conv.hip::launch_fprop takes the
-        # thin-input kernel -- it writes 2 * Cout bytes per pixel at memory speed: an HBM line, not an MFMA one
-        kname, flops = kname.replace('conv_fprop_kernel<bf16>', 'conv3x3_thin_in_kernel<bf16> (HBM)'), 0.0
-        nbytes = x.numel() * 2 + y.numel() * 2
-    if ksize == 1 and wlayout == 5:
-        # the NTAP = 1 form of the split-product kernel: fp32 in + out at memory speed -- an HBM line like the bf16 1x1 form
-        kname, flops = 'conv1x1_x3_kernel<f32 as 3 x bf16> (HBM)' + (f' {cin}->{cout}@{h}x{w}' if _EVENT_SHAPES else ''), 0.0
-    if ksize == 1 and kname.startswith('conv3x3_mx_kernel'):
-        # the NTAP = 1 instantiation (ResBlock shortcuts): memory-bound, reported with its bytes like the GroupNorm passes
-        kname, flops = kname.replace('conv3x3_mx_kernel<bf16>', 'conv1x1_mx_kernel<bf16> (HBM)'), 0.0
+    kname, flops = _fprop_event(x, out_dtype, cout, ksize, ups, act, wlayout, flops, 1 if residual is not None else 0)
     st = _timed(kname, flops,
                 lambda: _native.lib().vqk_conv2d_fprop(dcode(x.dtype), x.data_ptr(), wq.data_ptr(), _p(bias),
                                                        _p(residual), y.data_ptr(), dcode(out_dtype), n, h, w, cin,
@@ -569,7 +554,7 @@ def raw_conv_fprop_pooled(x, wq, bias, residual, ksize: int, ups: bool, cout: in
     nbytes = (x.numel() * x.element_size() + y.numel() * y.element_size()
               + (residual.numel() * residual.element_size() if residual is not None else 0)
               + cout * cin * ksize * ksize * x.element_size())
-    st = _timed(_fprop_kernel_name(x.dtype, 1, (n, h * s, w * s, cin, cout, 0, x.dtype)), flops,
+    st = _timed(*_fprop_event(x, x.dtype, cout, ksize, ups, 0, 1, flops, 2 | (1 if residual is not None else 0)),
                 lambda: _native.lib().vqk_conv2d_fprop_pooled(dcode(x.dtype), x.data_ptr(), wq.data_ptr(), _p(bias),
                                                               _p(residual), y.data_ptr(), n, h, w, cin, cout, ksize,
                                                               int(ups), float(pool_scale),
@@ -608,7 +593,7 @@ def raw_conv_fprop_gnstats(x, wq, bias, residual, ups: bool, cout: int, groups: 
     if x3:
         # split-product mode: fp32 sums of the fp32 output from the accumulators (csrc/conv_x3.hip)
         nbytes = x.numel() * 4 + y.numel() * 4 * (2 if residual is not None else 1) + cout * cin * 9 * 4
-        st = _timed(_fprop_kernel_name(x.dtype, 5), flops,
+        st = _timed(_X3_NAME, flops,
                     lambda: _native.lib().vqk_conv2d_fprop_x3_gnstats(x.data_ptr(), wq.data_ptr(), _p(bias), _p(residual), y.data_ptr(), n, h, w,
                                                                       cin, cout, int(ups), ws.data_ptr(), groups,
                                                                       zero_page(x.device).data_ptr(), _stream()), nbytes, exec_flops=3.0 * flops)
@@ -618,7 +603,7 @@ def raw_conv_fprop_gnstats(x, wq, bias, residual, ups: bool, cout: int, groups: 
         return y
     nbytes = (x.numel() * x.element_size() + y.numel() * y.element_size()
               + (residual.numel() * residual.element_size() if residual is not None else 0) + cout * cin * 9 * x.element_size())
-    st = _timed(_fprop_kernel_name(x.dtype, 1, (n, h * s, w * s, cin, cout, 0, x.dtype)), flops,
+    st = _timed(*_fprop_event(x, x.dtype, cout, 3, ups, 0, 1, flops, 4 | (2 if pool else 0) | (1 if residual is not None else 0)),
                 lambda: _native.lib().vqk_conv2d_fprop_gnstats(dcode(x.dtype), x.data_ptr(), wq.data_ptr(), _p(bias),
                                                                _p(residual), y.data_ptr(), n, h, w, cin, cout, 3, int(ups),
                                                                int(pool), float(pool_scale), ws.data_ptr(), groups,
@@ -676,7 +661,7 @@ def _phase_gn_ok(x, cout: int, gn_groups: int) -> bool:
 
 
 def _phase_name(dtype) -> str:
-    return 'conv3x3_mx_kernel<bf16>' if dtype == torch.bfloat16 else _fprop_kernel_name(dtype, 5)
+    return 'conv3x3_mx_kernel<bf16>' if dtype == torch.bfloat16 else _X3_NAME
 
 
 def raw_conv_ups_phase(x, wq4, bias, cout: int, backward: bool, gn_groups: int = 0):
