@@ -306,6 +306,42 @@ int64_t vqk_cos_backward_ws_bytes(int64_t n, int d);
 int vqk_cos_backward_f32(const float* z, const void* ws, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
                          float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws2,
                          int64_t ws2_bytes, void* stream);
+/* ---------------------------------------------------------------- grouped quantizer ---------
+ * Product (multi-codebook) quantization (csrc/gvq.hip): the D = G d channels of a row are cut into G contiguous groups of d, group g
+ * is looked up in its OWN codebook of K codes.  z[N][D] fp32 rows; e[G K][d] fp32, row g K + k = code k of group g; tokens
+ * idx[N][G] int64, group fastest.  Per (row, group): idx = argmin_k (|z_rg|^2 + |e_gk|^2) - 2 z_rg.e_gk with the arithmetic of
+ * vqk_row_sqnorm_f32 / vqk_vq_assign_f32 (assoc 0) on the contiguous [N, d] slice and the [K, d] slab, first minimum wins;
+ * q[r][g d .. (g + 1) d) = e[g K + idx]; sse = sum |q - z|^2; loss = (1 + beta) / (N D) sse; hist[g K + idx] += 1 (hist[G K] int32).
+ * Backward: dz = dq + s cz (z - q); de[g K + k] += s ce sum_{r: idx[r, g] = k} (e_gk - z_rg), cz = 2 beta / (N D), ce = 2 / (N D),
+ * s = *gscale_dev -- on the flat view [N G][d] with global code ids this is the standard quantizer's backward.  G = 1 is the standard
+ * quantizer.  1 <= groups <= 16, n < 2^31, k < 2^22 (VQK_ERR_SHAPE otherwise, nothing launched).  No call allocates or synchronises.
+ * forward: ONE launch, grid (ceil(n / 32), groups) -- block (b, g) stages group g's columns of its 32 rows in LDS, takes |z_rg|^2
+ * there, ranks against slab g streamed from L2, gathers into the strided slot and reduces; equal to `groups` times
+ * (vqk_row_sqnorm_f32 + vqk_vq_assign_f32 + vqk_vq_gather_f32) on contiguous copies of the slices in idx, q and hist, bit for bit.
+ * e2 = |e|^2[G K] from vqk_row_sqnorm_f32(e, G K, d) on the CURRENT codebook (an argument: no prepared workspace to go stale).
+ * q as fp32 (q) and / or bf16 (q_lo), sse[1] and hist are optional; sse and hist are pre-zeroed by the caller.  sse: one fp32 atomic
+ * per block (arrival order); in deterministic mode the partials go through the workspace of vqk_set_deterministic
+ * (>= ceil(n / 32) * groups * 4 bytes: VQK_ERR_WORKSPACE; slot g * ceil(n / 32) + b) and a second launch adds them in slot order.
+ * Served: d in {8, 16, 32, 64}, k % 32 == 0; z, e, e2, q 16-byte, q_lo 8-byte aligned (VQK_ERR_ALIGN). */
+int vqk_gvq_forward_f32(const float* z, const float* e, const float* e2, int64_t n, int k, int d, int groups, int64_t* idx,
+                        float* q /* optional */, void* q_lo /* optional */, float* sse /* optional */, int32_t* hist /* optional */,
+                        void* stream);
+/* idx[N][G] -> q[N][G d] as fp32 and / or bf16 (at least one): the forward's bits for the same tokens.  A token outside [0, K) gives
+ * a zero slice and reads nothing (never another group's rows).  Any d % 4 == 0; e and q 16-byte, q_lo 8-byte aligned. */
+int vqk_gvq_decode_f32(const int64_t* idx, const float* e, int64_t n, int k, int d, int groups, float* q /* optional */,
+                       void* q_lo /* optional */, void* stream);
+/* backward: ONE launch in default mode -- blocks of 32 flat rows [N G][d]; dz written once; the rows of a block that share a GLOBAL
+ * code id g K + k are summed in LDS and ONE coalesced fp32 atomic row per distinct (code, block) goes to de (which may be a view of
+ * the optimizer's gradient arena).  dq: optional (NULL = 0), fp32 or bf16 (dq_dtype); de: optional, pre-zeroed by the caller (or
+ * holding what it is added to).  A token outside [0, K) is a zero code and contributes nothing to de.  Deterministic mode with de:
+ * the per-row terms and the global ids go to ws group-major (>= vqk_gvq_backward_ws_bytes(n, d, groups) bytes, 8-byte aligned:
+ * VQK_ERR_WORKSPACE / VQK_ERR_ALIGN) and a second launch, one block per global code, adds its group's rows in row order: no float
+ * atomics, the same bits every run.  ws is not read otherwise (NULL allowed).  Served: d in {8, 16, 32, 64} (VQK_ERR_SHAPE
+ * otherwise, also from the size query). */
+int64_t vqk_gvq_backward_ws_bytes(int64_t n, int d, int groups);
+int vqk_gvq_backward_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
+                         int groups, float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws,
+                         int64_t ws_bytes, void* stream);
 /* ---------------------------------------------------------------- k-means codebook initialisation ---------
  * k-means++ seeding and the centroid update of a Lloyd iteration (csrc/kmeans.hip); the assignment and the per-cluster sums of an
  * iteration are vqk_vq_assign*_f32 and vqk_ema_stats*_f32.  No call allocates, synchronises or reads anything back to the host: a

@@ -28,8 +28,8 @@ from torch import nn
 from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
-from .modules.vector_quantizers import (CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GumbelVectorQuantizer,
-                                        LFQuantizer, ResidualVectorQuantizer, VectorQuantizer, _flat_view, gather_latent_sample)
+from .modules.vector_quantizers import (CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GroupedVectorQuantizer,
+                                        GumbelVectorQuantizer, LFQuantizer, ResidualVectorQuantizer, VectorQuantizer, _flat_view, gather_latent_sample)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
 from .optim import FlatAdamW
@@ -110,7 +110,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         # absent or empty: the uniform start
         self.codebook_init = self._parse_codebook_init(q_conf.get('codebook_init'), qt, self.cb_size)
         # optional `gradient` key of the standard and EMA quantizers: 'straight_through' (the default when absent) or 'rotation'
-        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'residual', 'cosine'):
+        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'residual', 'cosine', 'grouped'):
             raise ValueError(f"quantizer.params.gradient: the gradient estimator is built for the 'standard' and 'ema' quantizers only, "
                              f'not for {qt!r}')
         gradient = qp.get('gradient', 'straight_through')
@@ -148,6 +148,9 @@ class VQVAE(BaseVQVAE, _LightningBase):
             # the l2-normalised low-dimensional codebook (embedding_dim 8 to 64); a codebook_init block fits k-means to the
             # l2-normalised latent sample (CosineVectorQuantizer.init_codebook_from_data)
             self.quantizer = CosineVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']))
+        elif qt == 'grouped':
+            # one codebook of num_embeddings codes per group of embedding_dim / groups channels; tokens (B, H*W, groups)
+            self.quantizer = GroupedVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']), int(qp.get('groups', 1)))
         else:
             raise ValueError(f'unrecognized quantizer: {qt}')
 
@@ -235,7 +238,8 @@ class VQVAE(BaseVQVAE, _LightningBase):
         sample = gather_latent_sample(torch.cat(rows)[:want].contiguous())
         if sample.shape[0] < self.cb_size:
             raise ValueError(f'init_codebook_from_batches: {sample.shape[0]} latent rows over {world} ranks are fewer than num_embeddings = {self.cb_size}')
-        u = torch.rand(self.cb_size, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+        draws = self.cb_size * getattr(self.quantizer, 'groups', 1)      # the grouped quantizer seeds one codebook per group
+        u = torch.rand(draws, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
         fit = self.quantizer.init_codebook_from_data(sample, conf['iters'], u, rows_per_step=rows_per_batch * world)
         inertia, used = float(fit['inertia']), float(fit['used'])       # the one host read: the fit is over
         return dict(samples=int(sample.shape[0]), iters=conf['iters'], inertia=inertia, used=used, seconds=time.perf_counter() - t0)
@@ -532,7 +536,10 @@ class VQVAE(BaseVQVAE, _LightningBase):
         images = images[0] if isinstance(images, (tuple, list)) else images
         recon, _, used_indices = self(self.preprocess_batch(images))
         recon = self.preprocess_visualization(recon.float())[:, :3]
-        hist = torch.bincount(used_indices.reshape(-1), minlength=self.cb_size)
+        if hasattr(self.quantizer, 'tokens_to_hist'):       # token stacks whose table is not [cb_size] (grouped: one range per group)
+            hist = self.quantizer.tokens_to_hist(used_indices)
+        else:
+            hist = torch.bincount(used_indices.reshape(-1), minlength=self.cb_size)
         # (the reference writes `else + used_indices`, i.e. keeps the LAST batch's histogram; the sum is what it logs as usage)
         self.test_usage_count = hist if self.test_usage_count is None else self.test_usage_count + hist
         images = images.to(recon.device).float()

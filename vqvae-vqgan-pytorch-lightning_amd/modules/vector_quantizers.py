@@ -3,7 +3,8 @@
 EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274); ``FSQuantizer`` (finite scalar quantization, no counterpart in
 the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (residual quantization, no counterpart either) the sixth,
 ``CosineVectorQuantizer`` (the l2-normalised low-dimensional codebook of ViT-VQGAN, no counterpart either) the seventh,
-``LFQuantizer`` (lookup-free quantization of MAGVIT-v2: sign bits + an entropy loss, no counterpart either) the eighth.
+``LFQuantizer`` (lookup-free quantization of MAGVIT-v2: sign bits + an entropy loss, no counterpart either) the eighth,
+``GroupedVectorQuantizer`` (product quantization: one small codebook per channel group, no counterpart either) the ninth.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -440,3 +441,107 @@ class CosineVectorQuantizer(BaseVectorQuantizer):
         if flat_z.dim() != 2 or flat_z.shape[1] != w.shape[1]:
             raise ValueError(f'init_codebook_from_data: latents must be [N, {w.shape[1]}], got {tuple(flat_z.shape)}')
         return super().init_codebook_from_data(ops.l2norm_rows(flat_z), iters, u, rows_per_step)
+
+
+class GroupedVectorQuantizer(BaseVectorQuantizer):
+    """Product (multi-codebook, "multi-head") quantization, as in UniTok and wav2vec 2.0: the ``embedding_dim`` = D channels are cut
+    into ``groups`` = G contiguous groups of d = D / G channels and each group is looked up in its OWN codebook of ``num_embeddings``
+    = K codes; the decoder sees the concatenation and a position carries G tokens -- K^G effective codes from the codebook memory
+    (G K d = K D floats) and the lookup FLOP of the standard quantizer.  Every group carries the standard quantizer's codebook +
+    commitment loss on its slice; straight-through estimator.  One fused forward and one backward kernel (csrc/gvq.hip) for d in
+    {8, 16, 32, 64} and K % 32 == 0, the staged formulation (``ops.gvq_staged``) otherwise.  ``groups = 1`` is the standard quantizer.
+    ``codebook.weight`` is [G K, d], row g K + k = code k of group g (at G = 1 the standard quantizer's [K, D] tensor); tokens are
+    (B, H*W, G); ``last_hist``, the usage statistics and the dead-code re-initialisation work on the [G K] table, group by group."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25, groups: int = 1):
+        groups = int(groups)
+        if not 1 <= groups <= ops.GVQ_MAX_GROUPS:
+            raise ValueError(f'grouped quantizer: groups must be between 1 and {ops.GVQ_MAX_GROUPS}, got {groups}')
+        if int(embedding_dim) % groups != 0:
+            raise ValueError(f'grouped quantizer: embedding_dim = {embedding_dim} must be a multiple of groups = {groups}')
+        super().__init__(groups * int(num_embeddings), int(embedding_dim) // groups)       # the codebook the base class owns: [G K, d]
+        self.num_embeddings, self.embedding_dim, self.groups = int(num_embeddings), int(embedding_dim), groups
+        self.commitment_cost = commitment_cost
+
+    def init_codebook(self) -> None:
+        torch.nn.init.uniform_(self.codebook.weight, -1 / self.num_embeddings, 1 / self.num_embeddings)
+
+    def forward(self, x: torch.Tensor):
+        q, idx, loss, hist = ops.GVQLookupFn.apply(x, self.codebook.weight, self.commitment_cost, self.groups, self.compute_dtype)
+        self.last_hist = hist
+        return q, idx, loss
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        """x (B,D,H,W) -> codes (B,H*W,G) int64"""
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.gvq_assign(_flat_view(z), self.codebook.weight, self.groups).view(x.shape[0], -1, self.groups)
+
+    @torch.no_grad()
+    def codes_to_vec(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes (B,N,G) -> (B,N,D): the concatenated code rows, the bits the forward hands to the decoder"""
+        if codes.dim() != 3 or codes.shape[-1] != self.groups:
+            raise ValueError(f'grouped quantizer: codes must be (B, N, {self.groups}), got {tuple(codes.shape)}')
+        return ops.gvq_decode(codes, self.codebook.weight)
+
+    def tokens_to_hist(self, tokens: torch.Tensor) -> torch.Tensor:
+        """tokens (..., G) -> the [G K] usage table: entry g K + k counts token k in group g (tokens outside [0, K) count nowhere)"""
+        if tokens.shape[-1] != self.groups:
+            raise ValueError(f'grouped quantizer: tokens must be (..., {self.groups}), got {tuple(tokens.shape)}')
+        k = self.num_embeddings
+        t = tokens.reshape(-1, self.groups).to(torch.int64)
+        gid = t + torch.arange(self.groups, device=t.device, dtype=torch.int64) * k
+        return torch.bincount(gid[(t >= 0) & (t < k)], minlength=self.groups * k)
+
+    def get_codebook_usage(self, index_count: torch.Tensor):
+        """index_count (G K,) -> (usage probabilities (G K,), normalised PER GROUP; the mean of the per-group perplexities; the
+        percentage of all G K rows in use)"""
+        cnt = index_count.reshape(self.groups, self.num_embeddings)
+        p = cnt / torch.sum(cnt, dim=1, keepdim=True)
+        perplexity = torch.exp(-torch.sum(p * torch.log(p + 1e-10), dim=1)).mean().item()
+        used = torch.count_nonzero(p).item() * 100 / index_count.shape[0]
+        return p.reshape(-1), perplexity, used
+
+    @torch.no_grad()
+    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
+        """a dead code is overwritten with a code of ITS OWN group, sampled in proportion to that group's usage (a group without a
+        single live code is left alone).  Data parallel: the draw is made on rank 0 and broadcast, as in the base class."""
+        k = self.num_embeddings
+        usage = codebook_usage.reshape(self.groups, k)
+        dead, picks = [], []
+        for g in range(self.groups):
+            unused = torch.nonzero(usage[g] == 0).squeeze(1)
+            if unused.numel() == 0 or unused.numel() == k:
+                continue
+            dead.append(unused + g * k)
+            picks.append(torch.multinomial(usage[g].float(), unused.numel(), replacement=True) + g * k)
+        if not dead:
+            return
+        dead, picks = torch.cat(dead), torch.cat(picks)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            from ..optim import broadcast_
+            broadcast_(picks, src=0)                 # async + wait: no event on a stream that may capture next (optim.all_reduce_sum)
+        self.codebook.weight[dead] = self.codebook.weight[picks]
+
+    @torch.no_grad()
+    def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
+        """Data-dependent start, group by group: slab g becomes the k-means centres of the contiguous slice flat_z[:, g d:(g + 1) d]
+        (``ops.kmeans_fit`` with the draws u[g K:(g + 1) K]; ``u`` holds G K float64 draws).  Written in place and broadcast from rank
+        0 as in the base class.  Returns dict(centres [G K, d], counts [G K], inertia = the groups' sum, used = the used fraction of
+        all G K centres)."""
+        w = self.codebook.weight
+        k, d = self.num_embeddings, w.shape[1]
+        if flat_z.dim() != 2 or flat_z.shape[1] != self.embedding_dim:
+            raise ValueError(f'init_codebook_from_data: latents must be [N, {self.embedding_dim}], got {tuple(flat_z.shape)}')
+        if u.numel() != self.groups * k:
+            raise ValueError(f'init_codebook_from_data: {self.groups * k} draws are needed ({self.groups} groups of {k}), got {u.numel()}')
+        z = flat_z.detach().to(torch.float32)
+        fits = [ops.kmeans_fit(z[:, g * d:(g + 1) * d].contiguous(), k, iters, u[g * k:(g + 1) * k]) for g in range(self.groups)]
+        fit = dict(centres=torch.cat([f['centres'] for f in fits]), counts=torch.cat([f['counts'] for f in fits]).to(torch.float32),
+                   inertia=sum(f['inertia'] for f in fits), used=sum(f['used'] for f in fits) / self.groups)
+        w.data.copy_(fit['centres'])
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            from ..optim import broadcast_
+            broadcast_(w.data, src=0)
+            broadcast_(fit['counts'], src=0)
+        return fit
