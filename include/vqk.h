@@ -342,6 +342,28 @@ int64_t vqk_gvq_backward_ws_bytes(int64_t n, int d, int groups);
 int vqk_gvq_backward_f32(const float* z, const float* e, const int64_t* idx, const void* dq, int dq_dtype, int64_t n, int k, int d,
                          int groups, float cz, float ce, const float* gscale_dev, float* dz, float* de /* optional */, void* ws,
                          int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- SimVQ quantizer ---------
+ * Frozen code table + one learned linear layer (Zhu et al. 2024; csrc/simvq.hip): c[K][D] fp32 is never updated, w[D][D] (nn.Linear
+ * orientation: row i = output i) and bias[D] are learned, the effective codebook is e[k][i] = sum_j c[k][j] w[i][j] + bias[i].  The
+ * lookup against e is vqk_vq_prepare_f32 + vqk_vq_forward_f32 (d == 256) or vqk_row_sqnorm_f32 + vqk_vq_assign_f32 +
+ * vqk_vq_gather_f32 (assoc 0); loss = (1 + beta) / (N D) sse.  d in {64, 128, 256}, k < 2^26, n < 2^31 (VQK_ERR_SHAPE otherwise,
+ * nothing launched); c, w, bias, e, z, dz, ws 16-byte aligned, a bf16 dq 8-byte (VQK_ERR_ALIGN).  No call allocates or synchronises.
+ * project: exact fp32 products, fp32 accumulation (v_mfma_f32_32x32x2_f32), the order of the sum over j fixed for a given d; the bias
+ * is added last (bias NULL: none).  k % 32 == 0.  c is read once, e written once. */
+int vqk_simvq_project_f32(const float* c, const float* w, const float* bias /* optional */, int k, int d, float* e, void* stream);
+/* hist[idx[r]] += 1 for the tokens inside [0, k) (int32 atomics; for tables beyond the 16384 codes vqk_vq_gather_f32 counts itself) */
+int vqk_simvq_hist_i32(const int64_t* idx, int64_t n, int k, int32_t* hist, void* stream);
+/* backward, straight-through, two launches: dz = fma(s cz, z - q, dq) with q = e[idx] (the bits of vqk_vq_backward_f32);
+ * g_r = s ce (q_r - z_r); dw[i][j] += sum_r g_r[i] c[idx_r][j]; db[i] += sum_r g_r[i]; s = *gscale_dev (NULL: 1).  Launch 1: at most
+ * 256 blocks, each walks a contiguous row range (a function of n alone) in ascending order, writes dz and leaves its D x D + D
+ * partial in its own slice of ws (>= vqk_simvq_backward_ws_bytes(n, d) bytes: VQK_ERR_WORKSPACE).  Launch 2 adds the slices in block
+ * order and does one read-modify-write per element of dw and db, which may hold values already (views of a gradient arena).  No
+ * float atomics: the same bits in every run and every mode.  dq: optional (NULL = 0), fp32 or bf16; db optional.  A token outside
+ * [0, k) is a zero code: it reads nothing from e or c and adds nothing to dw / db.  c receives no gradient. */
+int64_t vqk_simvq_backward_ws_bytes(int64_t n, int d);
+int vqk_simvq_backward_f32(const float* z, const float* e, const float* c, const int64_t* idx, const void* dq, int dq_dtype, int64_t n,
+                           int k, int d, float cz, float ce, const float* gscale_dev, float* dz, float* dw, float* db /* optional */,
+                           void* ws, int64_t ws_bytes, void* stream);
 /* ---------------------------------------------------------------- k-means codebook initialisation ---------
  * k-means++ seeding and the centroid update of a Lloyd iteration (csrc/kmeans.hip); the assignment and the per-cluster sums of an
  * iteration are vqk_vq_assign*_f32 and vqk_ema_stats*_f32.  No call allocates, synchronises or reads anything back to the host: a

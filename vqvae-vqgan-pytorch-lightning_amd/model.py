@@ -29,7 +29,8 @@ from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
 from .modules.vector_quantizers import (CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GroupedVectorQuantizer,
-                                        GumbelVectorQuantizer, LFQuantizer, ResidualVectorQuantizer, VectorQuantizer, _flat_view, gather_latent_sample)
+                                        GumbelVectorQuantizer, LFQuantizer, ResidualVectorQuantizer, SimVectorQuantizer, VectorQuantizer, _flat_view,
+                                        gather_latent_sample)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
 from .optim import FlatAdamW
@@ -110,7 +111,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         # absent or empty: the uniform start
         self.codebook_init = self._parse_codebook_init(q_conf.get('codebook_init'), qt, self.cb_size)
         # optional `gradient` key of the standard and EMA quantizers: 'straight_through' (the default when absent) or 'rotation'
-        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'residual', 'cosine', 'grouped'):
+        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'residual', 'cosine', 'grouped', 'simvq'):
             raise ValueError(f"quantizer.params.gradient: the gradient estimator is built for the 'standard' and 'ema' quantizers only, "
                              f'not for {qt!r}')
         gradient = qp.get('gradient', 'straight_through')
@@ -151,6 +152,12 @@ class VQVAE(BaseVQVAE, _LightningBase):
         elif qt == 'grouped':
             # one codebook of num_embeddings codes per group of embedding_dim / groups channels; tokens (B, H*W, groups)
             self.quantizer = GroupedVectorQuantizer(self.cb_size, self.latent_dim, float(qp['commitment_cost']), int(qp.get('groups', 1)))
+        elif qt == 'simvq':
+            # a frozen Gaussian code table behind one learned linear layer: nothing to re-initialise, nothing to fit to data
+            if self.reinit_every_n_epochs is not None:
+                raise ValueError('simvq keeps its code table frozen: reinit_every_n_epochs must be empty')
+            self.quantizer = SimVectorQuantizer(self.cb_size, self.latent_dim, float(qp.get('commitment_cost', 0.25)),
+                                                bool(qp.get('proj_bias', True)))
         else:
             raise ValueError(f'unrecognized quantizer: {qt}')
 
@@ -192,9 +199,9 @@ class VQVAE(BaseVQVAE, _LightningBase):
         seeding (0 = the seeds)} -> the same with defaults filled in; None for an absent / empty block"""
         if not block:
             return None
-        if qt in ('gumbel', 'fsq', 'lfq'):
-            raise ValueError(f'quantizer.codebook_init: the {qt} quantizer has no codebook a k-means start would serve '
-                             f'({"no distance lookup" if qt == "gumbel" else "no learned codebook"})')
+        if qt in ('gumbel', 'fsq', 'lfq', 'simvq'):
+            why = {'gumbel': 'no distance lookup', 'simvq': 'the code table is frozen at its random start'}.get(qt, 'no learned codebook')
+            raise ValueError(f'quantizer.codebook_init: the {qt} quantizer has no codebook a k-means start would serve ({why})')
         unknown = set(block) - {'method', 'samples', 'iters'}
         if unknown:
             raise ValueError(f'quantizer.codebook_init: unknown keys {sorted(unknown)}')

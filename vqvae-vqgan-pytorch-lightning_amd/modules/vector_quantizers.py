@@ -4,7 +4,8 @@ EntropyVectorQuantizer :277-381, GumbelVectorQuantizer :206-274); ``FSQuantizer`
 the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (residual quantization, no counterpart either) the sixth,
 ``CosineVectorQuantizer`` (the l2-normalised low-dimensional codebook of ViT-VQGAN, no counterpart either) the seventh,
 ``LFQuantizer`` (lookup-free quantization of MAGVIT-v2: sign bits + an entropy loss, no counterpart either) the eighth,
-``GroupedVectorQuantizer`` (product quantization: one small codebook per channel group, no counterpart either) the ninth.
+``GroupedVectorQuantizer`` (product quantization: one small codebook per channel group, no counterpart either) the ninth,
+``SimVectorQuantizer`` (SimVQ: a frozen code table behind one learned linear layer, no counterpart either) the tenth.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -545,3 +546,49 @@ class GroupedVectorQuantizer(BaseVectorQuantizer):
             broadcast_(w.data, src=0)
             broadcast_(fit['counts'], src=0)
         return fit
+
+
+class SimVectorQuantizer(BaseVectorQuantizer):
+    """SimVQ (Zhu et al. 2024, "Addressing representation collapse in vector quantized models with one linear layer"): the code table
+    ``codebook.weight`` = C [K, D] is FROZEN at its random start and one linear layer ``codebook_proj`` (W [D, D], optional bias b) is
+    learned; the effective codebook is E = C W^T + b, so every optimizer step moves EVERY code and neither dead-code
+    re-initialisation nor a data-dependent start is needed (both raise).  The lookup against E, the codebook + commitment loss and the
+    straight-through estimator are the standard quantizer's; the backward is the gather-GEMM pair of csrc/simvq.hip for D in
+    {64, 128, 256} and K % 32 == 0 (the torch closed forms otherwise), E comes from torch.addmm unless ``ops.SIMVQ_PROJECT`` asks for
+    the HIP projection (the measured keep decision).  Tokens are (B, H*W)."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25, proj_bias: bool = True):
+        super().__init__(int(num_embeddings), int(embedding_dim))
+        self.commitment_cost = commitment_cost
+        self.codebook.requires_grad_(False)                    # the frozen table: same state-dict key as every other quantizer
+        self.codebook_proj = torch.nn.Linear(self.embedding_dim, self.embedding_dim, bias=bool(proj_bias))
+
+    @torch.no_grad()
+    def init_codebook(self) -> None:
+        """C ~ N(0, 1 / D); W = I, b = 0: at step 0 a standard quantizer over a Gaussian table (this module's own choice)"""
+        torch.nn.init.normal_(self.codebook.weight, 0.0, self.embedding_dim ** -0.5)
+        torch.nn.init.eye_(self.codebook_proj.weight)
+        if self.codebook_proj.bias is not None:
+            torch.nn.init.zeros_(self.codebook_proj.bias)
+
+    def forward(self, x: torch.Tensor):
+        q, idx, loss, hist = ops.SimVQLookupFn.apply(x, self.codebook.weight, self.codebook_proj.weight, self.codebook_proj.bias,
+                                                     self.commitment_cost, self.compute_dtype)
+        self.last_hist = hist
+        return q, idx, loss
+
+    @torch.no_grad()
+    def get_codebook(self) -> torch.Tensor:
+        """the EFFECTIVE codebook E [K, D] of the current parameters (a fresh tensor; the forward's bits)"""
+        return ops.simvq_effective(self.codebook.weight, self.codebook_proj.weight, self.codebook_proj.bias)
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.simvq_assign(_flat_view(z), self.codebook.weight, self.codebook_proj.weight, self.codebook_proj.bias).view(x.shape[0], -1)
+
+    def reinit_unused_codes(self, codebook_usage: torch.Tensor):
+        raise RuntimeError('simvq: the code table is frozen -- there is no dead-code re-initialisation (reinit_every_n_epochs must be empty)')
+
+    def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
+        raise RuntimeError('simvq: the code table is frozen at its random start -- there is no data-dependent codebook_init')
