@@ -143,7 +143,8 @@ static TuneSlot g_tune[] = {
     {"X3_WGRAD_PHASE_CAP_PCT", 0, 0},
     {"X3_WGRAD_PHASE_COEF_E4", 0, 0},
     {"WGRAD_GROUP_LOAD_PCT", 0, 0},
-    {"WGRAD_GROUP_MIN_PPS", 0, 0}
+    {"WGRAD_GROUP_MIN_PPS", 0, 0},
+    {"MX_PHASE_U64", 0, 0}
 };
 static constexpr int kTune = (int)(sizeof(g_tune) / sizeof(g_tune[0]));
 TuneSlot* tune_slot(const char* name) {

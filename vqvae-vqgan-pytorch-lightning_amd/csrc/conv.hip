@@ -1152,6 +1152,16 @@ inline bool mx_shape_ok(const ConvGeom& g, int variant) {
            (int64_t)g.n * g.h_in * g.w_in * g.cin * 2 < 0x7fffffffLL && (int64_t)g.m * g.cout * 2 < 0x7fffffffLL;
 }
 
+// its 2x2-tap phase forms (g.ntap = 4, g.phase_mode set) on units of 64 input channels instead of 32 (conv_mx.hip: U64): whole
+// 64-channel units, at least two units per tile (a tile is drained beside the NEXT tile's first unit and parked at the end of
+// its last: phase_mode 2 has four phases x units, the others need 128 channels), and the patch shape's LDS must fit.  Tuning
+// slot MX_PHASE_U64 = 0 forces the 32-channel form (A/B, and the bit-equality tests)
+inline bool mx_phase_u64_serves(const ConvGeom& g, int tw) {
+    const int units = (g.cin / 64) * (g.phase_mode == 2 ? 4 : 1);
+    return VQK_TUNE("MX_PHASE_U64", 1) && g.ntap == 4 && (g.cin % 64) == 0 && units >= 2 && (tw == 4 || tw == 5) &&
+           vqkd::mx_phase_u64_lds(tw) <= vqkd::MX_LDS_MAX;
+}
+
 // 1x1 convs (the ResBlock shortcuts, autoencoder.py:52-55): the NTAP = 1 form of that kernel
 inline bool mx_serves_1x1(const ConvGeom& g, int variant) {
     return mx_shape_ok(g, variant) && VQK_TUNE("MX_1X1", 1) && !g.ups;
@@ -1396,7 +1406,7 @@ int make_geom(ConvGeom& g, int dtype, int n, int h_in, int w_in, int cin, int co
     g.gn_ws = nullptr; g.gn_cpg = 0; g.gn_part_nblk = 0; g.gn_part_base = 0;
     g.act = 0; g.dy_pool = 0; g.tq = nullptr; g.tq_mode = 0; g.phase_rev = 0;
     g.ntap = ksize == 1 ? 1 : 9; g.tap_oy = g.tap_ox = 0; g.src_s = 1; g.src_a = g.src_b = 0; g.dst_s = 1; g.dst_a = g.dst_b = 0;
-    g.tapw = 0; g.dst_h = g.dst_w = 0; g.s2 = 0; g.phase_mode = 0;
+    g.tapw = 0; g.dst_h = g.dst_w = 0; g.s2 = 0; g.phase_mode = 0; g.unit64 = 0;
     g.fold = 0;
     const int64_t m = (int64_t)n * g.h * g.w;
     if (m > 0x7fffffff - 256) return VQK_ERR_SHAPE;
@@ -1658,6 +1668,7 @@ static int ups_phase_impl(int dtype, const void* x, const void* w4, const float*
             gp.gn_ws = gn_ws; gp.gn_cpg = gn_ws ? cout / groups : 0;
             if (gn_ws && g_det) { gp.gn_part_nblk = (g.h * g.w) / 256; gp.gn_part_base = 0; }
         }
+        gp.unit64 = mx_phase_u64_serves(gp, tw);
         return vqkd::launch_conv3x3_mx(x, w4, backward ? nullptr : bias, res, y, zeros, gp, tw, st);
     }
     for (int ph = 0; ph < 4; ++ph) {
@@ -1675,6 +1686,7 @@ static int ups_phase_impl(int dtype, const void* x, const void* w4, const float*
             gp.h_in = 2 * h; gp.w_in = 2 * w;                // the source tensor is dy at full resolution
             res = ph ? y : nullptr;                          // later phases accumulate in place
         }
+        gp.unit64 = mx_phase_u64_serves(gp, tw);
         const int r = vqkd::launch_conv3x3_mx(x, (const bf16_raw*)w4 + ph * phase_elems, backward ? nullptr : bias, res, y, zeros, gp, tw, st);
         if (r != VQK_OK) return r;
     }

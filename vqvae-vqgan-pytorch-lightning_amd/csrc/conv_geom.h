@@ -22,6 +22,9 @@ struct ConvGeom {
     int cpt;        // 16-byte chunks per tap  (cin / elems-per-16B)
     int kchunks;    // ks*ks*cpt
     int tiles_m, tiles_n;
+    int unit64;     // matrix/auxiliary-wave kernel, ntap = 4 (below): units of 64 input channels (conv_mx.hip: U64; set where
+                    // mx_phase_u64_serves says so), 0: 32-channel units.  Same operand, bit-identical result.  (Sits in what was
+                    // alignment padding: the kernel-argument offsets of every other field are unchanged)
     // matrix/auxiliary-wave kernel only: GroupNorm statistics of the OUTPUT fused into the drain -- the per-(sample, group)
     // sums of y and y*y (y as stored, i.e. rounded to bf16) are added to gn_ws[n][group][2] (vqk_gn_forward's workspace)
     double* gn_ws;
@@ -76,6 +79,13 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
     const f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+}
+
+// LDS of the 64-channel-unit phase form of that kernel on a 256-pixel patch of width 1 << twlog: two halo buffers of the
+// (TH+1) x (TW+1) phase window at 144 bytes per pixel in 1-KiB pieces, the staging tile, the statistics partials, the tile ring
+constexpr int MX_LDS_MAX = 160 * 1024;
+constexpr int mx_phase_u64_lds(int twlog) {
+    return 2 * ((((256 >> twlog) + 1) * ((1 << twlog) + 1) * 9 + 63) / 64) * 1024 + 256 * 272 + 1024 + 64;
 }
 
 // matrix-wave / auxiliary-wave 3x3 kernel (conv_mx.hip): bf16, whole 128-cout tiles, 256-pixel patches of width 1 << twlog

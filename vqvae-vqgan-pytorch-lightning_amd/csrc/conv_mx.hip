@@ -29,7 +29,9 @@
 // fetch beyond the end of its XCD's sequence; the last block to do so (census word) zeroes the counters again.
 //
 // LDS: 3 halo buffers (27 KiB) + the staging tile (256 pixels x 272 bytes) + 1 KiB of statistics partials + the 64-byte
-// tile ring = 150 KiB.
+// tile ring = 150 KiB.  The 2x2-tap phase forms on 64-channel units (U64, below): 2 halo buffers of the (TH+1) x (TW+1) phase
+// window at 144 bytes per pixel (8x32 patch: 297 pixels = 42 KiB each; 16x16: 289 pixels = 41 KiB) + the same rest = 153 KiB
+// (151 KiB) of the CU's 160 -- three buffers, or the untrimmed (TH+2) x (TW+2) halo, do not fit.
 // Numerics: the convolution sum is rounded to bf16 ONCE more than in the stream kernel when a bias / residual / pooling
 // follows (the epilogue arithmetic runs on the parked bf16 values, in fp32).
 // ------------------------------------------------------------------------------------------------
@@ -78,19 +80,28 @@ __host__ __device__ constexpr int mx_tap_pix(bool s2, int tap, int twd, int hw2,
 
 // TAPW: taps per window row when NTAP = 2 (2: a 1x2 window, 1: a 2x1 window -- the mixed-parity phases of a stride-2 conv's
 // data gradient).  S2: the stride-2 3x3 conv without padding of the StyleGAN2 discriminator (input (2h+1) x (2w+1)).
-template <int TWLOG, bool POOL, int NTAP, int PIXELS = 256, int TAPW = 0, bool S2 = false>
+// U64 (NTAP = 4 only): a unit is TWO 32-channel chunks.  A 2x2-tap unit of one chunk is 64 MFMAs per matrix wave against the 144 of a
+// 3x3 unit, but costs the same barrier, halo request and ring look-up: with 64 channels it has 128.  The halo pixel is 128 data
+// bytes + 16 pad (9 slots: odd, like 5), the halo is the (TH+1) x (TW+1) window that ONE phase reads (the phase's window offset
+// moves from the matrix waves' fragment addresses into the DMA source address), and there are two buffers in the stride-2 form's
+// schedule -- the untrimmed halo, or three buffers, do not fit beside the staging tile.  The matrix waves walk (chunk, tap,
+// k-substep): the MFMA sequence into every accumulator is the 32-channel form's, the results are bit-identical.
+template <int TWLOG, bool POOL, int NTAP, int PIXELS = 256, int TAPW = 0, bool S2 = false, bool U64 = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __restrict__ x, const bf16_raw* __restrict__ wp,
                                                             const float* __restrict__ bias,
                                                             const bf16_raw* __restrict__ res, bf16_raw* __restrict__ y,
                                                             ConvGeom g) {
     constexpr int HM = NTAP == 1 ? 0 : 1;                        // halo margin: a 1x1 conv (NTAP = 1) reads the tile's own pixels only
     constexpr int PIX = PIXELS, TW = 1 << TWLOG, TH = PIX / TW;
-    constexpr int HW2 = S2 ? TW + 1 : TW + 2 * HM;               // pixels per halo row
-    constexpr int SHP = (TH + 1) * (TW + 1);                     // S2: pixels of one parity sub-image
-    constexpr int HROWS = S2 ? 4 * SHP : (TH + 2 * HM) * HW2;
-    constexpr int RS = 80;                                       // bytes per halo pixel: 64 data + 16 pad
-    constexpr int PIECES = (HROWS * 5 + 63) / 64;                // 1-KiB LDS-DMA pieces per halo
-    constexpr int NBUF = S2 ? 2 : 3;                             // halo buffers (S2: a halo is 2.5x the bytes -- two fit)
+    constexpr int CPU = U64 ? 2 : 1;                             // 32-channel chunks per unit
+    constexpr int HW2 = (S2 || U64) ? TW + 1 : TW + 2 * HM;      // pixels per halo row
+    constexpr int SHP = (TH + 1) * (TW + 1);                     // S2: pixels of one parity sub-image; U64: of the one phase window
+    constexpr int HROWS = S2 ? 4 * SHP : U64 ? SHP : (TH + 2 * HM) * HW2;
+    constexpr int SPP = 4 * CPU + 1;                             // 16-byte slots per halo pixel: the data + one pad
+    constexpr int RS = SPP * 16;                                 // bytes per halo pixel: 64 (U64: 128) data + 16 pad
+    constexpr int PIECES = (HROWS * SPP + 63) / 64;              // 1-KiB LDS-DMA pieces per halo
+    constexpr int NBUF = (S2 || U64) ? 2 : 3;                    // halo buffers (S2 / U64: a halo is 2.5x / 1.5x the bytes -- two fit)
+    static_assert(!U64 || (NTAP == 4 && PIXELS == 256 && !S2), "64-channel units: the 2x2-tap phase forms");
     constexpr int BUF = PIECES * 1024, STG = NBUF * BUF, SPITCH = 272, SCR = STG + PIX * SPITCH;   // SCR: 1 KiB of statistics partials
     constexpr int TQR = SCR + 1024;                              // 8-entry ring of tile ids (dynamic tile queue)
     constexpr int TWD = TAPW ? TAPW : NTAP == 9 ? 3 : NTAP == 4 ? 2 : 1;      // taps per window row
@@ -98,7 +109,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
                                                                  // 16x16 maps, twice as many blocks for a chip that their 256-pixel tiles leave half empty)
     constexpr int NQ = PIX / 16;                                 // 16-byte staging pieces per auxiliary thread and tile
     static_assert(PIX == 256 || ((PIX == 128 || PIX == 64) && !POOL && NTAP == 9), "256-pixel tiles, or plain 128- / 64-pixel part tiles");
-    constexpr int NPH = NTAP * 2;                                // phases ((tap, k-substep) pairs) and weight fragments per unit
+    constexpr int NPH = NTAP * 2 * CPU;                          // phases ((chunk, tap, k-substep) triples) and weight fragments per unit
     static_assert(NTAP == 9 || ((NTAP == 4 || NTAP == 2 || NTAP == 1) && !POOL), "3x3 taps, the 2x2 / 1x2 / 2x1 taps of a phase, or a 1x1 conv");
     static_assert(!S2 || (NTAP == 9 && !POOL && PIX == 128), "stride 2: 3x3 taps, 128-pixel tiles");
     static_assert(TAPW == 0 || (NTAP == 2 && (TAPW == 1 || TAPW == 2)), "TAPW names the orientation of a 2-tap window");
@@ -119,7 +130,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
     // through the bf16 tensor in memory: three more passes over it).
     const int pmode = NTAP == 4 ? g.phase_mode : 0;
     const int total_tiles = g.n * tiles_y * tiles_x * g.tiles_n * (pmode == 1 ? 4 : 1);
-    const int nch = g.cpt >> 2;                                  // 32-channel chunks per tile (and phase)
+    const int nch = (g.cpt >> 2) / CPU;                          // units (32-channel chunks; U64: pairs of them) per tile (and phase)
     const int nun = pmode == 2 ? 4 * nch : nch;                  // units per tile
     // this block's XCD (block b runs on XCD b % 8) owns the virtual block ids [c0, c0 + cnt): xcd_remap, spelled out
     const int grid = (int)gridDim.x, q8 = grid >> 3, r8 = grid & 7, xcd = (int)blockIdx.x & 7;
@@ -161,7 +172,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
             int ty, tx;
             if (TWLOG == 5) { ty = wm * NI + i; tx = p; }
             else { ty = wm * 2 * NI + 2 * i + (p >> 4); tx = p & 15; }
-            abase[i] = (unsigned)(((ty + (pmode ? 0 : g.tap_oy)) * HW2 + tx + (pmode ? 0 : g.tap_ox)) * RS + kg * 16);
+            abase[i] = (unsigned)(((ty + ((pmode || U64) ? 0 : g.tap_oy)) * HW2 + tx + ((pmode || U64) ? 0 : g.tap_ox)) * RS + kg * 16);
             sbase[i] = (unsigned)(STG + (ty * TW + tx) * SPITCH + (wn * (32 * NJ) + 4 * kg) * 2);
         }
         const int lane16 = lane * 16;
@@ -176,9 +187,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
             return wph * phase_bytes + (((key & 0xffff) * 4 + wn * NJ + j) * nch + cc) * (NPH * 1024);
         };
         // window offset of a phase inside the halo: forward (a, b), data gradient (1 - a, 1 - b) (vqk_conv2d_ups_phase)
+        // (U64: the halo IS the phase's window -- issue_halo)
         auto phase_off = [&](int ph) -> int {
             const int a = ph >> 1, b = ph & 1;
-            return pmode == 1 ? (a * HW2 + b) * RS : pmode == 2 ? ((1 - a) * HW2 + (1 - b)) * RS : 0;
+            return U64 ? 0 : pmode == 1 ? (a * HW2 + b) * RS : pmode == 2 ? ((1 - a) * HW2 + (1 - b)) * RS : 0;
         };
         auto tile_nt = [&](int t) -> int {
             return (t % g.tiles_n) | (pmode == 1 ? ((t / g.tiles_n) & 3) << 16 : 0);
@@ -226,21 +238,27 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
             for (int i = 0; i < NI; ++i) a[0][i] = *reinterpret_cast<const frag_t*>(lbase[i]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
+            for (int cu = 0; cu < CPU; ++cu)                     // (U64: the unit's two chunks, 64 bytes apart in the halo pixel)
+#pragma unroll
             for (int tap = 0; tap < NTAP; ++tap) {
-                const int toff = mx_tap_pix(S2, tap, TWD, HW2, SHP) * RS;
+                const int toff = mx_tap_pix(S2, tap, TWD, HW2, SHP) * RS + cu * 64;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const bool reads = ks == 0 || tap < NTAP - 1;
-                    const int ph = tap * 2 + ks;
+                    const bool reads = ks == 0 || tap < NTAP - 1 || cu < CPU - 1;
+                    const int ph = (cu * NTAP + tap) * 2 + ks;
                     if (ks == 0) {
 #pragma unroll
                         for (int i = 0; i < NI; ++i) a[1][i] = *reinterpret_cast<const frag_t*>(lbase[i] + toff + 32);
                     } else if (tap < NTAP - 1) {
-                        const int toff1 = mx_tap_pix(S2, tap + 1, TWD, HW2, SHP) * RS;
+                        const int toff1 = mx_tap_pix(S2, tap + 1, TWD, HW2, SHP) * RS + cu * 64;
+#pragma unroll
+                        for (int i = 0; i < NI; ++i) a[0][i] = *reinterpret_cast<const frag_t*>(lbase[i] + toff1);
+                    } else if (cu < CPU - 1) {
+                        const int toff1 = mx_tap_pix(S2, 0, TWD, HW2, SHP) * RS + (cu + 1) * 64;
 #pragma unroll
                         for (int i = 0; i < NI; ++i) a[0][i] = *reinterpret_cast<const frag_t*>(lbase[i] + toff1);
                     }
-                    if (tap == 0 && ks == 0 && c == 0) {
+                    if (cu == 0 && tap == 0 && ks == 0 && c == 0) {
                         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int i = 0; i < NI; ++i)
@@ -310,32 +328,39 @@ __global__ __launch_bounds__(512, 2) void conv3x3_mx_kernel(const bf16_raw* __re
     const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc(y, 0, out_bytes >> (POOL ? 2 : 0), 0x00020000);
 
     // halo pieces of this wave: piece xw + 4*sl, lane -> 16-byte slot s = piece*64 + lane = halo pixel s/5, chunk s%5
-    // (chunk 4 = pad).  rel = byte offset against the tile origin (input resolution), flg = border classes of the pixel
-    // (1 top row, 2 bottom row, 4 left column, 8 right column of the halo; 16 = pad / beyond the halo: never fetched)
+    // (chunk 4 = pad; U64: s/9, s%9, chunk 8 = pad).  rel = byte offset against the tile origin (input resolution), flg = border classes of the pixel
+    // (1 top row, 2 bottom row, 4 left column, 8 right column of the halo; 16 = pad / beyond the halo: never fetched).
+    // U64: the halo is the (TH+1) x (TW+1) window of one phase, whose offset (oy, ox) in the full halo is known per unit
+    // (issue_halo): its row 0 / TH is the full halo's top / bottom row only for oy = 0 / 1 -- the tile's border mask says which
     int rel[XS], flg[XS];
 #pragma unroll
     for (int sl = 0; sl < XS; ++sl) {
         const int s = (xw + 4 * sl) * 64 + lane;
-        const int hp = s / 5, cp = s - hp * 5;
+        const int hp = s / SPP, cp = s - hp * SPP;
         if constexpr (S2) {
             // sub-image (a, b) of the patch: input pixel (2 hy + a, 2 hx + b); the odd sub-images have no row TH / column TW
             const int sh = hp / SHP, q = hp - sh * SHP;
             const int hy = q / HW2, hx = q - hy * HW2, pa = sh >> 1, pb = sh & 1;
             rel[sl] = (((2 * hy + pa) * g.w_in + 2 * hx + pb) * g.cin + cp * 8) * 2;
-            flg[sl] = (cp == 4 || hp >= HROWS || (pa && hy == TH) || (pb && hx == TW)) ? 16 : 0;
+            flg[sl] = (cp == SPP - 1 || hp >= HROWS || (pa && hy == TH) || (pb && hx == TW)) ? 16 : 0;
         } else {
             const int hy = hp / HW2, hx = hp - hy * HW2;
             rel[sl] = (((((hy - HM) * g.src_s) >> g.ups) * g.w_in + (((hx - HM) * g.src_s) >> g.ups)) * g.cin + cp * 8) * 2;
-            flg[sl] = (HM && hy == 0 ? 1 : 0) | (HM && hy == TH + 1 ? 2 : 0) | (HM && hx == 0 ? 4 : 0) | (HM && hx == TW + 1 ? 8 : 0) |
-                      ((cp == 4 || hp >= HROWS) ? 16 : 0);
+            constexpr int HB = U64 ? TH : TH + 1, HR = U64 ? TW : TW + 1;        // last row / column of the halo
+            flg[sl] = (HM && hy == 0 ? 1 : 0) | (HM && hy == HB ? 2 : 0) | (HM && hx == 0 ? 4 : 0) | (HM && hx == HR ? 8 : 0) |
+                      ((cp == SPP - 1 || hp >= HROWS) ? 16 : 0);
         }
     }
     auto issue_halo = [&](const TilePos& tp, int cu, int bufi) {
         // pmode 2: unit cu = phase * nch + chunk reads the phase (a, b) of the full-resolution gradient
         const int uph = pmode == 2 ? cu / nch : 0, c = pmode == 2 ? cu - uph * nch : cu;
         const int sa = pmode == 2 ? (uph >> 1) : g.src_a, sb = pmode == 2 ? (uph & 1) : g.src_b;
-        const int base = (((tp.img * g.h_in + ((tp.py0 * g.src_s + sa) >> g.ups)) * g.w_in + ((tp.px0 * g.src_s + sb) >> g.ups)) * g.cin + c * 32) * 2;
-        const int tb = S2 ? 16 : ((tp.py0 == 0 ? 1 : 0) | (tp.py0 + TH == g.h ? 2 : 0) | (tp.px0 == 0 ? 4 : 0) | (tp.px0 + TW == g.w ? 8 : 0) | 16);
+        // U64: window offset of the unit's phase (the M waves' phase_off / tap_oy, tap_ox of the 32-channel form)
+        const int oy = !U64 ? 0 : pmode == 1 ? (tp.ph >> 1) : pmode == 2 ? 1 - (uph >> 1) : g.tap_oy;
+        const int ox = !U64 ? 0 : pmode == 1 ? (tp.ph & 1) : pmode == 2 ? 1 - (uph & 1) : g.tap_ox;
+        const int base = (((tp.img * g.h_in + (((tp.py0 + oy) * g.src_s + sa) >> g.ups)) * g.w_in + (((tp.px0 + ox) * g.src_s + sb) >> g.ups)) * g.cin + c * (32 * CPU)) * 2;
+        const int tb = S2 ? 16 : ((tp.py0 == 0 && (!U64 || oy == 0) ? 1 : 0) | (tp.py0 + TH == g.h && (!U64 || oy == 1) ? 2 : 0) |
+                                  (tp.px0 == 0 && (!U64 || ox == 0) ? 4 : 0) | (tp.px0 + TW == g.w && (!U64 || ox == 1) ? 8 : 0) | 16);
 #pragma unroll
         for (int sl = 0; sl < XS; ++sl) {
             if (xw + 4 * sl < PIECES) {                          // wave-uniform
@@ -705,7 +730,8 @@ int launch_conv3x3_mx(const void* x, const void* w, const float* bias, const voi
     const int tqm = VQK_TUNE("TILE_QUEUE", 0);
     const DetState& tqs = tile_queue_state();
     auto set_queue = [&](int tiles, int blocks) {
-        const bool on = tqm > 0 && tqs.ws != nullptr && tqs.bytes >= 64 && tiles > blocks && (g.cpt >> 2) >= 2;
+        const int units = (g.cpt >> 2) / ((g.ntap == 4 && g.unit64) ? 2 : 1) * ((g.ntap == 4 && g.phase_mode == 2) ? 4 : 1);   // per tile
+        const bool on = tqm > 0 && tqs.ws != nullptr && tqs.bytes >= 64 && tiles > blocks && units >= 2;
         g.tq = on ? reinterpret_cast<int*>(tqs.ws) : nullptr;
         g.tq_mode = on ? (tqm >= 2 ? 2 : 1) : 0;
     };
@@ -741,6 +767,13 @@ int launch_conv3x3_mx(const void* x, const void* w, const float* bias, const voi
         if (twlog == 5) MXL((conv3x3_mx_kernel<5, false, 9, 128>), lds5h); else MXL((conv3x3_mx_kernel<4, false, 9, 128>), lds4h);
     } else if (g.ntap == 4) {
         if (g.pool) return VQK_ERR_ARG;
+        if (g.unit64) {                                          // 64-channel units (the caller asked mx_phase_u64_serves)
+            constexpr int lds5u = mx_phase_u64_lds(5), lds4u = mx_phase_u64_lds(4);
+            static_assert(lds5u <= MX_LDS_MAX && lds4u <= MX_LDS_MAX, "two trimmed 144-byte halo buffers fit beside the staging tile");
+            if ((g.cin & 63) != 0 || (g.cpt >> 3) * (g.phase_mode == 2 ? 4 : 1) < 2) return VQK_ERR_ARG;
+            if (twlog == 5) MXL((conv3x3_mx_kernel<5, false, 4, 256, 0, false, true>), lds5u);
+            else MXL((conv3x3_mx_kernel<4, false, 4, 256, 0, false, true>), lds4u);
+        }
         if (twlog == 5) MXL((conv3x3_mx_kernel<5, false, 4>), lds5); else MXL((conv3x3_mx_kernel<4, false, 4>), lds4);
     } else if (g.ntap == 1) {                                    // 1x1 conv: no halo, 2 phases per unit
         if (g.pool) return VQK_ERR_ARG;
