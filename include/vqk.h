@@ -217,6 +217,29 @@ int vqk_lfq_backward(const float* z, const float* u, const void* dq, int dq_dtyp
                      const float* ltab, const float* gscale_dev, int64_t n, int dm, int d, int g, float tau, float beta, float ratio,
                      float gamma, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out, int accumulate, void* ws,
                      int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- binary spherical quantizer ---------
+ * Zhao, Xiong, Kraehenbuehl 2024 (BSQ-ViT) (csrc/bsq.hip): lfq with the projected latent on the unit sphere.  Operands as for lfq.
+ * v = W_in z + b_in; r = 1 / max(|v|, 1e-12); u = v r; s = 1 / sqrt(d); c_j = +s if v_j > 0 else -s (a zero or a NaN gives -s); idx =
+ * sum_j [v_j > 0] 2^j; q = W_out c + b_out.  commit = sum |u - c|^2 / N (a sum over channels, a mean over rows: < 2 for every d);
+ * p_nj = sigmoid(a u_nj), a = 4 s / tau; H_sample, the groups of g bits, H_batch and the loss as for lfq.
+ * Served shapes, alignment, error codes, ordering of the sums and the workspace rule are lfq's, with vqk_bsq_ws_bytes(n, D, d, g).
+ * forward: as vqk_lfq_forward, plus r[N] (optional; u and r are what the backward needs).  Without out / ltab / ws: assignment only, ONE
+ * launch, no workspace. */
+int64_t vqk_bsq_ws_bytes(int64_t n, int dm, int d, int g);
+int vqk_bsq_forward(const float* z, const float* w_in, const float* b_in, const float* w_out, const float* b_out, int64_t n, int dm,
+                    int d, int g, float tau, float beta, float ratio, float gamma, int64_t* idx, float* u /* optional */,
+                    float* r /* optional */, float* q /* optional */, void* q_lo /* optional */, int32_t* hist /* optional */,
+                    float* out /* optional */, float* ltab /* optional */, void* ws /* optional */, int64_t ws_bytes, void* stream);
+/* idx[N] -> q (fp32 and / or bf16): c_j = +-s from bit j of the index, through the forward's own device function. */
+int vqk_bsq_decode(const int64_t* idx, const float* w_out, const float* b_out, int64_t n, int dm, int d, float* q /* optional */,
+                   void* q_lo /* optional */, void* stream);
+/* e = W_out^T dq (straight-through at u) + s dloss/du, s = *gscale_dev (NULL = 1), p recomputed from the forward's u, the H_batch term
+ * from the forward's ltab; through the normalisation dv = (e - u (u.e)) r with the forward's r; dz = dv W_in and the four parameter
+ * gradients (accumulate = 1: added to what the targets hold).  dq fp32 or bf16 (dq_dtype). */
+int vqk_bsq_backward(const float* z, const float* u, const float* r, const void* dq, int dq_dtype, const float* w_in, const float* w_out,
+                     const float* ltab, const float* gscale_dev, int64_t n, int dm, int d, int g, float tau, float beta, float ratio,
+                     float gamma, float* dz, float* dw_in, float* db_in, float* dw_out, float* db_out, int accumulate, void* ws,
+                     int64_t ws_bytes, void* stream);
 /* ---------------------------------------------------------------- self-attention core ---------
  * csrc/attn.hip.  o[b][i][h d + c] = sum_j softmax_j(scale <q[b][i][h], k[b][j][h]>) v[b][j][h d + c], lse[b][h][i] = log sum_j
  * exp(scale <q_i, k_j>) in fp32.  Operands are [B][N][ld] rows of `dtype` (VQK_F32: exact fp32 products; VQK_BF16: bf16 products, fp32

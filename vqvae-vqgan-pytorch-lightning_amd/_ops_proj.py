@@ -1,6 +1,6 @@
-"""Operators of the projection quantizers over the vqk C-ABI -- finite scalar (csrc/fsq.hip) and lookup-free (csrc/lfq.hip), one kernel
-core (csrc/proj_quant.h) and one host frame: the autograd Functions behind ``FSQuantizer`` / ``LFQuantizer`` plus the assignment-only
-and decode launchers.  Private part of :mod:`ops` like ``_ops_vq.py`` (imported at the end of ``ops.py``, which re-exports every name);
+"""Operators of the projection quantizers over the vqk C-ABI -- finite scalar (csrc/fsq.hip), lookup-free (csrc/lfq.hip) and binary
+spherical (csrc/bsq.hip), one kernel core (csrc/proj_quant.h) and one host frame: the autograd Functions behind ``FSQuantizer`` /
+``LFQuantizer`` / ``BSQuantizer`` plus the assignment-only and decode launchers.  Private part of :mod:`ops` like ``_ops_vq.py`` (imported at the end of ``ops.py``, which re-exports every name);
 shared infrastructure is reached through ``core``."""
 from __future__ import annotations
 
@@ -16,6 +16,9 @@ LFQ_MAX_BITS = 18
 LFQ_MAX_GROUP_BITS = 10
 _FSQ_WS: dict = {}                  # _wkey() -> slab workspace of vqk_fsq_backward: plain stores + ordered sums, no atomics
 _LFQ_WS: dict = {}                  # _wkey() -> slab workspace of vqk_lfq_forward / vqk_lfq_backward
+BSQ_MAX_BITS = 18
+BSQ_MAX_GROUP_BITS = 10
+_BSQ_WS: dict = {}                  # _wkey() -> slab workspace of vqk_bsq_forward / vqk_bsq_backward
 
 
 def _levels_arg(levels):
@@ -33,7 +36,14 @@ def _lfq_bits(bits: int) -> int:
     return bits
 
 
-# ---- the frame both quantizers share; ``kind`` / ``unit`` ('fsq', 'levels' | 'lfq', 'bits') only word the messages ----
+def _bsq_bits(bits: int) -> int:
+    bits = int(bits)
+    if not 1 <= bits <= BSQ_MAX_BITS:
+        raise ValueError(f'bsq: bits must be between 1 and {BSQ_MAX_BITS}, got {bits}')
+    return bits
+
+
+# ---- the frame the quantizers share; ``kind`` / ``unit`` ('fsq', 'levels' | 'lfq', 'bits' | 'bsq', 'bits') only word the messages ----
 
 def _proj_dm(kind: str, unit: str, w_in, w_out, d: int) -> int:
     """D of the [d, D] / [D, d] memory of the two 1x1 projections (Conv2d weights [O, I, 1, 1], or plain matrices)"""
@@ -232,6 +242,80 @@ class LFQFn(torch.autograd.Function):
                                            ltab.data_ptr(), gs.data_ptr(), n, dm, d, g, tau, beta, ratio, gamma, dz.data_ptr(),
                                            *(t.data_ptr() for t in tgt), int(direct), ws.data_ptr(), ws.numel(), core._stream()),
                       'lfq_backward')
+        return _grads(ctx, dz, tgt, direct)
+
+
+# ---- binary spherical quantizer ----
+
+def bsq_assign(flat_z: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, bits: int) -> torch.Tensor:
+    """flat_z [N, D] fp32 -> idx [N] int64: the forward kernel without q, u, r, loss and workspace"""
+    core._require_gpu(flat_z)
+    d = _bsq_bits(bits)
+    z, wi, bi, idx = _assign_args(flat_z, w_in, b_in)
+    _native.check(_native.lib().vqk_bsq_forward(z.data_ptr(), wi.data_ptr(), bi.data_ptr(), 0, 0, z.shape[0], z.shape[1], d, 1, 1.0,
+                                                0.0, 0.0, 0.0, idx.data_ptr(), 0, 0, 0, 0, 0, 0, 0, 0, 0, core._stream()), 'bsq_forward (assign)')
+    return idx
+
+
+def bsq_decode(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, bits: int, out_dtype=torch.float32) -> torch.Tensor:
+    """idx [...] int64 -> q [..., D] in ``out_dtype``: the bits the forward writes for the same index"""
+    core._require_gpu(idx)
+    d = _bsq_bits(bits)
+    return _decode(idx, w_out, b_out, d, out_dtype,
+                   lambda head, q, q_lo: _native.lib().vqk_bsq_decode(*head, d, q, q_lo, core._stream()), 'bsq_decode')
+
+
+class BSQFn(torch.autograd.Function):
+    """Binary spherical quantization (BSQ-ViT): project to ``bits`` channels, normalise to the unit sphere, take the sign (the corner
+    +-1 / sqrt(bits)), project back; straight-through gradient at the normalised latent u, carried through the normalisation, plus the
+    true gradient of loss = beta commit + ratio (H_sample - gamma H_batch).  Forward: one kernel + the ordered finish; backward: one
+    kernel + the ordered slab sum (bitwise reproducible in every mode).  ``cfg`` = (bits, group_bits, beta, ratio, gamma, tau).  Returns
+    (q [B,D,H,W] in out_dtype, idx [B, H*W] int64, loss 0-dim fp32 differentiable, hist int32 [K], parts fp32 [3] = commit, H_sample,
+    H_batch)."""
+
+    @staticmethod
+    def forward(ctx, z, w_in, b_in, w_out, b_out, cfg, out_dtype):
+        core._require_gpu(z)
+        d, g, beta, ratio, gamma, tau = int(cfg[0]), int(cfg[1]), float(cfg[2]), float(cfg[3]), float(cfg[4]), float(cfg[5])
+        d = _bsq_bits(d)
+        if not 1 <= g <= BSQ_MAX_GROUP_BITS:
+            raise ValueError(f'bsq: ent_group_bits must be between 1 and {BSQ_MAX_GROUP_BITS}, got {g}')
+        ctx.params = (w_in, b_in, w_out, b_out)
+        z, flat, (wi, bi, wo, bo), q, idx, u = _forward_buffers('bsq', 'bits', z, ctx.params, d, out_dtype)
+        n, dm = flat.shape
+        r = torch.empty(n, dtype=torch.float32, device=z.device)
+        hist = torch.zeros(1 << d, dtype=torch.int32, device=z.device)
+        out = torch.empty(4, dtype=torch.float32, device=z.device)
+        ltab = torch.empty(((d + g - 1) // g) << g, dtype=torch.float32, device=z.device)
+        lib = _native.lib()
+        nbytes = lib.vqk_bsq_ws_bytes(n, dm, d, g)
+        if nbytes < 0:
+            _native.check(int(nbytes), 'bsq_ws_bytes')
+        ws = core.grow_ws(_BSQ_WS, z.device, max(nbytes, 16))
+        _native.check(lib.vqk_bsq_forward(flat.data_ptr(), wi.data_ptr(), bi.data_ptr(), wo.data_ptr(), bo.data_ptr(), n, dm, d, g, tau,
+                                          beta, ratio, gamma, idx.data_ptr(), u.data_ptr(), r.data_ptr(), *_q_ptrs(q), hist.data_ptr(),
+                                          out.data_ptr(), ltab.data_ptr(), ws.data_ptr(), ws.numel(), core._stream()), 'bsq_forward')
+        ctx.save_for_backward(z, u, r, wi, wo, ltab)
+        ctx.cfg = (n, dm, d, g, beta, ratio, gamma, tau)
+        loss, parts = out[0], out[1:]
+        ctx.mark_non_differentiable(idx, hist, parts)
+        return q, idx.view(z.shape[0], z.shape[2] * z.shape[3]), loss, hist, parts
+
+    @staticmethod
+    def backward(ctx, dq, _didx, dloss, _dhist, _dparts):
+        z, u, r, wi, wo, ltab = ctx.saved_tensors
+        n, dm, d, g, beta, ratio, gamma, tau = ctx.cfg
+        dqc = _cotangent(dq, z)
+        # the loss cotangent stays on the device (a captured graph follows it); an unused loss contributes nothing
+        gs = dloss.to(torch.float32).contiguous() if dloss is not None else torch.zeros((), dtype=torch.float32, device=z.device)
+        dz = torch.empty_like(z, memory_format=core._CL)
+        tgt, direct = _grad_targets(ctx.params)
+        lib = _native.lib()
+        ws = core.grow_ws(_BSQ_WS, z.device, max(lib.vqk_bsq_ws_bytes(n, dm, d, g), 16))
+        _native.check(lib.vqk_bsq_backward(z.data_ptr(), u.data_ptr(), r.data_ptr(), dqc.data_ptr(), core.dcode(dqc.dtype), wi.data_ptr(),
+                                           wo.data_ptr(), ltab.data_ptr(), gs.data_ptr(), n, dm, d, g, tau, beta, ratio, gamma,
+                                           dz.data_ptr(), *(t.data_ptr() for t in tgt), int(direct), ws.data_ptr(), ws.numel(),
+                                           core._stream()), 'bsq_backward')
         return _grads(ctx, dz, tgt, direct)
 
 

@@ -172,4 +172,68 @@ inline int proj_launch_slab_sum(const void* ws, int slabs, int dm, int d, int ac
     return VQK_OK;
 }
 
+// ---- the transposing wave reduction (bsq.hip) ----
+// kMaxD <= 32 per-lane partials in (padded to 32 with zeros), the 64-lane sum of channel j out on the lanes 2 j and 2 j + 1 -- the
+// LANE MAP: lane l ends with channel l >> 1, both lanes of a pair with the same bits.  Five halving stages and a closing step, 32
+// exchanges where kMaxD butterflies take 6 kMaxD.  A stage pairs lane l with lane l ^ m; of the n values both hold, the lane with bit m
+// clear keeps the lower n / 2 channels and the other lane the upper n / 2, each adding the partner's partials of what it keeps:
+//   stage 1: m = 32, 16 exchanges (v_permlane32_swap: the two lanes' values trade places in one instruction, no select)
+//   stage 2: m = 16,  8 exchanges (v_permlane16_swap)
+//   stage 3: m = 8,   4 exchanges (DPP row_ror:8)          stage 4: m = 4, 2 exchanges (__shfl_xor)
+//   stage 5: m = 2,   1 exchange  (DPP quad_perm)          closing: m = 1, x + x(lane ^ 1): the two halves of the pair's sum
+// so bit 5 of the lane selects bit 4 of the channel, ..., bit 1 selects bit 0.  Every addition is (what the lane kept) + (what its
+// partner sent), the partner computing the same two terms the other way round: the order is fixed by the lane numbers alone, and float
+// addition commutes, so both lanes of the closing pair hold the same bits.
+template <int kCtrl> __device__ __forceinline__ float proj_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xf, 0xf, false));
+}
+
+// one stage on the lane bit m: t[0 .. n) -> t[0 .. n / 2); the value of lane ^ m through `xchg`
+template <int kN, int kMask, typename X>
+__device__ __forceinline__ void proj_tr_stage(float (&t)[32], int lane, X xchg) {
+    const bool up = (lane & kMask) != 0;
+#pragma unroll
+    for (int i = 0; i < kN / 2; ++i) {
+        const float keep = up ? t[i + kN / 2] : t[i], send = up ? t[i] : t[i + kN / 2];
+        t[i] = keep + xchg(send);
+    }
+}
+
+template <int kMaxD> __device__ __forceinline__ float proj_transpose_sum(const float (&acc)[kMaxD], int lane) {
+    static_assert(kMaxD <= 32, "the transposing reduction serves up to 32 channels");
+    float t[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) t[i] = i < kMaxD ? acc[i < kMaxD ? i : 0] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {       // lanes 0-31 end with [own t[i] | the upper lane's t[i]] in r[0] / r[1], lanes 32-63 with t[i + 16]
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(t[i]), __float_as_uint(t[i + 16]), false, false);
+        t[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {        // the same between the 16-lane rows: even rows keep t[i], odd rows t[i + 8]
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(t[i]), __float_as_uint(t[i + 8]), false, false);
+        t[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+    proj_tr_stage<8, 8>(t, lane, [](float v) { return proj_dpp<0x128>(v); });            // row_ror:8
+    proj_tr_stage<4, 4>(t, lane, [](float v) { return __shfl_xor(v, 4, 64); });
+    proj_tr_stage<2, 2>(t, lane, [](float v) { return proj_dpp<0x4e>(v); });             // quad_perm:[2,3,0,1]
+    return t[0] + proj_dpp<0xb1>(t[0]);                                                  // quad_perm:[1,0,3,2]
+}
+
+// the lane map and its inverse: the channel of a lane, and channel j of a value spread by that map, wave-uniform (j wave-uniform)
+__device__ __forceinline__ int proj_tr_channel(int lane) { return lane >> 1; }
+__device__ __forceinline__ float proj_tr_read(float v, int j) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 2 * j));
+}
+// a ballot over the map -> bit j = the predicate of channel j (taken on the even lane of the pair)
+__device__ __forceinline__ unsigned proj_tr_bits(unsigned long long ballot) {
+    unsigned long long x = ballot & 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
+    x = (x | (x >> 16)) & 0x00000000ffffffffull;
+    return (unsigned)x;
+}
+
 }  // namespace

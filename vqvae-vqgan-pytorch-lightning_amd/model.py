@@ -28,7 +28,7 @@ from torch import nn
 from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
-from .modules.vector_quantizers import (CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GroupedVectorQuantizer,
+from .modules.vector_quantizers import (BSQuantizer, CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GroupedVectorQuantizer,
                                         GumbelVectorQuantizer, LFQuantizer, ResidualVectorQuantizer, SimVectorQuantizer, VectorQuantizer, _flat_view,
                                         gather_latent_sample)
 from .modules.loss import loss as loss_mod
@@ -111,7 +111,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         # absent or empty: the uniform start
         self.codebook_init = self._parse_codebook_init(q_conf.get('codebook_init'), qt, self.cb_size)
         # optional `gradient` key of the standard and EMA quantizers: 'straight_through' (the default when absent) or 'rotation'
-        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'residual', 'cosine', 'grouped', 'simvq'):
+        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'bsq', 'residual', 'cosine', 'grouped', 'simvq'):
             raise ValueError(f"quantizer.params.gradient: the gradient estimator is built for the 'standard' and 'ema' quantizers only, "
                              f'not for {qt!r}')
         gradient = qp.get('gradient', 'straight_through')
@@ -139,6 +139,12 @@ class VQVAE(BaseVQVAE, _LightningBase):
                 raise ValueError('lfq has no learned codebook: reinit_every_n_epochs must be empty')
             self.quantizer = LFQuantizer(self.cb_size, self.latent_dim, int(qp['bits']), float(qp.get('commitment_cost', 0.25)),
                                          float(qp.get('ent_loss_ratio', 0.1)), float(qp.get('ent_temperature', 0.01)),
+                                         float(qp.get('diversity_gamma', 1.0)), int(qp.get('ent_group_bits', 9)))
+        elif qt == 'bsq':
+            if self.reinit_every_n_epochs is not None:
+                raise ValueError('bsq has no learned codebook: reinit_every_n_epochs must be empty')
+            self.quantizer = BSQuantizer(self.cb_size, self.latent_dim, int(qp['bits']), float(qp.get('commitment_cost', 0.25)),
+                                         float(qp.get('ent_loss_ratio', 0.1)), float(qp.get('ent_temperature', 0.02)),
                                          float(qp.get('diversity_gamma', 1.0)), int(qp.get('ent_group_bits', 9)))
         elif qt == 'residual':
             depth = int(qp.get('depth', 4))
@@ -199,7 +205,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         seeding (0 = the seeds)} -> the same with defaults filled in; None for an absent / empty block"""
         if not block:
             return None
-        if qt in ('gumbel', 'fsq', 'lfq', 'simvq'):
+        if qt in ('gumbel', 'fsq', 'lfq', 'bsq', 'simvq'):
             why = {'gumbel': 'no distance lookup', 'simvq': 'the code table is frozen at its random start'}.get(qt, 'no learned codebook')
             raise ValueError(f'quantizer.codebook_init: the {qt} quantizer has no codebook a k-means start would serve ({why})')
         unknown = set(block) - {'method', 'samples', 'iters'}

@@ -5,7 +5,8 @@ the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (r
 ``CosineVectorQuantizer`` (the l2-normalised low-dimensional codebook of ViT-VQGAN, no counterpart either) the seventh,
 ``LFQuantizer`` (lookup-free quantization of MAGVIT-v2: sign bits + an entropy loss, no counterpart either) the eighth,
 ``GroupedVectorQuantizer`` (product quantization: one small codebook per channel group, no counterpart either) the ninth,
-``SimVectorQuantizer`` (SimVQ: a frozen code table behind one learned linear layer, no counterpart either) the tenth.
+``SimVectorQuantizer`` (SimVQ: a frozen code table behind one learned linear layer, no counterpart either) the tenth,
+``BSQuantizer`` (binary spherical quantization of BSQ-ViT: ``LFQuantizer`` on the unit sphere, no counterpart either) the eleventh.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -229,7 +230,7 @@ class GumbelVectorQuantizer(BaseVectorQuantizer):
 
 
 class _ProjectionQuantizer(BaseVectorQuantizer):
-    """What the quantizers without a learned codebook share (``FSQuantizer``, ``LFQuantizer``): the D-channel latent is projected to
+    """What the quantizers without a learned codebook share (``FSQuantizer``, ``LFQuantizer``, ``BSQuantizer``): the D-channel latent is projected to
     ``channels`` channels, every channel is quantized on its own, the token is a number formed from the channels' codes and the code
     vector is projected back to D channels (the kernel core of csrc/proj_quant.h).  The two 1x1 projections are ``Conv2d`` modules for
     their parameters (names, initialisation, weight-decay group) only -- the kernels read their [d, D] / [D, d] weight memory directly.
@@ -358,6 +359,54 @@ class LFQuantizer(_ProjectionQuantizer):
     def forward(self, x: torch.Tensor):
         cfg = (self.bits, self.ent_group_bits, self.commitment_cost, self.ent_loss_ratio, self.diversity_gamma, self.ent_temperature)
         q, idx, loss, hist, parts = ops.LFQFn.apply(x, *self._projections(), cfg, self.compute_dtype)
+        self.last_hist, self.last_parts = hist, parts
+        return q, idx, loss
+
+
+class BSQuantizer(_ProjectionQuantizer):
+    """Binary spherical quantization (Zhao, Xiong, Kraehenbuehl 2024, BSQ-ViT): ``LFQuantizer`` with the projected latent put on the
+    unit sphere before the sign is taken -- u = v / |v|, code = the corner +-1 / sqrt(bits) of the hypercube inscribed in the sphere,
+    token = the bit pattern (K = 2^bits, first channel = bit 0).  The quantization error |u - c|^2 is below 2 for every ``bits``, so the
+    commitment term (a sum over channels, a mean over positions) keeps its scale as the vocabulary grows; the entropy terms and their
+    group factorisation are ``LFQuantizer``'s on the logits 4 u_j / (sqrt(bits) ent_temperature) (``ent_temperature`` 0.02 = the
+    paper's inverse temperature 100).  Straight-through at u, the gradient carried through the normalisation.  No learned codebook,
+    no search, no collective; training and evaluation behave the same.  One fused kernel each way (csrc/bsq.hip).  ``codebook`` holds
+    the IMPLICIT codebook, frozen: row i = the +-1 / sqrt(bits) vector of token i.  ``last_parts`` = (commit, H_sample, H_batch) of the
+    last forward, on the device, for logging."""
+    kind = 'bsq'
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float = 0.25, ent_loss_ratio: float = 0.1,
+                 ent_temperature: float = 0.02, diversity_gamma: float = 1.0, ent_group_bits: int = 9):
+        bits, ent_group_bits = int(bits), int(ent_group_bits)
+        if not 1 <= bits <= ops.BSQ_MAX_BITS:
+            raise ValueError(f'bsq: bits must be between 1 and {ops.BSQ_MAX_BITS}, got {bits}')
+        if num_embeddings != 2 ** bits:
+            raise ValueError(f'bsq: num_embeddings = {num_embeddings} must equal 2**bits = {2 ** bits}')
+        if not 1 <= ent_group_bits <= ops.BSQ_MAX_GROUP_BITS:
+            raise ValueError(f'bsq: ent_group_bits must be between 1 and {ops.BSQ_MAX_GROUP_BITS}, got {ent_group_bits}')
+        if not float(ent_temperature) > 0.0:
+            raise ValueError(f'bsq: ent_temperature must be > 0, got {ent_temperature}')
+        super().__init__(num_embeddings, embedding_dim, bits)
+        self.bits, self.ent_group_bits = bits, ent_group_bits
+        self.commitment_cost, self.ent_loss_ratio = float(commitment_cost), float(ent_loss_ratio)
+        self.ent_temperature, self.diversity_gamma = float(ent_temperature), float(diversity_gamma)
+        self.last_parts = None
+        self.init_codebook()
+
+    def _assign(self, flat_z: torch.Tensor) -> torch.Tensor:
+        return ops.bsq_assign(flat_z, self.project_in.weight, self.project_in.bias, self.bits)
+
+    def _decode(self, codes: torch.Tensor) -> torch.Tensor:
+        return ops.bsq_decode(codes, self.project_out.weight, self.project_out.bias, self.bits)
+
+    def implicit_codebook(self) -> torch.Tensor:
+        """[K, bits] fp32: row i, column j = +1 / sqrt(bits) if bit j of i is set, else -1 / sqrt(bits)"""
+        tokens = torch.arange(self.num_embeddings, dtype=torch.int64)
+        return (((tokens[:, None] >> torch.arange(self.bits)) & 1) * 2 - 1).to(torch.float32) / math.sqrt(self.bits)
+
+    def forward(self, x: torch.Tensor):
+        cfg = (self.bits, self.ent_group_bits, self.commitment_cost, self.ent_loss_ratio, self.diversity_gamma, self.ent_temperature)
+        q, idx, loss, hist, parts = ops.BSQFn.apply(x, *self._projections(), cfg, self.compute_dtype)
         self.last_hist, self.last_parts = hist, parts
         return q, idx, loss
 
