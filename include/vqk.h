@@ -387,6 +387,37 @@ int64_t vqk_simvq_backward_ws_bytes(int64_t n, int d);
 int vqk_simvq_backward_f32(const float* z, const float* e, const float* c, const int64_t* idx, const void* dq, int dq_dtype, int64_t n,
                            int k, int d, float cz, float ce, const float* gscale_dev, float* dz, float* dw, float* db /* optional */,
                            void* ws, int64_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- IBQ quantizer ---------
+ * Index backpropagation (csrc/ibq.hip): z[N][D], e[K][D] fp32 rows; S_ij = inv_t (z_i . e_j), P = softmax_j S, lse_i = logsumexp_j S,
+ * ebar_i = sum_j P_ij e_j, idx_i = argmax_j S_ij on the fp32 logits (the smallest index wins a tie), q_i = e[idx_i] (a bit-exact
+ * gather), sse = sum_i |q_i - z_i|^2, hist[idx_i] += 1.  Exact fp32 products (v_mfma_f32_32x32x2_f32), fp32 accumulation and
+ * statistics; no N x K array is ever in memory; no call allocates or synchronises.  No float atomics: every element of ebar, lse, dz
+ * and de is summed by one workgroup in a fixed order and sse by an ordered finish, so the results are the same bits on every run and in
+ * every mode (hist: int32 atomics).  d in {64, 128, 256}, ANY 1 <= n < 2^31 and ANY 1 <= k < 2^31 (VQK_ERR_SHAPE otherwise, nothing
+ * launched): tail rows and tail codes are zeros in LDS, never read or stored; a tail code weighs exactly zero and can never win the
+ * argmax.  z, e, ebar, q32, dz, de, ws 16-byte aligned, a bf16 q / dq 8-byte (VQK_ERR_ALIGN).  inv_t = 1 / T > 0.
+ * forward: one launch, plus the ordered finish when sse is asked for.  idx is always written.  lse and ebar: both or neither; with
+ * neither the ARGMAX-ONLY mode runs -- the same logit arithmetic, no exponentials, no second product, the same tokens bit for bit.
+ * q32, qlo (bf16), sse, hist (caller-zeroed; counts are added): each optional in both modes.  sse is ASSIGNED; it needs ws of
+ * >= vqk_ibq_forward_ws_bytes(n) bytes (VQK_ERR_WORKSPACE). */
+int64_t vqk_ibq_forward_ws_bytes(int64_t n);
+int vqk_ibq_forward_f32(const float* z, const float* e, int64_t n, int k, int d, float inv_t, int64_t* idx, float* lse /* optional */,
+                        float* ebar /* optional */, float* q32 /* optional */, void* qlo /* optional */, float* sse /* optional */,
+                        int32_t* hist /* optional */, void* ws, int64_t ws_bytes, void* stream);
+/* backward, three launches (a row pass, a code-owning pass, a row-owning pass), s = *gscale_dev (NULL: 1), g = dq (NULL: 0, fp32 or
+ * bf16), diff_i = q_i - z_i with q_i = e[idx_i]:
+ *   G_i = g_i + s ce diff_i;  delta_i = G_i . ebar_i;  dS_ij = P_ij (G_i . e_j - delta_i) with P_ij = exp(S_ij - lse_i) recomputed;
+ *   dz_i = -2 s ce diff_i + inv_t sum_j dS_ij e_j;   de_j += sum_{i: idx_i = j} (G_i + s cz diff_i) + inv_t sum_i dS_ij z_i
+ * (ce = 2 / (N D), cz = beta ce; there is no straight-through copy of g onto z).  de is accumulated as old + sum with one
+ * read-modify-write per element, so it may be a view of a gradient arena that already holds values; de NULL: the code-owning pass
+ * is skipped.  The hard term is an exact product with the tile's 0 / 1 selection matrix in the fixed row order.  A token outside
+ * [0, k) has diff = 0, reads nothing from e and adds no hard term; its soft terms are intact.  ws: >= vqk_ibq_backward_ws_bytes(n, d)
+ * bytes (G, G + s cz diff and delta: 2 N D + N floats). */
+int64_t vqk_ibq_backward_ws_bytes(int64_t n, int d);
+int vqk_ibq_backward_f32(const float* z, const float* e, const int64_t* idx, const float* lse, const float* ebar,
+                         const void* dq /* optional */, int dq_dtype, int64_t n, int k, int d, float inv_t, float cz, float ce,
+                         const float* gscale_dev /* optional */, float* dz, float* de /* optional */, void* ws, int64_t ws_bytes,
+                         void* stream);
 /* ---------------------------------------------------------------- k-means codebook initialisation ---------
  * k-means++ seeding and the centroid update of a Lloyd iteration (csrc/kmeans.hip); the assignment and the per-cluster sums of an
  * iteration are vqk_vq_assign*_f32 and vqk_ema_stats*_f32.  No call allocates, synchronises or reads anything back to the host: a

@@ -89,6 +89,8 @@ _PROTOS = {
     'vqk_simvq_project_f32': [P, P, P, I, I, P, P],
     'vqk_simvq_hist_i32': [P, L, I, P, P],
     'vqk_simvq_backward_f32': [P, P, P, P, P, I, L, I, I, F, F, P, P, P, P, P, L, P],
+    'vqk_ibq_forward_f32': [P, P, L, I, I, F, P, P, P, P, P, P, P, P, L, P],
+    'vqk_ibq_backward_f32': [P, P, P, P, P, P, I, L, I, I, F, F, F, P, P, P, P, L, P],
     'vqk_kmeans_seed_step_f32': [P, L, I, I, I, P, P, P, P, P, L, P],
     'vqk_kmeans_update_f32': [P, P, I, I, P, P, P],
     'vqk_ema_stats_f32': [P, P, L, I, I, P, P, P],
@@ -189,7 +191,7 @@ _PROTOS = {
 }
 _SPECIAL = {'vqk_set_tuning': (I, [c_char_p, I]), 'vqk_reset_tuning': (I, []), 'vqk_tuning_count': (I, []),
             'vqk_tuning_name': (c_char_p, [I]), 'vqk_conv_fprop_form_name': (c_char_p, [I, I]),
-            'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_fsq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_lfq_ws_bytes': (c_int64, [L, I, I, I]), 'vqk_bsq_ws_bytes': (c_int64, [L, I, I, I]), 'vqk_rvq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_cos_ws_bytes': (c_int64, [I, I]), 'vqk_cos_backward_ws_bytes': (c_int64, [L, I]), 'vqk_gvq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_simvq_backward_ws_bytes': (c_int64, [L, I]), 'vqk_kmeans_seed_ws_bytes': (c_int64, [L]), 'vqk_conv4x4_wgrad_ws_bytes': (c_int64, [I, I, I, I, I, I, I]), 'vqk_bn_ws_bytes': (c_int64, [L, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_arena_stats_ws_bytes': (c_int64, [L, I]), 'vqk_adamw_bias_table': (c_int64, [F, F, P, L]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
+            'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_fsq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_lfq_ws_bytes': (c_int64, [L, I, I, I]), 'vqk_bsq_ws_bytes': (c_int64, [L, I, I, I]), 'vqk_rvq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_cos_ws_bytes': (c_int64, [I, I]), 'vqk_cos_backward_ws_bytes': (c_int64, [L, I]), 'vqk_gvq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_simvq_backward_ws_bytes': (c_int64, [L, I]), 'vqk_ibq_forward_ws_bytes': (c_int64, [L]), 'vqk_ibq_backward_ws_bytes': (c_int64, [L, I]), 'vqk_kmeans_seed_ws_bytes': (c_int64, [L]), 'vqk_conv4x4_wgrad_ws_bytes': (c_int64, [I, I, I, I, I, I, I]), 'vqk_bn_ws_bytes': (c_int64, [L, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_arena_stats_ws_bytes': (c_int64, [L, I]), 'vqk_adamw_bias_table': (c_int64, [F, F, P, L]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
 EXPORTS = sorted(list(_PROTOS) + list(_SPECIAL))
 
 

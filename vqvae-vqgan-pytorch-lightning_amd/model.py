@@ -29,7 +29,7 @@ from . import ops
 from .modules.abstract_modules.base_autoencoder import BaseVQVAE
 from .modules.autoencoder import Decoder, Encoder, GroupNorm, Conv2d, resolve_compute_dtype, set_compute_dtype
 from .modules.vector_quantizers import (BSQuantizer, CosineVectorQuantizer, EMAVectorQuantizer, EntropyVectorQuantizer, FSQuantizer, GroupedVectorQuantizer,
-                                        GumbelVectorQuantizer, LFQuantizer, ResidualVectorQuantizer, SimVectorQuantizer, VectorQuantizer, _flat_view,
+                                        GumbelVectorQuantizer, IBQuantizer, LFQuantizer, ResidualVectorQuantizer, SimVectorQuantizer, VectorQuantizer, _flat_view,
                                         gather_latent_sample)
 from .modules.loss import loss as loss_mod
 from .modules.loss.loss import VQLPIPSWithDiscriminator
@@ -111,7 +111,7 @@ class VQVAE(BaseVQVAE, _LightningBase):
         # absent or empty: the uniform start
         self.codebook_init = self._parse_codebook_init(q_conf.get('codebook_init'), qt, self.cb_size)
         # optional `gradient` key of the standard and EMA quantizers: 'straight_through' (the default when absent) or 'rotation'
-        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'bsq', 'residual', 'cosine', 'grouped', 'simvq'):
+        if 'gradient' in qp and qt in ('entropy', 'gumbel', 'fsq', 'lfq', 'bsq', 'residual', 'cosine', 'grouped', 'simvq', 'ibq'):
             raise ValueError(f"quantizer.params.gradient: the gradient estimator is built for the 'standard' and 'ema' quantizers only, "
                              f'not for {qt!r}')
         gradient = qp.get('gradient', 'straight_through')
@@ -164,6 +164,10 @@ class VQVAE(BaseVQVAE, _LightningBase):
                 raise ValueError('simvq keeps its code table frozen: reinit_every_n_epochs must be empty')
             self.quantizer = SimVectorQuantizer(self.cb_size, self.latent_dim, float(qp.get('commitment_cost', 0.25)),
                                                 bool(qp.get('proj_bias', True)))
+        elif qt == 'ibq':
+            # index backpropagation: a learned codebook ranked by dot products, every code updated on every step
+            self.quantizer = IBQuantizer(self.cb_size, self.latent_dim, float(qp.get('commitment_cost', 0.25)),
+                                         float(qp.get('temperature', 1.0)))
         else:
             raise ValueError(f'unrecognized quantizer: {qt}')
 
@@ -205,8 +209,9 @@ class VQVAE(BaseVQVAE, _LightningBase):
         seeding (0 = the seeds)} -> the same with defaults filled in; None for an absent / empty block"""
         if not block:
             return None
-        if qt in ('gumbel', 'fsq', 'lfq', 'bsq', 'simvq'):
-            why = {'gumbel': 'no distance lookup', 'simvq': 'the code table is frozen at its random start'}.get(qt, 'no learned codebook')
+        if qt in ('gumbel', 'fsq', 'lfq', 'bsq', 'simvq', 'ibq'):
+            why = {'gumbel': 'no distance lookup', 'simvq': 'the code table is frozen at its random start',
+                   'ibq': 'the lookup ranks dot products, not distances'}.get(qt, 'no learned codebook')
             raise ValueError(f'quantizer.codebook_init: the {qt} quantizer has no codebook a k-means start would serve ({why})')
         unknown = set(block) - {'method', 'samples', 'iters'}
         if unknown:

@@ -6,7 +6,8 @@ the reference) is the fifth member of the family, ``ResidualVectorQuantizer`` (r
 ``LFQuantizer`` (lookup-free quantization of MAGVIT-v2: sign bits + an entropy loss, no counterpart either) the eighth,
 ``GroupedVectorQuantizer`` (product quantization: one small codebook per channel group, no counterpart either) the ninth,
 ``SimVectorQuantizer`` (SimVQ: a frozen code table behind one learned linear layer, no counterpart either) the tenth,
-``BSQuantizer`` (binary spherical quantization of BSQ-ViT: ``LFQuantizer`` on the unit sphere, no counterpart either) the eleventh.
+``BSQuantizer`` (binary spherical quantization of BSQ-ViT: ``LFQuantizer`` on the unit sphere, no counterpart either) the eleventh,
+``IBQuantizer`` (index backpropagation: a straight-through estimator on softmax(z E^T), every code updated, no counterpart either) the twelfth.
 
 The nearest-codeword search is one exact-fp32 MFMA kernel that never materialises the [N,K] distance
 matrix or a one-hot; the reference's association order of the three distance terms is kept so that the
@@ -641,3 +642,32 @@ class SimVectorQuantizer(BaseVectorQuantizer):
 
     def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
         raise RuntimeError('simvq: the code table is frozen at its random start -- there is no data-dependent codebook_init')
+
+
+class IBQuantizer(BaseVectorQuantizer):
+    """Index backpropagation (IBQ): the token is the argmax of softmax(z E^T / T) over the learned codebook ``codebook.weight`` =
+    E [K, D], the output the gathered code, and the one-hot is made differentiable with a straight-through estimator on the softmax --
+    so every optimizer step moves EVERY code and the encoder is trained through the logits, not through a copy of the decoder's
+    gradient.  loss = (2 + beta) / (N D) sum |q - z|^2.  The lookup ranks dot products, not distances.  Fused HIP kernels that never
+    hold an N x K array for D in {64, 128, 256} (csrc/ibq.hip), the staged torch formulation otherwise.  Tokens are
+    (B, H*W); the uniform start, usage statistics, dead-code re-initialisation and ``codes_to_vec`` are the base class's."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float = 0.25, temperature: float = 1.0):
+        super().__init__(int(num_embeddings), int(embedding_dim))
+        self.commitment_cost = float(commitment_cost)
+        self.temperature = float(temperature)
+        if not (self.temperature > 0.0 and self.temperature < math.inf):
+            raise ValueError(f'ibq: temperature must be a positive finite number, got {temperature!r}')
+
+    def forward(self, x: torch.Tensor):
+        q, idx, loss, hist = ops.IBQLookupFn.apply(x, self.codebook.weight, self.commitment_cost, self.temperature, self.compute_dtype)
+        self.last_hist = hist
+        return q, idx, loss
+
+    @torch.no_grad()
+    def vec_to_codes(self, x: torch.Tensor) -> torch.Tensor:
+        z = ops.nhwc(x.to(torch.float32))
+        return ops.ibq_assign(_flat_view(z), self.codebook.weight, self.temperature).view(x.shape[0], -1)
+
+    def init_codebook_from_data(self, flat_z: torch.Tensor, iters: int, u: torch.Tensor, rows_per_step: int = None) -> dict:
+        raise RuntimeError('ibq: the lookup ranks dot products, not distances -- there is no k-means codebook_init')

@@ -2191,6 +2191,7 @@ RVQ_FUSED = _native.switch('VQK_RVQ_FUSED', '1') != '0'    # residual quantizer:
 GVQ_FUSED = _native.switch('VQK_GVQ_FUSED', '1') != '0'    # grouped quantizer: the one-launch per-group rank + gather forward and the flat-row backward (0: the staged formulation, _ops_gvq.gvq_staged)
 SIMVQ_FUSED = _native.switch('VQK_SIMVQ_FUSED', '1') != '0'  # SimVQ quantizer: the per-call prepare + one-kernel lookup and the two-launch gather-GEMM backward (0: the staged formulation, _ops_simvq.simvq_staged)
 SIMVQ_PROJECT = _native.switch('VQK_SIMVQ_PROJECT', '0') == '1'  # SimVQ quantizer: E by the HIP projection (csrc/simvq.hip) instead of torch.addmm -- off: no measured shape class met the keep criterion (profiles/simvq_bench.txt)
+IBQ_FUSED = _native.switch('VQK_IBQ_FUSED', '1') != '0'    # IBQ quantizer: the fused online-softmax + argmax forward and the three-launch atomic-free backward (0: the staged formulation, _ops_ibq.ibq_staged)
 COS_FUSED = _native.switch('VQK_COS_FUSED', '1') != '0'    # cosine quantizer: the one-launch normalise + rank + gather forward (0: the staged formulation, _ops_cos.cos_staged)
 ATTN_FUSED = _native.switch('VQK_ATTN_FUSED', '1') != '0'   # self-attention: the fused forward / backward kernels (0: the staged formulation, _ops_attn.attention_staged)
 ENTROPY_FUSED_ROWS = _native.switch('VQK_ENTROPY_FUSED_ROWS', '1') != '0'
@@ -2270,6 +2271,7 @@ from ._ops_rvq import *       # noqa: E402,F401,F403  residual quantizer
 from ._ops_cos import *       # noqa: E402,F401,F403  cosine quantizer
 from ._ops_gvq import *       # noqa: E402,F401,F403  grouped quantizer
 from ._ops_simvq import *     # noqa: E402,F401,F403  SimVQ quantizer
+from ._ops_ibq import *       # noqa: E402,F401,F403  index-backpropagation quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
 from ._ops_attn import *      # noqa: E402,F401,F403  self-attention core
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins
