@@ -1,5 +1,5 @@
 """Operators of the projection quantizers over the vqk C-ABI -- finite scalar (csrc/fsq.hip), lookup-free (csrc/lfq.hip) and binary
-spherical (csrc/bsq.hip), one kernel core (csrc/proj_quant.h) and one host frame: the autograd Functions behind ``FSQuantizer`` /
+spherical (csrc/bsq.hip), one kernel core (csrc/proj_quant.h, csrc/sign_quant.h) and one host frame: the autograd Functions behind ``FSQuantizer`` /
 ``LFQuantizer`` / ``BSQuantizer`` plus the assignment-only and decode launchers.  Private part of :mod:`ops` like ``_ops_vq.py`` (imported at the end of ``ops.py``, which re-exports every name);
 shared infrastructure is reached through ``core``."""
 from __future__ import annotations
@@ -29,17 +29,14 @@ def _levels_arg(levels):
     return (ctypes.c_int32 * 8)(*levels), len(levels), math.prod(levels)
 
 
-def _lfq_bits(bits: int) -> int:
-    bits = int(bits)
-    if not 1 <= bits <= LFQ_MAX_BITS:
-        raise ValueError(f'lfq: bits must be between 1 and {LFQ_MAX_BITS}, got {bits}')
-    return bits
+# the sign quantizers (csrc/sign_quant.h), by kind: (max bits, max group bits, workspace dict, has the per-row buffer r = 1 / |v|)
+_SIGN = {'lfq': (LFQ_MAX_BITS, LFQ_MAX_GROUP_BITS, _LFQ_WS, False), 'bsq': (BSQ_MAX_BITS, BSQ_MAX_GROUP_BITS, _BSQ_WS, True)}
 
 
-def _bsq_bits(bits: int) -> int:
+def _sign_bits(kind: str, bits: int) -> int:
     bits = int(bits)
-    if not 1 <= bits <= BSQ_MAX_BITS:
-        raise ValueError(f'bsq: bits must be between 1 and {BSQ_MAX_BITS}, got {bits}')
+    if not 1 <= bits <= _SIGN[kind][0]:
+        raise ValueError(f'{kind}: bits must be between 1 and {_SIGN[kind][0]}, got {bits}')
     return bits
 
 
@@ -173,24 +170,84 @@ class FSQFn(torch.autograd.Function):
         return _grads(ctx, dz, tgt, direct)
 
 
-# ---- lookup-free quantizer ----
+# ---- the sign quantizers, lookup-free (lfq) and binary spherical (bsq): one frame; ``kind`` names the C functions vqk_<kind>_* ----
+
+def _sign_fn(kind: str, name: str):
+    return getattr(_native.lib(), f'vqk_{kind}_{name}')
+
+
+def _sign_assign(kind: str, flat_z, w_in, b_in, bits: int) -> torch.Tensor:
+    """flat_z [N, D] fp32 -> idx [N] int64: the forward kernel without q, u, r, loss and workspace"""
+    core._require_gpu(flat_z)
+    d = _sign_bits(kind, bits)
+    z, wi, bi, idx = _assign_args(flat_z, w_in, b_in)
+    no_r = (0,) if _SIGN[kind][3] else ()
+    _native.check(_sign_fn(kind, 'forward')(z.data_ptr(), wi.data_ptr(), bi.data_ptr(), 0, 0, z.shape[0], z.shape[1], d, 1, 1.0, 0.0, 0.0,
+                                            0.0, idx.data_ptr(), 0, *no_r, 0, 0, 0, 0, 0, 0, 0, core._stream()), f'{kind}_forward (assign)')
+    return idx
+
+
+def _sign_decode(kind: str, idx, w_out, b_out, bits: int, out_dtype) -> torch.Tensor:
+    """idx [...] int64 -> q [..., D] in ``out_dtype``: the bits the forward writes for the same index"""
+    core._require_gpu(idx)
+    d = _sign_bits(kind, bits)
+    fn = _sign_fn(kind, 'decode')
+    return _decode(idx, w_out, b_out, d, out_dtype, lambda head, q, q_lo: fn(*head, d, q, q_lo, core._stream()), f'{kind}_decode')
+
+
+def _sign_forward(kind: str, ctx, z, w_in, b_in, w_out, b_out, cfg, out_dtype):
+    core._require_gpu(z)
+    _, max_group, ws_of, has_r = _SIGN[kind]
+    d, g, beta, ratio, gamma, tau = int(cfg[0]), int(cfg[1]), float(cfg[2]), float(cfg[3]), float(cfg[4]), float(cfg[5])
+    d = _sign_bits(kind, d)
+    if not 1 <= g <= max_group:
+        raise ValueError(f'{kind}: ent_group_bits must be between 1 and {max_group}, got {g}')
+    ctx.params = (w_in, b_in, w_out, b_out)
+    z, flat, (wi, bi, wo, bo), q, idx, u = _forward_buffers(kind, 'bits', z, ctx.params, d, out_dtype)
+    n, dm = flat.shape
+    r = (torch.empty(n, dtype=torch.float32, device=z.device),) if has_r else ()
+    hist = torch.zeros(1 << d, dtype=torch.int32, device=z.device)
+    out = torch.empty(4, dtype=torch.float32, device=z.device)
+    ltab = torch.empty(((d + g - 1) // g) << g, dtype=torch.float32, device=z.device)
+    nbytes = _sign_fn(kind, 'ws_bytes')(n, dm, d, g)
+    if nbytes < 0:
+        _native.check(int(nbytes), f'{kind}_ws_bytes')
+    ws = core.grow_ws(ws_of, z.device, max(nbytes, 16))
+    _native.check(_sign_fn(kind, 'forward')(flat.data_ptr(), wi.data_ptr(), bi.data_ptr(), wo.data_ptr(), bo.data_ptr(), n, dm, d, g, tau,
+                                            beta, ratio, gamma, idx.data_ptr(), u.data_ptr(), *(t.data_ptr() for t in r), *_q_ptrs(q),
+                                            hist.data_ptr(), out.data_ptr(), ltab.data_ptr(), ws.data_ptr(), ws.numel(), core._stream()),
+                  f'{kind}_forward')
+    ctx.save_for_backward(z, u, *r, wi, wo, ltab)
+    ctx.cfg = (n, dm, d, g, beta, ratio, gamma, tau)
+    loss, parts = out[0], out[1:]
+    ctx.mark_non_differentiable(idx, hist, parts)
+    return q, idx.view(z.shape[0], z.shape[2] * z.shape[3]), loss, hist, parts
+
+
+def _sign_backward(kind: str, ctx, dq, dloss):
+    z, u, *r, wi, wo, ltab = ctx.saved_tensors
+    n, dm, d, g, beta, ratio, gamma, tau = ctx.cfg
+    dqc = _cotangent(dq, z)
+    # the loss cotangent stays on the device (a captured graph follows it); an unused loss contributes nothing
+    gs = dloss.to(torch.float32).contiguous() if dloss is not None else torch.zeros((), dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z, memory_format=core._CL)
+    tgt, direct = _grad_targets(ctx.params)
+    ws = core.grow_ws(_SIGN[kind][2], z.device, max(_sign_fn(kind, 'ws_bytes')(n, dm, d, g), 16))
+    _native.check(_sign_fn(kind, 'backward')(z.data_ptr(), u.data_ptr(), *(t.data_ptr() for t in r), dqc.data_ptr(), core.dcode(dqc.dtype),
+                                             wi.data_ptr(), wo.data_ptr(), ltab.data_ptr(), gs.data_ptr(), n, dm, d, g, tau, beta, ratio,
+                                             gamma, dz.data_ptr(), *(t.data_ptr() for t in tgt), int(direct), ws.data_ptr(), ws.numel(),
+                                             core._stream()), f'{kind}_backward')
+    return _grads(ctx, dz, tgt, direct)
+
 
 def lfq_assign(flat_z: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, bits: int) -> torch.Tensor:
     """flat_z [N, D] fp32 -> idx [N] int64: the forward kernel without q, u, loss and workspace"""
-    core._require_gpu(flat_z)
-    d = _lfq_bits(bits)
-    z, wi, bi, idx = _assign_args(flat_z, w_in, b_in)
-    _native.check(_native.lib().vqk_lfq_forward(z.data_ptr(), wi.data_ptr(), bi.data_ptr(), 0, 0, z.shape[0], z.shape[1], d, 1, 1.0,
-                                                0.0, 0.0, 0.0, idx.data_ptr(), 0, 0, 0, 0, 0, 0, 0, 0, core._stream()), 'lfq_forward (assign)')
-    return idx
+    return _sign_assign('lfq', flat_z, w_in, b_in, bits)
 
 
 def lfq_decode(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, bits: int, out_dtype=torch.float32) -> torch.Tensor:
     """idx [...] int64 -> q [..., D] in ``out_dtype``: the bits the forward writes for the same index"""
-    core._require_gpu(idx)
-    d = _lfq_bits(bits)
-    return _decode(idx, w_out, b_out, d, out_dtype,
-                   lambda head, q, q_lo: _native.lib().vqk_lfq_decode(*head, d, q, q_lo, core._stream()), 'lfq_decode')
+    return _sign_decode('lfq', idx, w_out, b_out, bits, out_dtype)
 
 
 class LFQFn(torch.autograd.Function):
@@ -202,67 +259,21 @@ class LFQFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, w_in, b_in, w_out, b_out, cfg, out_dtype):
-        core._require_gpu(z)
-        d, g, beta, ratio, gamma, tau = int(cfg[0]), int(cfg[1]), float(cfg[2]), float(cfg[3]), float(cfg[4]), float(cfg[5])
-        d = _lfq_bits(d)
-        if not 1 <= g <= LFQ_MAX_GROUP_BITS:
-            raise ValueError(f'lfq: ent_group_bits must be between 1 and {LFQ_MAX_GROUP_BITS}, got {g}')
-        ctx.params = (w_in, b_in, w_out, b_out)
-        z, flat, (wi, bi, wo, bo), q, idx, u = _forward_buffers('lfq', 'bits', z, ctx.params, d, out_dtype)
-        n, dm = flat.shape
-        hist = torch.zeros(1 << d, dtype=torch.int32, device=z.device)
-        out = torch.empty(4, dtype=torch.float32, device=z.device)
-        ltab = torch.empty(((d + g - 1) // g) << g, dtype=torch.float32, device=z.device)
-        lib = _native.lib()
-        nbytes = lib.vqk_lfq_ws_bytes(n, dm, d, g)
-        if nbytes < 0:
-            _native.check(int(nbytes), 'lfq_ws_bytes')
-        ws = core.grow_ws(_LFQ_WS, z.device, max(nbytes, 16))
-        _native.check(lib.vqk_lfq_forward(flat.data_ptr(), wi.data_ptr(), bi.data_ptr(), wo.data_ptr(), bo.data_ptr(), n, dm, d, g, tau,
-                                          beta, ratio, gamma, idx.data_ptr(), u.data_ptr(), *_q_ptrs(q), hist.data_ptr(), out.data_ptr(),
-                                          ltab.data_ptr(), ws.data_ptr(), ws.numel(), core._stream()), 'lfq_forward')
-        ctx.save_for_backward(z, u, wi, wo, ltab)
-        ctx.cfg = (n, dm, d, g, beta, ratio, gamma, tau)
-        loss, parts = out[0], out[1:]
-        ctx.mark_non_differentiable(idx, hist, parts)
-        return q, idx.view(z.shape[0], z.shape[2] * z.shape[3]), loss, hist, parts
+        return _sign_forward('lfq', ctx, z, w_in, b_in, w_out, b_out, cfg, out_dtype)
 
     @staticmethod
     def backward(ctx, dq, _didx, dloss, _dhist, _dparts):
-        z, u, wi, wo, ltab = ctx.saved_tensors
-        n, dm, d, g, beta, ratio, gamma, tau = ctx.cfg
-        dqc = _cotangent(dq, z)
-        # the loss cotangent stays on the device (a captured graph follows it); an unused loss contributes nothing
-        gs = dloss.to(torch.float32).contiguous() if dloss is not None else torch.zeros((), dtype=torch.float32, device=z.device)
-        dz = torch.empty_like(z, memory_format=core._CL)
-        tgt, direct = _grad_targets(ctx.params)
-        lib = _native.lib()
-        ws = core.grow_ws(_LFQ_WS, z.device, max(lib.vqk_lfq_ws_bytes(n, dm, d, g), 16))
-        _native.check(lib.vqk_lfq_backward(z.data_ptr(), u.data_ptr(), dqc.data_ptr(), core.dcode(dqc.dtype), wi.data_ptr(), wo.data_ptr(),
-                                           ltab.data_ptr(), gs.data_ptr(), n, dm, d, g, tau, beta, ratio, gamma, dz.data_ptr(),
-                                           *(t.data_ptr() for t in tgt), int(direct), ws.data_ptr(), ws.numel(), core._stream()),
-                      'lfq_backward')
-        return _grads(ctx, dz, tgt, direct)
+        return _sign_backward('lfq', ctx, dq, dloss)
 
-
-# ---- binary spherical quantizer ----
 
 def bsq_assign(flat_z: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor, bits: int) -> torch.Tensor:
     """flat_z [N, D] fp32 -> idx [N] int64: the forward kernel without q, u, r, loss and workspace"""
-    core._require_gpu(flat_z)
-    d = _bsq_bits(bits)
-    z, wi, bi, idx = _assign_args(flat_z, w_in, b_in)
-    _native.check(_native.lib().vqk_bsq_forward(z.data_ptr(), wi.data_ptr(), bi.data_ptr(), 0, 0, z.shape[0], z.shape[1], d, 1, 1.0,
-                                                0.0, 0.0, 0.0, idx.data_ptr(), 0, 0, 0, 0, 0, 0, 0, 0, 0, core._stream()), 'bsq_forward (assign)')
-    return idx
+    return _sign_assign('bsq', flat_z, w_in, b_in, bits)
 
 
 def bsq_decode(idx: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, bits: int, out_dtype=torch.float32) -> torch.Tensor:
     """idx [...] int64 -> q [..., D] in ``out_dtype``: the bits the forward writes for the same index"""
-    core._require_gpu(idx)
-    d = _bsq_bits(bits)
-    return _decode(idx, w_out, b_out, d, out_dtype,
-                   lambda head, q, q_lo: _native.lib().vqk_bsq_decode(*head, d, q, q_lo, core._stream()), 'bsq_decode')
+    return _sign_decode('bsq', idx, w_out, b_out, bits, out_dtype)
 
 
 class BSQFn(torch.autograd.Function):
@@ -275,48 +286,11 @@ class BSQFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, w_in, b_in, w_out, b_out, cfg, out_dtype):
-        core._require_gpu(z)
-        d, g, beta, ratio, gamma, tau = int(cfg[0]), int(cfg[1]), float(cfg[2]), float(cfg[3]), float(cfg[4]), float(cfg[5])
-        d = _bsq_bits(d)
-        if not 1 <= g <= BSQ_MAX_GROUP_BITS:
-            raise ValueError(f'bsq: ent_group_bits must be between 1 and {BSQ_MAX_GROUP_BITS}, got {g}')
-        ctx.params = (w_in, b_in, w_out, b_out)
-        z, flat, (wi, bi, wo, bo), q, idx, u = _forward_buffers('bsq', 'bits', z, ctx.params, d, out_dtype)
-        n, dm = flat.shape
-        r = torch.empty(n, dtype=torch.float32, device=z.device)
-        hist = torch.zeros(1 << d, dtype=torch.int32, device=z.device)
-        out = torch.empty(4, dtype=torch.float32, device=z.device)
-        ltab = torch.empty(((d + g - 1) // g) << g, dtype=torch.float32, device=z.device)
-        lib = _native.lib()
-        nbytes = lib.vqk_bsq_ws_bytes(n, dm, d, g)
-        if nbytes < 0:
-            _native.check(int(nbytes), 'bsq_ws_bytes')
-        ws = core.grow_ws(_BSQ_WS, z.device, max(nbytes, 16))
-        _native.check(lib.vqk_bsq_forward(flat.data_ptr(), wi.data_ptr(), bi.data_ptr(), wo.data_ptr(), bo.data_ptr(), n, dm, d, g, tau,
-                                          beta, ratio, gamma, idx.data_ptr(), u.data_ptr(), r.data_ptr(), *_q_ptrs(q), hist.data_ptr(),
-                                          out.data_ptr(), ltab.data_ptr(), ws.data_ptr(), ws.numel(), core._stream()), 'bsq_forward')
-        ctx.save_for_backward(z, u, r, wi, wo, ltab)
-        ctx.cfg = (n, dm, d, g, beta, ratio, gamma, tau)
-        loss, parts = out[0], out[1:]
-        ctx.mark_non_differentiable(idx, hist, parts)
-        return q, idx.view(z.shape[0], z.shape[2] * z.shape[3]), loss, hist, parts
+        return _sign_forward('bsq', ctx, z, w_in, b_in, w_out, b_out, cfg, out_dtype)
 
     @staticmethod
     def backward(ctx, dq, _didx, dloss, _dhist, _dparts):
-        z, u, r, wi, wo, ltab = ctx.saved_tensors
-        n, dm, d, g, beta, ratio, gamma, tau = ctx.cfg
-        dqc = _cotangent(dq, z)
-        # the loss cotangent stays on the device (a captured graph follows it); an unused loss contributes nothing
-        gs = dloss.to(torch.float32).contiguous() if dloss is not None else torch.zeros((), dtype=torch.float32, device=z.device)
-        dz = torch.empty_like(z, memory_format=core._CL)
-        tgt, direct = _grad_targets(ctx.params)
-        lib = _native.lib()
-        ws = core.grow_ws(_BSQ_WS, z.device, max(lib.vqk_bsq_ws_bytes(n, dm, d, g), 16))
-        _native.check(lib.vqk_bsq_backward(z.data_ptr(), u.data_ptr(), r.data_ptr(), dqc.data_ptr(), core.dcode(dqc.dtype), wi.data_ptr(),
-                                           wo.data_ptr(), ltab.data_ptr(), gs.data_ptr(), n, dm, d, g, tau, beta, ratio, gamma,
-                                           dz.data_ptr(), *(t.data_ptr() for t in tgt), int(direct), ws.data_ptr(), ws.numel(),
-                                           core._stream()), 'bsq_backward')
-        return _grads(ctx, dz, tgt, direct)
+        return _sign_backward('bsq', ctx, dq, dloss)
 
 
 __all__ = [_n for _n in dir() if not _n.startswith('__') and _n not in ('core', 'annotations', 'ctypes', 'math')]

@@ -3,8 +3,8 @@
 // The token of a latent row z_i is the argmax of the logits S_ij = (z_i . e_j) / T over the codebook e[K][D]; the one-hot that gathers
 // the code is made differentiable with a straight-through estimator on P = softmax_j(S), so a step sends gradient to EVERY code and
 // the encoder is trained through the logits.  The soft part is attention with Q = the latent rows and K = V = the codebook, and the
-// kernels are the fp32 forms of csrc/attn.hip (on copies of its tile helpers) with a query count that differs from the key count and
-// an argmax carried beside the running maximum.  One workgroup = 4 waves = one 64-row tile:
+// kernels are the fp32 forms of csrc/attn.hip (on the same tile helpers, mfma_tile.h) with a query count that differs from the key
+// count and an argmax carried beside the running maximum.  One workgroup = 4 waves = one 64-row tile:
 //   forward : owns 64 latent rows, walks the codes in tiles of 64 (online softmax; m, l, lse, the argmax in fp32 / int32), then
 //             gathers q = e[idx], sums |q - z|^2 of its rows and counts the tokens
 //   rows    : G = g + s c2 (q - z), H = G + s beta c2 (q - z), delta = G . ebar, dz = -2 s c2 (q - z): one wave per row
@@ -20,71 +20,17 @@
 // The argmax-only mode (lse == NULL) runs the same logit arithmetic (same tiles, same MFMA order, same scaling) and skips the
 // exponentials and the second product: the same tokens, bit for bit.
 #include "common.h"
+#include "mfma_tile.h"
 
 #include <limits.h>
 #include <math.h>
 
 namespace {
 
-constexpr int AT = 64;           // tile rows (latent rows or codes) of a workgroup, and the d chunk
-constexpr int LD = 68;           // fp32 tile pitch: 272 B rows, 16-byte aligned, rows 4 banks apart
+constexpr int LD = Pitch<float>::LD;     // fp32 tile pitch
 constexpr int TB = AT * LD;
 
 static inline bool ibq_d_ok(int d) { return d == 64 || d == 128 || d == 256; }
-
-// row of a 32x32 accumulator register (the column is lane & 31)
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
-__device__ __forceinline__ void acc_zero(f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.0f;
-}
-
-// One 64 x 64 fp32 tile on its way from global memory to LDS, held in registers in between (the loads of the NEXT step are issued
-// before the MFMAs of the current one)
-struct TileRegs { vqk_u32x4 v[4]; };
-
-// regs <- src[row0 + r][c0 + c] (row pitch ld), rows past n are zeros (never read)
-__device__ __forceinline__ void gload(TileRegs& t, const float* __restrict__ src, int64_t ld, int row0, int n, int c0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = threadIdx.x + 256 * j, r = i >> 4, v = i & 15;
-        vqk_u32x4 x = {0u, 0u, 0u, 0u};
-        if (row0 + r < n) x = *reinterpret_cast<const vqk_u32x4*>(src + (int64_t)(row0 + r) * ld + c0 + v * 4);
-        t.v[j] = x;
-    }
-}
-__device__ __forceinline__ void lstore(float* __restrict__ dst, const TileRegs& t) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = threadIdx.x + 256 * j, r = i >> 4, v = i & 15;
-        *reinterpret_cast<vqk_u32x4*>(dst + r * LD + v * 4) = t.v[j];
-    }
-}
-
-// acc[i][j] += sum_k a[i][k] b[j][k], k < 64; a and b point at the first of the wave's 32 rows
-__device__ __forceinline__ void mma_nt(f32x16& acc, const float* a, const float* b, int lane) {
-    const float* pa = a + (lane & 31) * LD + 4 * (lane >> 5);
-    const float* pb = b + (lane & 31) * LD + 4 * (lane >> 5);
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const f32x4 va = *reinterpret_cast<const f32x4*>(pa + 8 * s);
-        const f32x4 vb = *reinterpret_cast<const f32x4*>(pb + 8 * s);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(va[j], vb[j], acc, 0, 0, 0);
-    }
-}
-// acc[i][j] += sum_k a[i][k] b[k][col0 + j]
-__device__ __forceinline__ void mma_ab(f32x16& acc, const float* a, const float* b, int col0, int lane) {
-    const float* pa = a + (lane & 31) * LD + 4 * (lane >> 5);
-    const float* pb = b + 4 * (lane >> 5) * LD + col0 + (lane & 31);
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const f32x4 va = *reinterpret_cast<const f32x4*>(pa + 8 * s);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(va[j], pb[(8 * s + j) * LD], acc, 0, 0, 0);
-    }
-}
 
 struct IbqArgs {
     const float *z, *e;
@@ -128,7 +74,7 @@ __global__ __launch_bounds__(256) void ibq_fwd_kernel(const IbqArgs a) {
     float m = -INFINITY, l = 0.0f;                               // the same in the 4 threads of a row
     int best = 0;
 
-    TileRegs ra, rb;                                             // the next step's tiles, in flight
+    TileRegs<float> ra, rb;                                             // the next step's tiles, in flight
     gload(ra, zb, D, q0, n, 0);
     gload(rb, eb, D, 0, k, 0);
     for (int k0 = 0; k0 < k; k0 += AT) {
@@ -351,7 +297,7 @@ __global__ __launch_bounds__(256) void ibq_de_kernel(const IbqArgs a) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) { acc_zero(soft[c]); acc_zero(hard[c]); }
 
-    TileRegs ra, rb;
+    TileRegs<float> ra, rb;
     gload(ra, a.e, D, k0, k, 0);
     gload(rb, a.z, D, 0, n, 0);
     for (int q0 = 0; q0 < n; q0 += AT) {
@@ -444,7 +390,7 @@ __global__ __launch_bounds__(256) void ibq_dz_kernel(const IbqArgs a) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) acc_zero(acc[c]);
 
-    TileRegs ra, rb;
+    TileRegs<float> ra, rb;
     gload(ra, a.z, D, q0, n, 0);
     gload(rb, a.e, D, 0, k, 0);
     for (int k0 = 0; k0 < k; k0 += AT) {

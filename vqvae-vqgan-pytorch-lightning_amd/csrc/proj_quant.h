@@ -1,5 +1,6 @@
-// The core the projection quantizers share (fsq.hip, lfq.hip): u = W_in z + b_in, a code c per channel, q = W_out c + b_out, and the
-// straight-through backward with its ordered parameter-gradient sums.
+// The core the projection quantizers share (fsq.hip, lfq.hip, bsq.hip): u = W_in z + b_in, a code c per channel, q = W_out c + b_out,
+// and the straight-through backward with its ordered parameter-gradient sums.  What only the two sign quantizers share (sigmoid /
+// entropy, group tables, finish and decode kernels, host launchers) is sign_quant.h, on top of this file.
 //
 // Every kernel works a WAVE PER ROW.  Lane l owns the 16-byte chunks l, l + 64, ... of the row (4 fp32 channels each), so every global
 // access of z / q / dq / dz is 16 bytes per lane (8 bytes for 4 packed bf16) and contiguous over the wave.  W_in [d][D] and W_out^T

@@ -317,28 +317,26 @@ class FSQuantizer(_ProjectionQuantizer):
         return q, idx, loss
 
 
-class LFQuantizer(_ProjectionQuantizer):
-    """Lookup-free quantization (Yu et al. 2023, MAGVIT-v2; Open-MAGVIT2): the D-channel latent is projected to ``bits`` channels, each
-    is quantized to its sign, the bit pattern is the token (K = 2^bits, first channel = bit 0) and the sign vector is projected back
-    to D channels.  loss = commitment_cost * commit + ent_loss_ratio * (H_sample - diversity_gamma * H_batch): the per-position
-    entropy keeps the bits confident, the entropy of the batch-average distribution -- factorised over groups of ``ent_group_bits``
-    bits -- keeps the vocabulary evenly used.  No learned codebook, no search, no dead codes, no collective (data parallel, the batch
-    average is per rank, as the entropy quantizer's statistics are); training and evaluation behave the same.  One fused kernel each
-    way (csrc/lfq.hip).  ``codebook`` holds the IMPLICIT codebook, frozen: row i = the +-1 vector of token i.  ``last_parts`` =
-    (commit, H_sample, H_batch) of the last forward, on the device, for logging."""
-    kind = 'lfq'
+class _SignQuantizer(_ProjectionQuantizer):
+    """What the sign quantizers share (``LFQuantizer``, ``BSQuantizer``; kernel core csrc/sign_quant.h): ``bits`` channels quantized
+    to their sign, token = the bit pattern, loss = commitment_cost * commit + ent_loss_ratio * (H_sample - diversity_gamma * H_batch).
+    A subclass sets ``kind``, its autograd Function ``Fn``, its default ``ent_temperature`` and the scale of the +-1 table in
+    ``implicit_codebook()``; ``ops.<kind>_assign`` / ``ops.<kind>_decode`` and ``ops.<KIND>_MAX_*`` are found by ``kind``."""
+    Fn = None
 
-    def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float = 0.25, ent_loss_ratio: float = 0.1,
-                 ent_temperature: float = 0.01, diversity_gamma: float = 1.0, ent_group_bits: int = 9):
+    def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float, ent_loss_ratio: float,
+                 ent_temperature: float, diversity_gamma: float, ent_group_bits: int):
+        kind = self.kind
+        max_bits, max_group = getattr(ops, f'{kind.upper()}_MAX_BITS'), getattr(ops, f'{kind.upper()}_MAX_GROUP_BITS')
         bits, ent_group_bits = int(bits), int(ent_group_bits)
-        if not 1 <= bits <= ops.LFQ_MAX_BITS:
-            raise ValueError(f'lfq: bits must be between 1 and {ops.LFQ_MAX_BITS}, got {bits}')
+        if not 1 <= bits <= max_bits:
+            raise ValueError(f'{kind}: bits must be between 1 and {max_bits}, got {bits}')
         if num_embeddings != 2 ** bits:
-            raise ValueError(f'lfq: num_embeddings = {num_embeddings} must equal 2**bits = {2 ** bits}')
-        if not 1 <= ent_group_bits <= ops.LFQ_MAX_GROUP_BITS:
-            raise ValueError(f'lfq: ent_group_bits must be between 1 and {ops.LFQ_MAX_GROUP_BITS}, got {ent_group_bits}')
+            raise ValueError(f'{kind}: num_embeddings = {num_embeddings} must equal 2**bits = {2 ** bits}')
+        if not 1 <= ent_group_bits <= max_group:
+            raise ValueError(f'{kind}: ent_group_bits must be between 1 and {max_group}, got {ent_group_bits}')
         if not float(ent_temperature) > 0.0:
-            raise ValueError(f'lfq: ent_temperature must be > 0, got {ent_temperature}')
+            raise ValueError(f'{kind}: ent_temperature must be > 0, got {ent_temperature}')
         super().__init__(num_embeddings, embedding_dim, bits)
         self.bits, self.ent_group_bits = bits, ent_group_bits
         self.commitment_cost, self.ent_loss_ratio = float(commitment_cost), float(ent_loss_ratio)
@@ -347,24 +345,45 @@ class LFQuantizer(_ProjectionQuantizer):
         self.init_codebook()
 
     def _assign(self, flat_z: torch.Tensor) -> torch.Tensor:
-        return ops.lfq_assign(flat_z, self.project_in.weight, self.project_in.bias, self.bits)
+        return getattr(ops, f'{self.kind}_assign')(flat_z, self.project_in.weight, self.project_in.bias, self.bits)
 
     def _decode(self, codes: torch.Tensor) -> torch.Tensor:
-        return ops.lfq_decode(codes, self.project_out.weight, self.project_out.bias, self.bits)
+        return getattr(ops, f'{self.kind}_decode')(codes, self.project_out.weight, self.project_out.bias, self.bits)
 
-    def implicit_codebook(self) -> torch.Tensor:
+    def _signs(self) -> torch.Tensor:
         """[K, bits] fp32: row i, column j = +1 if bit j of i is set, else -1"""
         tokens = torch.arange(self.num_embeddings, dtype=torch.int64)
         return (((tokens[:, None] >> torch.arange(self.bits)) & 1) * 2 - 1).to(torch.float32)
 
     def forward(self, x: torch.Tensor):
         cfg = (self.bits, self.ent_group_bits, self.commitment_cost, self.ent_loss_ratio, self.diversity_gamma, self.ent_temperature)
-        q, idx, loss, hist, parts = ops.LFQFn.apply(x, *self._projections(), cfg, self.compute_dtype)
+        q, idx, loss, hist, parts = self.Fn.apply(x, *self._projections(), cfg, self.compute_dtype)
         self.last_hist, self.last_parts = hist, parts
         return q, idx, loss
 
 
-class BSQuantizer(_ProjectionQuantizer):
+class LFQuantizer(_SignQuantizer):
+    """Lookup-free quantization (Yu et al. 2023, MAGVIT-v2; Open-MAGVIT2): the D-channel latent is projected to ``bits`` channels, each
+    is quantized to its sign, the bit pattern is the token (K = 2^bits, first channel = bit 0) and the sign vector is projected back
+    to D channels.  loss = commitment_cost * commit + ent_loss_ratio * (H_sample - diversity_gamma * H_batch): the per-position
+    entropy keeps the bits confident, the entropy of the batch-average distribution -- factorised over groups of ``ent_group_bits``
+    bits -- keeps the vocabulary evenly used.  No learned codebook, no search, no dead codes, no collective (data parallel, the batch
+    average is per rank, as the entropy quantizer's statistics are); training and evaluation behave the same.  One fused kernel each
+    way (csrc/lfq.hip).  ``codebook`` holds the IMPLICIT codebook, frozen: row i = the +-1 vector of token i.  ``last_parts`` =
+    (commit, H_sample, H_batch) of the last forward, on the device, for logging."""
+    kind, Fn = 'lfq', ops.LFQFn
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float = 0.25, ent_loss_ratio: float = 0.1,
+                 ent_temperature: float = 0.01, diversity_gamma: float = 1.0, ent_group_bits: int = 9):
+        super().__init__(num_embeddings, embedding_dim, bits, commitment_cost, ent_loss_ratio, ent_temperature, diversity_gamma,
+                         ent_group_bits)
+
+    def implicit_codebook(self) -> torch.Tensor:
+        """[K, bits] fp32: row i, column j = +1 if bit j of i is set, else -1"""
+        return self._signs()
+
+
+class BSQuantizer(_SignQuantizer):
     """Binary spherical quantization (Zhao, Xiong, Kraehenbuehl 2024, BSQ-ViT): ``LFQuantizer`` with the projected latent put on the
     unit sphere before the sign is taken -- u = v / |v|, code = the corner +-1 / sqrt(bits) of the hypercube inscribed in the sphere,
     token = the bit pattern (K = 2^bits, first channel = bit 0).  The quantization error |u - c|^2 is below 2 for every ``bits``, so the
@@ -374,42 +393,16 @@ class BSQuantizer(_ProjectionQuantizer):
     no search, no collective; training and evaluation behave the same.  One fused kernel each way (csrc/bsq.hip).  ``codebook`` holds
     the IMPLICIT codebook, frozen: row i = the +-1 / sqrt(bits) vector of token i.  ``last_parts`` = (commit, H_sample, H_batch) of the
     last forward, on the device, for logging."""
-    kind = 'bsq'
+    kind, Fn = 'bsq', ops.BSQFn
 
     def __init__(self, num_embeddings: int, embedding_dim: int, bits: int, commitment_cost: float = 0.25, ent_loss_ratio: float = 0.1,
                  ent_temperature: float = 0.02, diversity_gamma: float = 1.0, ent_group_bits: int = 9):
-        bits, ent_group_bits = int(bits), int(ent_group_bits)
-        if not 1 <= bits <= ops.BSQ_MAX_BITS:
-            raise ValueError(f'bsq: bits must be between 1 and {ops.BSQ_MAX_BITS}, got {bits}')
-        if num_embeddings != 2 ** bits:
-            raise ValueError(f'bsq: num_embeddings = {num_embeddings} must equal 2**bits = {2 ** bits}')
-        if not 1 <= ent_group_bits <= ops.BSQ_MAX_GROUP_BITS:
-            raise ValueError(f'bsq: ent_group_bits must be between 1 and {ops.BSQ_MAX_GROUP_BITS}, got {ent_group_bits}')
-        if not float(ent_temperature) > 0.0:
-            raise ValueError(f'bsq: ent_temperature must be > 0, got {ent_temperature}')
-        super().__init__(num_embeddings, embedding_dim, bits)
-        self.bits, self.ent_group_bits = bits, ent_group_bits
-        self.commitment_cost, self.ent_loss_ratio = float(commitment_cost), float(ent_loss_ratio)
-        self.ent_temperature, self.diversity_gamma = float(ent_temperature), float(diversity_gamma)
-        self.last_parts = None
-        self.init_codebook()
-
-    def _assign(self, flat_z: torch.Tensor) -> torch.Tensor:
-        return ops.bsq_assign(flat_z, self.project_in.weight, self.project_in.bias, self.bits)
-
-    def _decode(self, codes: torch.Tensor) -> torch.Tensor:
-        return ops.bsq_decode(codes, self.project_out.weight, self.project_out.bias, self.bits)
+        super().__init__(num_embeddings, embedding_dim, bits, commitment_cost, ent_loss_ratio, ent_temperature, diversity_gamma,
+                         ent_group_bits)
 
     def implicit_codebook(self) -> torch.Tensor:
         """[K, bits] fp32: row i, column j = +1 / sqrt(bits) if bit j of i is set, else -1 / sqrt(bits)"""
-        tokens = torch.arange(self.num_embeddings, dtype=torch.int64)
-        return (((tokens[:, None] >> torch.arange(self.bits)) & 1) * 2 - 1).to(torch.float32) / math.sqrt(self.bits)
-
-    def forward(self, x: torch.Tensor):
-        cfg = (self.bits, self.ent_group_bits, self.commitment_cost, self.ent_loss_ratio, self.diversity_gamma, self.ent_temperature)
-        q, idx, loss, hist, parts = ops.BSQFn.apply(x, *self._projections(), cfg, self.compute_dtype)
-        self.last_hist, self.last_parts = hist, parts
-        return q, idx, loss
+        return self._signs() / math.sqrt(self.bits)
 
 
 class ResidualVectorQuantizer(BaseVectorQuantizer):
