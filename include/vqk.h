@@ -255,6 +255,25 @@ int vqk_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o
 int vqk_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse, const void* dout, void* dq,
                  void* dk, void* dv, float* delta, int b, int n, int heads, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
                  int64_t lddo, int64_t lddq, int64_t lddk, int64_t lddv, float scale, void* stream);
+/* ---------------------------------------------------------------- spatially conditioned GroupNorm ---------
+ * csrc/spnorm.hip (MoVQ's spatially conditional normalisation).  f, out, dy, df [N][H][W][C] of `dtype`; m, a [N][h][w][C] fp32
+ * modulation tables at the latent resolution, H = r h, W = r w:  u = GroupNorm_32(f) * gamma + beta (per (sample, group) mean and
+ * UNBIASED variance, as vqk_gn_*);  out = act(u * m[n][i / r][j / r] + a[n][i / r][j / r]), act = identity or SiLU (silu != 0).
+ * stats[N][32] = {mean, rstd} fp32 is written by the forward and read by the backward, which recomputes the pre-activation from f.
+ * backward: dm, da [N][h][w][C] fp32 are STORED (the r x r block of a latent pixel is summed by one workgroup); dgamma, dbeta [C] are
+ * ADDED onto what the targets hold; df is stored.  Group and channel sums leave their workgroups as partials in ws and are added in a
+ * fixed order: no float atomics, the same bits on every run in every mode.
+ * Served: groups == 32, c % 32 == 0, c <= 512, r in {1, 2, 4, 8, 16, 32}, 1 <= n <= 65535, h w < 2^24, H W < 2^31 (VQK_ERR_SHAPE
+ * otherwise, also from the size query; nothing launched).  f, out, dy, df, m, a, ws 16-byte aligned (VQK_ERR_ALIGN); ws_bytes >=
+ * vqk_spnorm_ws_bytes (a function of the shape; one size serves forward and backward: VQK_ERR_WORKSPACE).  ws needs no initial
+ * contents.  No call allocates or synchronises. */
+int64_t vqk_spnorm_ws_bytes(int dtype, int n, int h, int w, int r, int c);
+int vqk_spnorm_forward(int dtype, const void* f, const float* m, const float* a, const float* gamma, const float* beta, void* out,
+                       float* stats, void* ws, int64_t ws_bytes, int n, int h, int w, int r, int c, int groups, float eps, int silu,
+                       void* stream);
+int vqk_spnorm_backward(int dtype, const void* f, const float* stats, const float* m, const float* a, const float* gamma,
+                        const float* beta, const void* dy, void* df, float* dm, float* da, float* dgamma, float* dbeta, void* ws,
+                        int64_t ws_bytes, int n, int h, int w, int r, int c, int groups, int silu, void* stream);
 /* ---------------------------------------------------------------- residual quantizer ---------
  * Lee et al. 2022 (RQ-VAE) / SoundStream (csrc/rvq.hip).  z[N][D] fp32 rows, ONE codebook e[K][D] shared by the `depth` stages:
  * r_0 = z; k_q = argmin_k (|r_{q-1}|^2 + |e_k|^2) - 2 r_{q-1}.e_k (the arithmetic of vqk_vq_forward_f32 with assoc 0, first minimum

@@ -179,7 +179,8 @@ class VQVAE(BaseVQVAE, _LightningBase):
         attn = dict(attn_resolutions=ae_conf.get('attn_resolutions'), attn_heads=1 if attn_heads is None else attn_heads,
                     image_size=image_size)
         self.encoder = Encoder(ch, nrb, mult, self.cb_size if qt == 'gumbel' else self.latent_dim, **attn)   # model.py:130
-        self.decoder = Decoder(ch, nrb, mult, self.latent_dim, **attn)
+        # optional: decoder_norm: spatial -- every decoder norm modulated by the quantized latent (MoVQ); absent: group
+        self.decoder = Decoder(ch, nrb, mult, self.latent_dim, **attn, norm=ae_conf.get('decoder_norm'))
 
         if load_loss:
             if l_conf is None:

@@ -6,6 +6,9 @@ Encoder :109-143, Decoder :146-180); the arithmetic is the NHWC kernel set behin
 GroupNorm+SiLU is one fused op, the residual add rides in the conv epilogue, the nearest x2 upsample is
 folded into the conv's input addressing, tanh into the last conv's epilogue.
 
+``Decoder(norm='spatial')`` (config ``autoencoder.decoder_norm``) is this project's own: every decoder norm becomes a
+:class:`SpatialNorm` modulated by the decoder's input (MoVQ); the default ``'group'`` is the reference's decoder.
+
 ``compute_dtype`` (module attribute, set with :func:`set_compute_dtype`) selects the exact-fp32 MFMA path
 (parity mode, default) or bf16 storage / bf16 MFMA with fp32 accumulation (throughput mode).
 """
@@ -127,6 +130,62 @@ class AttnBlock(nn.Module):
         return self.proj_out(a, residual=x)
 
 
+class SpatialNorm(nn.Module):
+    """MoVQ's spatially conditional normalisation with the parameter names of MoVQ / diffusers (``norm_layer``, ``conv_y``,
+    ``conv_b``): GroupNorm(f) * conv_y(zq) + conv_b(zq), the two 1x1 convs evaluated at the LATENT resolution (nearest upsampling by
+    an integer ratio commutes with a 1x1 conv) and indexed by the kernel with i // r, j // r; SiLU optionally fused behind it.
+    ``norm_layer`` is this project's GroupNorm (unbiased variance), affine [1, C, 1, 1]."""
+
+    def __init__(self, f_channels: int, zq_channels: int):
+        super().__init__()
+        self.norm_layer = GroupNorm(32, f_channels, eps=1e-6)
+        self.conv_y = Conv2d(zq_channels, f_channels, 1, bias=True)
+        self.conv_b = Conv2d(zq_channels, f_channels, 1, bias=True)
+
+    def forward(self, f: torch.Tensor, zq: torch.Tensor, silu: bool = False) -> torch.Tensor:
+        # zq: the decoder's input in its internal form (NHWC, compute dtype); the tables are fp32 in every compute mode
+        m = self.conv_y(zq, out_dtype=torch.float32)
+        a = self.conv_b(zq, out_dtype=torch.float32)
+        return ops.spatial_norm(f, m, a, self.norm_layer.weight, self.norm_layer.bias, self.norm_layer.num_groups,
+                                self.norm_layer.eps, silu)
+
+
+class SpatialResBlock(nn.Module):
+    """ResBlock whose two norms are conditioned on the quantized latent (``Decoder(norm='spatial')``): a composed block on
+    ``ops.spatial_norm`` and ``ops.conv2d`` nodes (the fused ``ops.res_block`` node takes per-channel affines only); the residual
+    add still rides in conv2's epilogue.  Same attribute names as :class:`ResBlock`."""
+
+    def __init__(self, in_channels: int, out_channels: int, zq_channels: int):
+        super().__init__()
+        if out_channels is None or out_channels == in_channels:
+            out_channels = in_channels
+            self.conv_shortcut = None
+        else:
+            self.conv_shortcut = Conv2d(in_channels, out_channels, 1, bias=False)
+        self.norm1 = SpatialNorm(in_channels, zq_channels)
+        self.conv1 = Conv2d(in_channels, out_channels, 3, bias=False)
+        self.norm2 = SpatialNorm(out_channels, zq_channels)
+        self.conv2 = Conv2d(out_channels, out_channels, 3, bias=False)
+
+    def forward(self, x, zq):
+        h = self.conv1(self.norm1(x, zq, silu=True))
+        h = self.norm2(h, zq, silu=True)
+        return self.conv2(h, residual=x if self.conv_shortcut is None else self.conv_shortcut(x))
+
+
+class SpatialAttnBlock(AttnBlock):
+    """:class:`AttnBlock` whose ``norm`` is conditioned on the quantized latent"""
+
+    def __init__(self, in_channels: int, heads: int, zq_channels: int):
+        super().__init__(in_channels, heads)
+        self.norm = SpatialNorm(in_channels, zq_channels)
+
+    def forward(self, x, zq):
+        h = self.norm(x, zq)
+        a = ops.attention(self.q(h), self.k(h), self.v(h), self.heads)
+        return self.proj_out(a, residual=x)
+
+
 def attn_sides(attn_resolutions, image_size) -> tuple:
     """the config's ``attn_resolutions`` as a tuple of map sides; absent, None or empty: no attention anywhere"""
     if attn_resolutions is None:
@@ -143,15 +202,29 @@ def attn_sides(attn_resolutions, image_size) -> tuple:
     return tuple(sides)
 
 
-def _res_level(ch_in: int, ch_out: int, count: int, side, sides: tuple, heads: int) -> list:
-    """``count`` ResBlocks at one map side, each followed by an AttnBlock when that side is an attention resolution"""
+def _res_level(ch_in: int, ch_out: int, count: int, side, sides: tuple, heads: int, zq_channels: int = None) -> list:
+    """``count`` ResBlocks at one map side, each followed by an AttnBlock when that side is an attention resolution;
+    ``zq_channels``: the blocks' norms are spatially conditioned on a latent of that many channels"""
     out = []
     for _ in range(count):
-        out.append(ResBlock(ch_in, ch_out))
+        out.append(ResBlock(ch_in, ch_out) if zq_channels is None else SpatialResBlock(ch_in, ch_out, zq_channels))
         ch_in = ch_out
         if side in sides:
-            out.append(AttnBlock(ch_out, heads))
+            out.append(AttnBlock(ch_out, heads) if zq_channels is None else SpatialAttnBlock(ch_out, heads, zq_channels))
     return out
+
+
+DECODER_NORMS = ('group', 'spatial')
+
+
+def decoder_norm_kind(value) -> str:
+    """the config's ``autoencoder.decoder_norm``: absent / None -> 'group' (a GroupNorm in every decoder block), 'spatial' (every
+    decoder norm modulated by the quantized latent, MoVQ); anything else is an error"""
+    if value is None:
+        return 'group'
+    if not isinstance(value, str) or value not in DECODER_NORMS:
+        raise ValueError(f"autoencoder.decoder_norm must be 'group' or 'spatial', got {value!r}")
+    return value
 
 
 class Downsample(nn.Module):
@@ -260,29 +333,41 @@ class Encoder(nn.Module):
 
 class Decoder(nn.Module):
     def __init__(self, channels: int, num_res_blocks: int, channel_multipliers: tuple, embedding_dim: int,
-                 attn_resolutions=None, attn_heads: int = 1, image_size: int = None):
+                 attn_resolutions=None, attn_heads: int = 1, image_size: int = None, norm: str = 'group'):
         super().__init__()
         self.compute_dtype = torch.float32
+        self.norm_kind = decoder_norm_kind(norm)
+        zqc = embedding_dim if self.norm_kind == 'spatial' else None
         sides = attn_sides(attn_resolutions, image_size)
         side = image_size // (2 ** len(channel_multipliers)) if sides else None
         ch_in = channels * channel_multipliers[-1]
         self.conv_in = Conv2d(embedding_dim, ch_in, 3, bias=True)
-        self.initial_residual = nn.Sequential(*_res_level(ch_in, ch_in, num_res_blocks, side, sides, attn_heads))
+        self.initial_residual = nn.Sequential(*_res_level(ch_in, ch_in, num_res_blocks, side, sides, attn_heads, zqc))
         blocks = []
         for i in reversed(range(len(channel_multipliers))):
             ch_out = channels * channel_multipliers[i - 1] if i > 0 else channels
-            blocks += _res_level(ch_in, ch_out, num_res_blocks, side, sides, attn_heads)
+            blocks += _res_level(ch_in, ch_out, num_res_blocks, side, sides, attn_heads, zqc)
             ch_in = ch_out
             blocks.append(Upsample(ch_out))
             side = side * 2 if sides else side
         self.blocks = nn.Sequential(*blocks)
-        self.norm = GroupNorm(32, channels, eps=1e-6)
+        self.norm = GroupNorm(32, channels, eps=1e-6) if zqc is None else SpatialNorm(channels, zqc)
         self.conv_out = Conv2d(channels, 3, 3, bias=True)
+
+    def _forward_spatial(self, zq):
+        """every norm takes the decoder's input: composed blocks, no GroupNorm sums ride in the convs (next_gn = 0)"""
+        x = self.conv_in(zq)
+        for blk in list(self.initial_residual) + list(self.blocks):
+            x = blk(x) if isinstance(blk, Upsample) else blk(x, zq)
+        x = self.norm(x, zq, silu=True)
+        return self.conv_out(x, act=1)                        # tanh in the epilogue
 
     def forward_padded(self, x):
         """reconstruction with its zero pad channels ([N, 4 or 8, H, W], NHWC) -- what the fused loss reads"""
         ops.set_conv_products(getattr(self, 'conv_products', 'fp32'))
         x = _to_internal(x, self.compute_dtype)
+        if self.norm_kind == 'spatial':
+            return self._forward_spatial(x)
         x = self.conv_in(x)
         # a ResBlock / Upsample output is read next by a 32-group GroupNorm (the next block's norm1, finally self.norm)
         # unless an Upsample conv follows it

@@ -2194,6 +2194,7 @@ SIMVQ_PROJECT = _native.switch('VQK_SIMVQ_PROJECT', '0') == '1'  # SimVQ quantiz
 IBQ_FUSED = _native.switch('VQK_IBQ_FUSED', '1') != '0'    # IBQ quantizer: the fused online-softmax + argmax forward and the three-launch atomic-free backward (0: the staged formulation, _ops_ibq.ibq_staged)
 COS_FUSED = _native.switch('VQK_COS_FUSED', '1') != '0'    # cosine quantizer: the one-launch normalise + rank + gather forward (0: the staged formulation, _ops_cos.cos_staged)
 ATTN_FUSED = _native.switch('VQK_ATTN_FUSED', '1') != '0'   # self-attention: the fused forward / backward kernels (0: the staged formulation, _ops_attn.attention_staged)
+SPNORM_FUSED = _native.switch('VQK_SPNORM_FUSED', '1') != '0'   # spatially conditioned GroupNorm: the fused statistics / apply / two-sweep backward kernels (0: the staged formulation, _ops_spnorm.spatial_norm_staged)
 ENTROPY_FUSED_ROWS = _native.switch('VQK_ENTROPY_FUSED_ROWS', '1') != '0'
 ENTROPY_SPLIT_GEMM = _native.switch('VQK_ENTROPY_SPLIT_GEMM', '1') != '0'     # bf16 compute mode: the entropy cotangent's two GEMMs as bf16 split products
 ACT_CODE = {'linear': 0, 'tanh': 1, 'relu': 2, 'lrelu': 3}
@@ -2274,5 +2275,6 @@ from ._ops_simvq import *     # noqa: E402,F401,F403  SimVQ quantizer
 from ._ops_ibq import *       # noqa: E402,F401,F403  index-backpropagation quantizer
 from ._ops_kmeans import *    # noqa: E402,F401,F403  k-means codebook initialisation
 from ._ops_attn import *      # noqa: E402,F401,F403  self-attention core
+from ._ops_spnorm import *    # noqa: E402,F401,F403  spatially conditioned GroupNorm (decoder_norm: spatial)
 from ._ops_gan import *       # noqa: E402,F401,F403  VQ-GAN loss path, the reference's two plugins
 from ._ops_patchgan import *  # noqa: E402,F401,F403  PatchGAN discriminator: 4x4 convs, BatchNorm
