@@ -775,6 +775,12 @@ int vqk_conv2d_wgrad_edge(int dtype, const void* x, const void* dy, float* dw, v
  * the sums of the zero-padded channels are dropped.  thin_true = 8: vqk_conv2d_wgrad_edge. */
 int vqk_conv2d_wgrad_edge_true(int dtype, const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes, int n, int h,
                                int w, int cin, int cout, int thin_true, const void* zeros, void* stream);
+/* vqk_conv2d_wgrad_edge_true that also sums the bias gradient of the LAST conv ((cin, cout) = (128, 8); VQK_ERR_ARG otherwise):
+ * db[c] += sum over pixels of dy[pixel][c] for c < thin_true, gathered from the kernel's own staged copy of dy (no second pass
+ * over dy), one fp32 atomic per channel and block -- order-dependent in the last bits, so deterministic mode keeps vqk_colsum_lead.
+ * db = NULL: vqk_conv2d_wgrad_edge_true.  dw is bit-identical either way. */
+int vqk_conv2d_wgrad_edge_bias(int dtype, const void* x, const void* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int n,
+                               int h, int w, int cin, int cout, int thin_true, const void* zeros, void* stream);
 /* The decoder's last conv (autoencoder.py:170): 3x3, stride 1, 'same', cin = 128 -> cout = 8 (the 3 image channels padded to
  * one 16-byte chunk), y = act(conv(x, w) + bias) with act 0 none / 1 tanh; bf16 in and out, h % 8 == 0, w % 32 == 0;
  * w: bf16 [8][3][3][128] (weight layout 0).  VQK_ERR_SHAPE when not served (nothing launched: callers use vqk_conv2d_fprop). */
@@ -813,6 +819,16 @@ int vqk_gn_forward_presummed(int dtype, const void* x, const float* w, const flo
 int vqk_gn_forward_presummed_parts(int dtype, const void* x, const float* w, const float* b, void* y, float* stats,
                                    const double* parts, int nblk, double* sums, int n, int64_t hw, int c, int groups, float eps,
                                    int silu, void* stream);
+/* vqk_gn_forward_presummed / _parts whose apply pass ALSO stores the 2x2 average of its input (the skip of a pooling ResBlock):
+ * pooled[n][h/2][w/2][c] = ((x00 + x01) + (x10 + x11)) * pool_scale, bit for bit what vqk_pool2x2(x, pool_scale) stores, for one
+ * quarter-size store instead of a pass of its own; y and stats are those of the unpooled call.  Blocks own whole row pairs.
+ * VQK_ERR_SHAPE for an odd h or w (or a map beyond 2^30 pixels / 2^20 columns): callers then run the two launches. */
+int vqk_gn_forward_presummed_pooled(int dtype, const void* x, const float* w, const float* b, void* y, float* stats, double* ws,
+                                    int n, int h, int wd, int c, int groups, float eps, int silu, void* pooled, float pool_scale,
+                                    void* stream);
+int vqk_gn_forward_presummed_parts_pooled(int dtype, const void* x, const float* w, const float* b, void* y, float* stats,
+                                          const double* parts, int nblk, double* sums, int n, int h, int wd, int c, int groups,
+                                          float eps, int silu, void* pooled, float pool_scale, void* stream);
 /* backward of y = act(GN(x)): needs x, stats, w, b and dy.  red = N*G*2+N doubles scratch with the vqk_gn_forward
  * workspace protocol (zero on entry, zero again on exit); dw/db [C] fp32 pre-zeroed (accumulated into).  accumulate != 0: dx += result; add != NULL: dx = result + add (the residual-branch
  * gradient of a ResBlock, fused instead of a separate add pass). */

@@ -139,6 +139,7 @@ _PROTOS = {
     'vqk_conv2d_wgrad_pooled_dy_phase': [I, P, P, P, I, I, I, I, I, F, P, P],
     'vqk_conv2d_wgrad_edge': [I, P, P, P, P, L, I, I, I, I, I, P, P],
     'vqk_conv2d_wgrad_edge_true': [I, P, P, P, P, L, I, I, I, I, I, I, P, P],
+    'vqk_conv2d_wgrad_edge_bias': [I, P, P, P, P, P, L, I, I, I, I, I, I, P, P],
     'vqk_conv2d_thin_out': [I, P, P, P, P, I, I, I, I, I, I, P, P],
     'vqk_colsum': [I, P, L, I, P, P],
     'vqk_colsum_lead': [I, P, L, I, I, F, P, P],
@@ -148,6 +149,8 @@ _PROTOS = {
     'vqk_gn_forward': [I, P, P, P, P, P, P, I, L, I, I, F, I, P],
     'vqk_gn_forward_presummed': [I, P, P, P, P, P, P, I, L, I, I, F, I, P],
     'vqk_gn_forward_presummed_parts': [I, P, P, P, P, P, P, I, P, I, L, I, I, F, I, P],
+    'vqk_gn_forward_presummed_pooled': [I, P, P, P, P, P, P, I, I, I, I, I, F, I, P, F, P],
+    'vqk_gn_forward_presummed_parts_pooled': [I, P, P, P, P, P, P, I, P, I, I, I, I, I, F, I, P, F, P],
     'vqk_gn_backward': [I, P, P, P, P, P, P, P, P, P, I, L, I, I, I, I, P, P],
     'vqk_gn_backward_pooled_add': [I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, F, P],
     'vqk_gn_backward_ws': [I, P, P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, I, P, P, F, P],

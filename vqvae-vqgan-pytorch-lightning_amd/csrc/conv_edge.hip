@@ -58,7 +58,12 @@ template <int MODE>
 __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_thin_kernel(const bf16_raw* __restrict__ wide,
                                                                     const bf16_raw* __restrict__ thin,
                                                                     float* __restrict__ ws, const char* __restrict__ zeros,
-                                                                    int n, int h, int w) {
+                                                                    int n, int h, int w, float* __restrict__ tsum = nullptr,
+                                                                    int tsum_n = 0) {
+    // tsum (MODE 1, optional, fp32 [tsum_n <= 8], accumulated into): the per-channel sums of the THIN tensor -- the bias gradient
+    // of the decoder's last conv (thin = dy), which was a column-sum pass of its own over dy.  The centre tap of the im2col tile
+    // is the patch's own 128 pixels of dy and the patches cover every pixel once: wave 0 adds them up from LDS (two pixels per
+    // lane and patch, off the MFMA operands' path), one atomic per channel and block at the end.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -116,6 +121,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_thin_kernel(const bf16_r
     for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+    const bool do_tsum = MODE == 1 && tsum != nullptr && wave == 0;
+    float tacc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) tacc[k] = 0.0f;
 
     if (cnt > 0) issue(b, 0);
     if (cnt > 1) issue(b + G, 1);
@@ -134,6 +143,23 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_thin_kernel(const bf16_r
                 const bf16x8_t bj = tr_frag<EDGE_IM_PITCH, false>(st + EDGE_WIDE_B, k0, 32 * j, lane);
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bj, acc[j], 0, 0, 0);
             }
+        }
+        if (MODE == 1 && do_tsum) {                              // wave-uniform
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const vqk_u32x4 v = *reinterpret_cast<const vqk_u32x4*>(st + EDGE_WIDE_B + (lane + 64 * half) * EDGE_IM_PITCH + 4 * 16);
+                float f[8];
+                Vec16<bf16_raw>::unpack(v, f);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) tacc[k] += f[k];
+            }
+        }
+    }
+    if (MODE == 1 && do_tsum) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float t = wave_sum(tacc[k]);
+            if (lane == 0 && k < tsum_n) atomicAdd(tsum + k, t);
         }
     }
     // partial of this block: acc[j][r] = out[wc = 32*wave + (r&3) + 8*(r>>2) + 4*(lane>>5)][col = 32*j + (lane&31)]
@@ -325,7 +351,13 @@ int vqk_conv2d_wgrad_edge(int dtype, const void* x, const void* dy, float* dw, v
 
 int vqk_conv2d_wgrad_edge_true(int dtype, const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes, int n, int h,
                                int w, int cin, int cout, int thin_true, const void* zeros, void* stream) {
+    return vqk_conv2d_wgrad_edge_bias(dtype, x, dy, dw, nullptr, ws, ws_bytes, n, h, w, cin, cout, thin_true, zeros, stream);
+}
+
+int vqk_conv2d_wgrad_edge_bias(int dtype, const void* x, const void* dy, float* dw, float* db, void* ws, int64_t ws_bytes, int n,
+                               int h, int w, int cin, int cout, int thin_true, const void* zeros, void* stream) {
     VQK_REQUIRE(x && dy && dw && ws && zeros, VQK_ERR_ARG);
+    VQK_REQUIRE(!db || (cout == 8 && cin == EDGE_CW), VQK_ERR_ARG);      // the bias sum rides with the LAST conv's dy only
     VQK_REQUIRE(thin_true >= 1 && thin_true <= 8, VQK_ERR_ARG);
     VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy) && vqk_aligned16(ws) && vqk_aligned16(zeros), VQK_ERR_ALIGN);
     VQK_REQUIRE(dtype == VQK_BF16, VQK_ERR_DTYPE);
@@ -350,7 +382,7 @@ int vqk_conv2d_wgrad_edge_true(int dtype, const void* x, const void* dy, float* 
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, EDGE_LDS);
         if (attr != hipSuccess) return VQK_ERR_LAUNCH;
         hipLaunchKernelGGL(conv3x3_wgrad_thin_kernel<1>, dim3((unsigned)blocks), dim3(256), EDGE_LDS, st, (const bf16_raw*)x,
-                           (const bf16_raw*)dy, (float*)ws, (const char*)zeros, n, h, w);
+                           (const bf16_raw*)dy, (float*)ws, (const char*)zeros, n, h, w, db, thin_true);
     }
     VQK_CHECK_LAUNCH();
     static_assert(EDGE_OUT % 16 == 0, "reduce blocks own 16 outputs");

@@ -177,12 +177,20 @@ __device__ __forceinline__ void ws_release(double* __restrict__ ws, int n_sample
 
 // gn_finalize + gn_apply in one pass: every thread derives (mean, rstd) of its channels' groups from the double
 // sums; the first pixel block of each sample also stores them as fp32 stats for the backward.
-template <typename T, bool SILU>
+//
+// POOL: the pass also stores the 2x2 average of its INPUT, pooled[n, oy, ox, :] = ((x00 + x01) + (x10 + x11)) * pool_scale -- the
+// skip of a pooling ResBlock, bit for bit what pool2x2_kernel (pointwise.hip) makes of x, for one quarter-size store instead of a
+// pass of its own.  pix_per_block is then a multiple of 2 * width (a block owns whole row pairs, so its pooled pixels are the
+// contiguous range [p0 / 4, p1 / 4) of the sample's half-resolution map) and a thread walks pooled pixels: four loads, four y
+// stores, one pooled store each, two quads (8 vectors >= GN_DEPTH + 1) in flight.
+template <typename T, bool SILU, bool POOL = false>
 __global__ __launch_bounds__(256) void gn_apply_fin_kernel(const T* __restrict__ x, double* __restrict__ ws,
                                                            float* __restrict__ stats, const float* __restrict__ w,
                                                            const float* __restrict__ b, T* __restrict__ y, int64_t hw,
                                                            int c, int groups, int silu, int pix_per_block, float eps,
-                                                           const double* __restrict__ part = nullptr, int nblk = 0) {
+                                                           const double* __restrict__ part = nullptr, int nblk = 0,
+                                                           T* __restrict__ pooled = nullptr, int width = 0,
+                                                           float pool_scale = 0.f) {
     constexpr int V = Vec16<T>::N;
     const int vpp = c / V, slot = threadIdx.x % vpp, prow = threadIdx.x / vpp, pstep = 256 / vpp;
     const int n = blockIdx.y, cpg = c / groups;
@@ -220,7 +228,59 @@ __global__ __launch_bounds__(256) void gn_apply_fin_kernel(const T* __restrict__
     const int64_t p0 = (int64_t)blockIdx.x * pix_per_block;
     const int64_t p1 = min(hw, p0 + pix_per_block);
     const int64_t off = (int64_t)n * hw * c + slot * V;
-    {
+    if constexpr (POOL) {
+        typedef typename Raw16<T>::type raw_t;
+        constexpr int D = 2;                                 // quads in flight
+        const int ow = width >> 1;
+        const int q0 = (int)(p0 >> 2), q1 = (int)(p1 >> 2), qlast = q1 - 1;
+        const int64_t row = (int64_t)width * c;
+        T* __restrict__ po = pooled + (int64_t)n * (hw >> 2) * c + slot * V;
+        raw_t buf[D][4];
+        int64_t tap[D];                                      // element offset of the quad's top-left tap
+        // issue the four loads of pooled pixel q (clamped to the block's last one: unconditional, counted waits)
+        auto fetch = [&](int u, int q) {
+            q = min(q, qlast);
+            const int oy = q / ow, ox = q - oy * ow;
+            tap[u] = off + ((int64_t)oy * 2 * width + 2 * ox) * c;
+            const T* s = x + tap[u];
+            buf[u][0] = gn_ld<T, false>(s); buf[u][1] = gn_ld<T, false>(s + c);
+            buf[u][2] = gn_ld<T, false>(s + row); buf[u][3] = gn_ld<T, false>(s + row + c);
+        };
+        int q = q0 + prow;
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+            fetch(u, q + u * pstep);
+            // quads stay in issue order: the loop's first wait is counted from here too, and a quad the scheduler moved behind
+            // the other one would turn it into a full drain on every trip
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        for (; q < q1; q += D * pstep) {
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                const int qq = q + u * pstep;
+                float v[4][V];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) Raw16<T>::unpack(buf[u][k], v[k]);
+                T* d = y + tap[u];
+                fetch(u, qq + D * pstep);
+                float o[V];
+#pragma unroll
+                for (int i = 0; i < V; ++i) o[i] = ((v[0][i] + v[1][i]) + (v[2][i] + v[3][i])) * pool_scale;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        float t = __fmaf_rn(v[k][i], scale[i], shift[i]);
+                        v[k][i] = SILU ? silu_f(t) : t;
+                    }
+                if (qq < q1) {
+                    GN_STORE_FWD(d, v[0]); GN_STORE_FWD(d + c, v[1]);
+                    GN_STORE_FWD(d + row, v[2]); GN_STORE_FWD(d + row + c, v[3]);
+                    Vec16<T>::store(po + (int64_t)qq * c, o);
+                }
+            }
+        }
+    } else {
         typedef typename Raw16<T>::type raw_t;
         constexpr int D = GN_DEPTH + 1;
         const int64_t last = p1 - 1, step = pstep;
@@ -1139,6 +1199,58 @@ int vqk_gn_forward_presummed(int dtype, const void* x, const float* w, const flo
         { if (silu) hipLaunchKernelGGL((gn_apply_fin_kernel<bf16_raw, true>), grid, dim3(256), (size_t)groups * 8, st, (const bf16_raw*)x, ws, stats, w, b, (bf16_raw*)y, hw, c, groups, silu, ppb, eps); else hipLaunchKernelGGL((gn_apply_fin_kernel<bf16_raw, false>), grid, dim3(256), (size_t)groups * 8, st, (const bf16_raw*)x, ws, stats, w, b, (bf16_raw*)y, hw, c, groups, silu, ppb, eps); }
     VQK_CHECK_LAUNCH();
     return VQK_OK;
+}
+
+}  // extern "C"
+
+// the apply pass that also pools its input (gn_apply_fin_kernel<T, SILU, true>): blocks own whole row pairs
+static int gn_apply_fin_pool_launch(int dtype, const void* x, double* ws, float* stats, const float* w, const float* b, void* y,
+                                    const double* part, int n, int h, int wd, int c, int groups, float eps, int silu, void* pooled,
+                                    float pool_scale, hipStream_t st) {
+    const int64_t hw = (int64_t)h * wd;
+    const int pair = 2 * wd;
+    const int ppb = (pick_ppb(n, hw) + pair - 1) / pair * pair;
+    const dim3 grid((unsigned)((hw + ppb - 1) / ppb), (unsigned)n);
+    const int nblk = part ? 1 : 0;
+#define VQK_GN_FIN_POOL(T, S) hipLaunchKernelGGL((gn_apply_fin_kernel<T, S, true>), grid, dim3(256), (size_t)groups * 8, st, (const T*)x, ws, \
+        stats, w, b, (T*)y, hw, c, groups, silu, ppb, eps, part, nblk, (T*)pooled, wd, pool_scale)
+    if (dtype == VQK_F32) { if (silu) VQK_GN_FIN_POOL(float, true); else VQK_GN_FIN_POOL(float, false); }
+    else { if (silu) VQK_GN_FIN_POOL(bf16_raw, true); else VQK_GN_FIN_POOL(bf16_raw, false); }
+#undef VQK_GN_FIN_POOL
+    VQK_CHECK_LAUNCH();
+    return VQK_OK;
+}
+
+static int check_gn_pooled(int dtype, const void* x, const void* y, const void* pooled, int n, int h, int wd, int c, int groups) {
+    VQK_REQUIRE(n > 0 && h > 0 && wd > 0, VQK_ERR_SHAPE);
+    VQK_REQUIRE(!(h & 1) && !(wd & 1) && (int64_t)h * wd <= (int64_t)1 << 30 && wd <= 1 << 20, VQK_ERR_SHAPE);
+    const int rc = check_gn(dtype, c, groups);
+    if (rc) return rc;
+    VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(y) && vqk_aligned16(pooled), VQK_ERR_ALIGN);
+    return VQK_OK;
+}
+
+extern "C" {
+
+int vqk_gn_forward_presummed_pooled(int dtype, const void* x, const float* w, const float* b, void* y, float* stats, double* ws,
+                                    int n, int h, int wd, int c, int groups, float eps, int silu, void* pooled, float pool_scale,
+                                    void* stream) {
+    VQK_REQUIRE(x && w && b && y && stats && ws && pooled, VQK_ERR_ARG);
+    const int rc = check_gn_pooled(dtype, x, y, pooled, n, h, wd, c, groups);
+    if (rc) return rc;
+    return gn_apply_fin_pool_launch(dtype, x, ws, stats, w, b, y, nullptr, n, h, wd, c, groups, eps, silu, pooled, pool_scale,
+                                    vqk_stream(stream));
+}
+
+int vqk_gn_forward_presummed_parts_pooled(int dtype, const void* x, const float* w, const float* b, void* y, float* stats,
+                                          const double* parts, int nblk, double* sums, int n, int h, int wd, int c, int groups,
+                                          float eps, int silu, void* pooled, float pool_scale, void* stream) {
+    VQK_REQUIRE(x && w && b && y && stats && parts && sums && nblk > 0 && pooled, VQK_ERR_ARG);
+    const int rc = check_gn_pooled(dtype, x, y, pooled, n, h, wd, c, groups);
+    if (rc) return rc;
+    hipStream_t st = vqk_stream(stream);
+    hipLaunchKernelGGL(gn_parts_reduce_kernel, dim3((unsigned)(n * groups)), dim3(64), 0, st, parts, nblk, sums);
+    return gn_apply_fin_pool_launch(dtype, x, sums, stats, w, b, y, sums, n, h, wd, c, groups, eps, silu, pooled, pool_scale, st);
 }
 
 }  // extern "C"

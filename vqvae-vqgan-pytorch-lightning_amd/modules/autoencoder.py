@@ -75,8 +75,8 @@ class GroupNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(1, num_channels, 1, 1))
         self.bias = nn.Parameter(torch.zeros(1, num_channels, 1, 1))
 
-    def forward(self, x: torch.Tensor, silu: bool = False) -> torch.Tensor:
-        return ops.group_norm_silu(x, self.weight, self.bias, self.num_groups, self.eps, silu)
+    def forward(self, x: torch.Tensor, silu: bool = False, sole_consumer: bool = False) -> torch.Tensor:
+        return ops.group_norm_silu(x, self.weight, self.bias, self.num_groups, self.eps, silu, sole_consumer)
 
 
 class ResBlock(nn.Module):
@@ -376,7 +376,7 @@ class Decoder(nn.Module):
         for i, blk in enumerate(mods):
             to_conv = i + 1 < len(mods) and isinstance(mods[i + 1], Upsample)
             x = blk(x, next_gn=0 if to_conv else gn)
-        x = self.norm(x, silu=True)
+        x = self.norm(x, silu=True, sole_consumer=True)       # (the last Upsample conv's bias gradient rides in this norm's backward)
         return self.conv_out(x, act=1)                        # tanh in the epilogue
 
     def forward(self, x):

@@ -902,10 +902,19 @@ def raw_split_pair(t) -> torch.Tensor:
     return out
 
 
-def raw_conv_wgrad(x, dy, ksize: int, ups: bool, out=None, thin_true: int = 8, x3: bool = False) -> torch.Tensor:
+def edge_wgrad_takes_bias(x, dy, ksize: int, ups: bool) -> bool:
+    """the edge weight-gradient launch of this problem can also sum the conv's bias gradient (the LAST conv: thin dy, staged whole)"""
+    return (FUSE_BIAS_COLSUM and EDGE_BIAS_COLSUM and not DETERMINISTIC and edge_wgrad_served(x, dy, ksize, ups)
+            and (x.shape[1], dy.shape[1]) == (128, 8))
+
+
+def raw_conv_wgrad(x, dy, ksize: int, ups: bool, out=None, thin_true: int = 8, x3: bool = False, db=None) -> torch.Tensor:
     """dw as fp32 with memory [Cout][k][k][Cin] (logical [Cout,Cin,k,k] channels_last); ``out``: accumulate
     into this (pre-existing) buffer instead of a fresh zeroed one.  ``thin_true`` < 8 (edge convs only, with ``out``): ``out`` is
-    the parameter's own UNPADDED gradient (3 true channels on the thin side: vqk_conv2d_wgrad_edge_true)."""
+    the parameter's own UNPADDED gradient (3 true channels on the thin side: vqk_conv2d_wgrad_edge_true).  ``db`` (only where
+    :func:`edge_wgrad_takes_bias`): fp32 [thin_true] that also receives the column sums of dy (vqk_conv2d_wgrad_edge_bias)."""
+    if db is not None and not edge_wgrad_takes_bias(x, dy, ksize, ups):
+        raise RuntimeError('vqk: this weight-gradient launch cannot carry the bias sum')
     n, cin, h, w = x.shape
     cout = dy.shape[1]
     dw = out if out is not None else \
@@ -915,8 +924,8 @@ def raw_conv_wgrad(x, dy, ksize: int, ups: bool, out=None, thin_true: int = 8, x
         # the two edge convs (padded 3-channel image / reconstruction): K = 72 GEMM, HBM-bound, workspace split-K
         ws = _edge_ws(x.device)
         nbytes = (x.numel() + dy.numel()) * 2
-        st = _timed('conv3x3_wgrad_thin_kernel<bf16>' + (f' {cin}->{cout}@{h}x{w}' if _EVENT_SHAPES else ''), 0.0,
-                    lambda: _native.lib().vqk_conv2d_wgrad_edge_true(dcode(x.dtype), x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
+        st = _timed('conv3x3_wgrad_thin_kernel<bf16>' + (f' {cin}->{cout}@{h}x{w}{" +bias-grad" if db is not None else ""}' if _EVENT_SHAPES else ''), 0.0,
+                    lambda: _native.lib().vqk_conv2d_wgrad_edge_bias(dcode(x.dtype), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _p(db),
                                                                      ws.data_ptr(), ws.numel() * 4, n, h, w, cin, cout, int(thin_true),
                                                                      zero_page(x.device).data_ptr(), _stream()), nbytes)
         _native.check(st, 'conv2d_wgrad_edge')
@@ -1193,9 +1202,18 @@ def raw_gn_apply(x, stats, w, b, groups: int, silu: bool) -> torch.Tensor:
     return y
 
 
-def raw_gn_forward(x, w, b, groups: int, eps: float, silu: bool, presummed: bool = False, conv_hw: int = 0):
+# The skip of a pooling ResBlock (x itself, no 1x1 shortcut) is pooled by the GroupNorm apply pass that streams x for norm1 anyway
+# (vqk_gn_forward_presummed_pooled: one quarter-size store more) instead of a pool2x2 pass of its own: 3 launches and 1.09 GB of
+# traffic per headline step.  Bit-identical to raw_pool; VQK_GN_POOLED_SKIP=0 keeps the two launches (A/B).
+GN_POOLED_SKIP = _native.switch('VQK_GN_POOLED_SKIP', '1') != '0'
+
+
+def raw_gn_forward(x, w, b, groups: int, eps: float, silu: bool, presummed: bool = False, conv_hw: int = 0,
+                   pooled_scale: float | None = None):
     """(y, stats): sums kernel + finalize-and-apply kernel on the persistent workspace; ``presummed``: the sums of x were
-    left in the workspace by the conv that produced x (``raw_conv_fprop_gnstats``), only the apply pass runs"""
+    left in the workspace by the conv that produced x (``raw_conv_fprop_gnstats``), only the apply pass runs.
+    ``pooled_scale``: (y, stats, pooled) with pooled = raw_pool(x, pooled_scale), written by the apply pass itself where that
+    form applies (presummed x, even sides) and by raw_pool otherwise."""
     n, c, h, wd = x.shape
     y = torch.empty_like(x, memory_format=_CL)
     stats = torch.empty(n * groups * 2, dtype=torch.float32, device=x.device)
@@ -1205,23 +1223,44 @@ def raw_gn_forward(x, w, b, groups: int, eps: float, silu: bool, presummed: bool
     if claimed:
         conv_hw = _HANDOFF.claimed_hw                              # (a pooled producer: 4x the pixels of x)
     presummed = presummed or claimed
+    want_pool = pooled_scale is not None
+    fuse_pool = want_pool and presummed and GN_POOLED_SKIP and h % 2 == 0 and wd % 2 == 0
+    pooled = empty_nhwc(n, c, h // 2, wd // 2, x.dtype, x.device) if fuse_pool else None
+    tag = ' +pooled-skip' if fuse_pool else ''
+    nbytes = 2 * nb + (nb // 4 if fuse_pool else 0)
+
+    def done():
+        if not want_pool:
+            return y, stats
+        return y, stats, (pooled if fuse_pool else raw_pool(x, pooled_scale))
+
     if presummed and DETERMINISTIC:
         nblk = (conv_hw or h * wd) // 256
         buf = _gn_parts(x.device, n * groups * 2 * (nblk + 1))
-        st = _timed('group_norm_fwd (HBM)' + (f' {c}@{h}x{wd} presummed' if _EVENT_SHAPES else ''), 0.0,
-                    lambda: _native.lib().vqk_gn_forward_presummed_parts(dcode(x.dtype), x.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                                                         y.data_ptr(), stats.data_ptr(), buf[n * groups * 2:].data_ptr(),
-                                                                         nblk, buf.data_ptr(), n, h * wd, c, groups, eps, int(silu),
-                                                                         _stream()), 2 * nb)
+        if fuse_pool:
+            call = lambda: _native.lib().vqk_gn_forward_presummed_parts_pooled(
+                dcode(x.dtype), x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(),
+                buf[n * groups * 2:].data_ptr(), nblk, buf.data_ptr(), n, h, wd, c, groups, eps, int(silu), pooled.data_ptr(),
+                float(pooled_scale), _stream())
+        else:
+            call = lambda: _native.lib().vqk_gn_forward_presummed_parts(
+                dcode(x.dtype), x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(),
+                buf[n * groups * 2:].data_ptr(), nblk, buf.data_ptr(), n, h * wd, c, groups, eps, int(silu), _stream())
+        st = _timed('group_norm_fwd (HBM)' + (f' {c}@{h}x{wd} presummed{tag}' if _EVENT_SHAPES else ''), 0.0, call, nbytes)
         _native.check(st, 'gn_forward_presummed_parts')
-        return y, stats
+        return done()
     if presummed:
-        st = _timed('group_norm_fwd (HBM)' + (f' {c}@{h}x{wd} presummed' if _EVENT_SHAPES else ''), 0.0,
-                    lambda: _native.lib().vqk_gn_forward_presummed(dcode(x.dtype), x.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                                                   y.data_ptr(), stats.data_ptr(), ws.data_ptr(), n, h * wd, c,
-                                                                   groups, eps, int(silu), _stream()), 2 * nb)
+        if fuse_pool:
+            call = lambda: _native.lib().vqk_gn_forward_presummed_pooled(
+                dcode(x.dtype), x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(), ws.data_ptr(), n, h, wd,
+                c, groups, eps, int(silu), pooled.data_ptr(), float(pooled_scale), _stream())
+        else:
+            call = lambda: _native.lib().vqk_gn_forward_presummed(
+                dcode(x.dtype), x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(), ws.data_ptr(), n, h * wd,
+                c, groups, eps, int(silu), _stream())
+        st = _timed('group_norm_fwd (HBM)' + (f' {c}@{h}x{wd} presummed{tag}' if _EVENT_SHAPES else ''), 0.0, call, nbytes)
         _native.check(st, 'gn_forward_presummed')
-        return y, stats
+        return done()
     # algorithmic bytes: x read for the statistics, x read + y written by the apply pass (one read, one write on the
     # single-kernel path of the small maps)
     st = _timed('group_norm_fwd (HBM)' + (f' {c}@{h}x{wd}' if _EVENT_SHAPES else ''), 0.0,
@@ -1229,7 +1268,7 @@ def raw_gn_forward(x, w, b, groups: int, eps: float, silu: bool, presummed: bool
                                                      stats.data_ptr(), ws.data_ptr(), n, h * wd, c, groups, eps, int(silu),
                                                      _stream()), (2 if h * wd <= 1024 else 3) * nb)
     _native.check(st, 'gn_forward')
-    return y, stats
+    return done()
 
 
 def raw_gn_backward(x, stats, w, b, dy, groups: int, silu: bool, dw=None, db=None, add=None, dx_colsum=None, out=None,
@@ -1270,7 +1309,12 @@ def raw_gn_backward(x, stats, w, b, dy, groups: int, silu: bool, dw=None, db=Non
 # writes d(block input) = the conv's dy): Conv2dFn.forward notes (output tensor, bias parameter), ResBlockFn.forward claims the
 # note when that very tensor is its input, its backward hands the bias's arena gradient to the kernel and marks the bias as
 # done; Conv2dFn.backward then skips its column-sum pass over dy (185 us for the 537-MB gradient of the last Upsample conv).
+# The same holds for a conv read by nothing but a GroupNormSiLUFn (``sole_consumer``: the decoder's final norm behind the last
+# Upsample conv, 101 us), and the decoder head's own bias rides in its edge weight-gradient launch, which stages dy whole
+# (``edge_wgrad_takes_bias``, 25 us).  Left alone: the maps of <= 1024 pixels (their single-kernel backwards carry no sums; 22 / 10 us)
+# and the encoder's 1x1 conv_out (9 us) -- profiles/gn_pooled_skip_ab.txt.
 FUSE_BIAS_COLSUM = _native.switch('VQK_FUSE_BIAS_COLSUM', '1') != '0'
+EDGE_BIAS_COLSUM = _native.switch('VQK_EDGE_BIAS_COLSUM', '1') != '0'     # the decoder head's bias sum rides in its weight-gradient launch
 _DB_DONE: set = set()         # ids of bias parameters whose gradient a GroupNorm backward already summed (autograd thread; keyed
                               # by the parameter: two models never share an entry)
 
@@ -1728,24 +1772,31 @@ class Conv2dFn(torch.autograd.Function):
                 if ups:
                     dx = raw_pool(dx, 1.0)
         padded = cin != i or cout_pad != o
+        db_rode = False
         if ctx.needs_input_grad[1]:
             tgt = None if padded else direct_grad(ctx.weight_ref)
             thin = 8
+            tb = None
             if padded and edge_wgrad_served(x, dyc, k, ups) and (cin == i or cout_pad == o):
                 # the 3-channel edge convs (image in, reconstruction out): the kernel drops the zero-padded channels itself and adds
                 # the TRUE gradient to the arena -- no zero-filled padded temporary, no slice, no AccumulateGrad pass
                 tgt = direct_grad(ctx.weight_ref)
                 thin = (i if cin != i else o) if tgt is not None else 8
+                if thin == o and has_bias and ctx.needs_input_grad[2] and edge_wgrad_takes_bias(x, dyc, k, ups):
+                    tb = direct_grad(ctx.bias_ref)               # the decoder head: dy's column sums ride in this launch (no colsum pass)
             if thin == 8 and wgrad_group_deferrable(x, dyc, tgt, ctx.x3, k, ups):
                 defer_wgrad(x, dyc, tgt)                         # a small map: the stage's grouped launch adds it to the arena
             else:
-                dw = raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3)
+                dw = raw_conv_wgrad(x, dyc, k, ups, out=tgt, thin_true=thin, x3=ctx.x3, db=tb)
+                db_rode = tb is not None
             if tgt is not None:
                 dw = None                                        # already accumulated in the flat arena
             elif padded:
                 dw = dw[:o, :i]
         if has_bias and ctx.needs_input_grad[2] and id(ctx.bias_ref) in _DB_DONE:
             _DB_DONE.discard(id(ctx.bias_ref))                   # the consumer's GroupNorm backward summed dy's columns already
+        elif db_rode:
+            pass                                                 # ... or this node's own weight-gradient launch did
         elif has_bias and ctx.needs_input_grad[2]:
             n, c, h, w = dyc.shape
             tgt = direct_grad(ctx.bias_ref) if (cout_pad == c) else None     # (padded output channels: only the true ones are written)
@@ -1762,8 +1813,12 @@ class GroupNormSiLUFn(torch.autograd.Function):
     """y = [silu](GroupNorm(x)) with the reference's unbiased variance (autoencoder.py:25-39)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, groups: int, eps: float, silu: bool):
+    def forward(ctx, x, weight, bias, groups: int, eps: float, silu: bool, sole_consumer: bool = False):
         _require_gpu(x)
+        # sole_consumer: nothing but this norm reads x, so d(x) is this node's dx -- when x is the output of a conv with a bias, the
+        # backward's apply pass sums that bias's gradient as it writes dx (the decoder's last Upsample conv: a 101-us column-sum
+        # pass over the 537-MB gradient at 128 ch @256^2), as a ResBlock's does for the conv in front of it
+        ctx.db_param = _claim_bias_colsum(x) if sole_consumer else None
         x = nhwc(x)
         w = weight.detach().reshape(-1).contiguous()
         b = bias.detach().reshape(-1).contiguous()
@@ -1780,11 +1835,16 @@ class GroupNormSiLUFn(torch.autograd.Function):
         groups, silu, wshape, bshape = ctx.cfg
         tw, tb = direct_grad(ctx.params[0]), direct_grad(ctx.params[1])
         direct = tw is not None and tb is not None
+        cs = None
+        if ctx.db_param is not None and gn_colsum_ok(x.shape[2], x.shape[3]) and not torch.is_grad_enabled():
+            cs = direct_grad(ctx.db_param)
+            if cs is not None:
+                _DB_DONE.add(id(ctx.db_param))
         dx, dw, db = raw_gn_backward(x, stats, w, b, nhwc(dy), groups, silu, tw if direct else None,
-                                     tb if direct else None, cluster_ok=ctx.cluster_ok)
+                                     tb if direct else None, dx_colsum=cs, cluster_ok=ctx.cluster_ok)
         if direct:
-            return dx, None, None, None, None, None
-        return dx, dw.view(wshape), db.view(bshape), None, None, None
+            return dx, None, None, None, None, None, None
+        return dx, dw.view(wshape), db.view(bshape), None, None, None, None
 
 
 POOLED_BWD = _native.switch('VQK_POOLED_BWD', '1') != '0'      # ResBlock + fused avg-pool: the backward keeps the gradient pooled
@@ -1951,7 +2011,16 @@ class ResBlockFn(torch.autograd.Function):
             raise RuntimeError('vqk: ResBlock channels must be whole 16-byte chunks')
         w1 = n1w.detach().reshape(-1).contiguous(); b1 = n1b.detach().reshape(-1).contiguous()
         w2 = n2w.detach().reshape(-1).contiguous(); b2 = n2b.detach().reshape(-1).contiguous()
-        a1, st1 = raw_gn_forward(x, w1, b1, groups, eps, True)
+        l2 = weight_layout(dt, n, h, w, cout, cout, 3, False)
+        pooled_phase = (pool and POOLED_FPROP_PHASE and cout % 128 == 0 and h * w >= POOLED_FPROP_MIN_HW
+                        and ((dt == torch.bfloat16 and l2 == 1) or (l2 == 5 and phase_layout(dt, X3) and h % 16 == 0 and w % 32 == 0)))
+        skip_pooled = None
+        if pooled_phase and scw is None:
+            # the pooled-forward phase form adds its residual at OUTPUT resolution: norm1's apply pass, which streams x anyway, also
+            # stores the pooled skip (raw_gn_forward: pooled_scale)
+            a1, st1, skip_pooled = raw_gn_forward(x, w1, b1, groups, eps, True, pooled_scale=0.25)
+        else:
+            a1, st1 = raw_gn_forward(x, w1, b1, groups, eps, True)
         l1 = weight_layout(dt, n, h, w, cin, cout, 3, False)
         wq1 = packed_weight(c1w, cin, cout, dt, 3, False, l1)
         # the first conv's drain also sums its output for the second GroupNorm (no statistics pass over r1)
@@ -1965,14 +2034,14 @@ class ResBlockFn(torch.autograd.Function):
             lsc = weight_layout(dt, n, h, w, cin, cout, 1, False)
             skip = raw_conv_fprop(x, packed_weight(scw, cin, cout, dt, 1, False, lsc), None, None, 1,
                                   False, 0, dt, cout, lsc)
-        l2 = weight_layout(dt, n, h, w, cout, cout, 3, False)
         wq2 = packed_weight(c2w, cout, cout, dt, 3, False, l2)
         out = None
-        if (pool and POOLED_FPROP_PHASE and cout % 128 == 0 and h * w >= POOLED_FPROP_MIN_HW
-                and ((dt == torch.bfloat16 and l2 == 1) or (l2 == 5 and phase_layout(dt, X3) and h % 16 == 0 and w % 32 == 0))):
-            # conv2 + the level's average pool as the 4x4 stride-2 conv it is (4/9 of the multiply-adds); the skip is pooled by its
-            # own memory-bound pass (the launch adds a residual at its OUTPUT resolution)
-            out = raw_conv_pooled_fprop_phase(a2, c2w, raw_pool(skip, 0.25), 0.25, next_gn, x3=X3)
+        if pooled_phase:
+            # conv2 + the level's average pool as the 4x4 stride-2 conv it is (4/9 of the multiply-adds); the launch adds a residual at
+            # its OUTPUT resolution: the skip pooled by norm1's apply pass, or (behind a 1x1 shortcut) by a memory-bound pass of its own
+            if skip_pooled is None:
+                skip_pooled = raw_pool(skip, 0.25)
+            out = raw_conv_pooled_fprop_phase(a2, c2w, skip_pooled, 0.25, next_gn, x3=X3)
         if out is not None:
             pass
         elif next_gn and l2 in (1, 5) and cout % 128 == 0:       # the sums for the GroupNorm that reads `out` next
@@ -2127,8 +2196,9 @@ def res_block(x, n1w, n1b, c1w, n2w, n2b, c2w, scw=None, groups: int = 32, eps: 
     return ResBlockFn.apply(x, n1w, n1b, c1w, n2w, n2b, c2w, scw, groups, eps, pool, next_gn)
 
 
-def group_norm_silu(x, weight, bias, groups: int = 32, eps: float = 1e-6, silu: bool = True):
-    return GroupNormSiLUFn.apply(x, weight, bias, groups, eps, silu)
+def group_norm_silu(x, weight, bias, groups: int = 32, eps: float = 1e-6, silu: bool = True, sole_consumer: bool = False):
+    """``sole_consumer``: x is read by nothing else (GroupNormSiLUFn: the bias gradient of the conv that produced x rides in the backward)"""
+    return GroupNormSiLUFn.apply(x, weight, bias, groups, eps, silu, sole_consumer)
 
 
 class AvgPool2x2Fn(torch.autograd.Function):
