@@ -667,7 +667,7 @@ const char* vqk_conv_fprop_form_name(int form, int dtype);
 /* Deterministic mode (the reference trains with `deterministic=True`, vqvae/train.py:130).  on = 1: the float accumulations of
  * the train step that are otherwise combined with atomics in arrival order -- split-K partials of the weight gradients, column
  * sums (bias gradients), the cross-block sums of the GroupNorm statistics / backward reductions and of d gamma / d beta, the
- * per-code sums of the codebook gradient -- go through `ws` (>= 64 MiB recommended; VQK_ERR_WORKSPACE when a call needs more)
+ * per-code sums of the codebook gradient -- go through `ws` (>= 64 MiB recommended; VQK_ERR_WORKSPACE when a call needs more -- vqk_colsum_lead alone answers VQK_ERR_ARG, see there)
  * as per-block partials that are added in index order, or run unsplit.  THREAD-LOCAL like the block caps; the workspace must
  * belong to the stream the following launches go to (two streams = two workspaces, re-armed on every switch).  The scalar
  * loss sums keep their atomics (values, not gradients); the EMA statistics, which the codebook is trained from, are added in row order
@@ -790,7 +790,9 @@ int vqk_conv2d_thin_out(int dtype, const void* x, const void* w, const float* bi
 int vqk_colsum(int dtype, const void* x, int64_t rows, int c, float* out, void* stream);
 /* out[i] += scale * sum_rows x[row][i] for the first c_out <= c columns only: `out` is the gradient of a bias whose layer carries
  * zero-padded output channels (the decoder's 3-channel head on 8) -- the sums go straight into the parameter's own (unpadded)
- * gradient; `scale` undoes a gain folded into x (the StyleGAN2 layers' runtime weight gain). */
+ * gradient; `scale` undoes a gain folded into x (the StyleGAN2 layers' runtime weight gain).  c <= 8192 (VQK_ERR_SHAPE above).
+ * Deterministic mode: the block count is halved until the partial rows ([blocks][c] fp32) fit the armed workspace; a workspace
+ * that cannot hold ONE partial row (c * 4 bytes) is a bad argument of vqk_set_deterministic: VQK_ERR_ARG, nothing launched. */
 int vqk_colsum_lead(int dtype, const void* x, int64_t rows, int c, int c_out, float scale, float* out, void* stream);
 /* elementwise fp32 -> dtype cast (weight shadow copies) */
 int vqk_cast(const float* src, void* dst, int dtype, int64_t n, void* stream);
@@ -882,7 +884,11 @@ int vqk_preprocess(const float* images, void* x_pad, int dtype, float* target, i
  * tensors: no host sync); the kornia generator itself is not in the reference tree, so its exact stream is unpinned. */
 int vqk_augment_preprocess(const float* images, const float* box, const int32_t* flip, void* x_pad, int dtype, float* target,
                            int n, int h, int w, int cpad, void* stream);
-/* loss[0] += sum (recon - target)^2 over n elements (recon dtype given; target fp32). */
+/* loss[0] += sum (recon - target)^2 over n elements (recon dtype given; target fp32).  Up to 32 blocks (65536 elements) add their
+ * partials to loss[0] by fp32 atomics.  Larger sums, given a stream scratch of >= 8 KiB (vqk_set_scratch), store the block partials
+ * there and a second one-block launch adds them in block order in double and rounds once: the same bits every run, ~1e-7 relative
+ * (2048 atomics in arrival order are a random walk of up to 2.4e-6 relative at 4M elements).  Without a scratch: the atomics.
+ * vqk_pair_stats sums its out5[0] the same way. */
 int vqk_sse(int dtype, const void* recon, const float* target, int64_t n, float* loss, void* stream);
 /* d = s * gscale * 2 (recon - target) * (through_tanh ? 1 - recon^2 : 1), s = *gscale_dev (NULL = 1)
  * (MSE backward, optionally through the decoder's tanh head; model.py:272, autoencoder.py:179) */

@@ -105,9 +105,32 @@ __global__ __launch_bounds__(256) void augment_preprocess_kernel(const float* __
     }
 }
 
+// Scalar sums (sse, pair_stats) of more than SUM_ATOMIC_BLOCKS blocks: 2048 fp32 atomics on ONE float round the running total 2048
+// times in arrival order -- a random walk of ~13 ulp, up to 2.4e-6 relative at one 8 x 8 x 256 x 256 batch and different every run.
+// With the stream's scratch (vqk_set_scratch) a block stores its partial instead (`part` != NULL) and this one block adds the
+// partials in a fixed order in double and rounds ONCE: the same bits every run, ~1e-7 relative.
+constexpr int SUM_ATOMIC_BLOCKS = 32;
+__global__ __launch_bounds__(256) void scalar_sum_reduce_kernel(const float* __restrict__ part, int blocks, float* __restrict__ out) {
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += 256) s += (double)part[b];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd(out, (float)sh[0]);
+}
+// the partial slots of a scalar sum of `grid` blocks in the calling thread's scratch, or NULL: few blocks, or no scratch armed
+static float* scalar_sum_slots(int grid) {
+    const vqkd::DetState& sc = vqkd::scratch_state();
+    return (grid > SUM_ATOMIC_BLOCKS && sc.ws && sc.bytes >= (int64_t)grid * 4) ? sc.ws : nullptr;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void sse_kernel(const T* __restrict__ r, const float* __restrict__ t, int64_t n,
-                                                  float* __restrict__ loss) {
+                                                  float* __restrict__ loss, float* __restrict__ slots) {
     __shared__ float part[4];
     float acc = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -117,7 +140,11 @@ __global__ __launch_bounds__(256) void sse_kernel(const T* __restrict__ r, const
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, (part[0] + part[1]) + (part[2] + part[3]));
+    if (threadIdx.x == 0) {
+        const float s = (part[0] + part[1]) + (part[2] + part[3]);
+        if (slots) slots[blockIdx.x] = s;
+        else atomicAdd(loss, s);
+    }
 }
 
 template <typename T>
@@ -188,7 +215,7 @@ __device__ __forceinline__ void atomic_max_f(float* addr, float v) {
 }
 
 __global__ __launch_bounds__(256) void pair_stats_kernel(const float* __restrict__ p, const float* __restrict__ t, int64_t n,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, float* __restrict__ slots) {
     __shared__ float part[5][4];
     float sse = 0.f, tmin = INFINITY, tmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -206,7 +233,9 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const float* __restrict
     if ((threadIdx.x & 63) == 0) { part[0][wv] = sse; part[1][wv] = tmin; part[2][wv] = tmax; part[3][wv] = pmin; part[4][wv] = pmax; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(out, (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
+        const float s = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+        if (slots) slots[blockIdx.x] = s;
+        else atomicAdd(out, s);
         atomic_min_f(out + 1, fminf(fminf(part[1][0], part[1][1]), fminf(part[1][2], part[1][3])));
         atomic_max_f(out + 2, fmaxf(fmaxf(part[2][0], part[2][1]), fmaxf(part[2][2], part[2][3])));
         atomic_min_f(out + 3, fminf(fminf(part[3][0], part[3][1]), fminf(part[3][2], part[3][3])));
@@ -323,9 +352,11 @@ int vqk_sse(int dtype, const void* recon, const float* target, int64_t n, float*
     VQK_REQUIRE(recon && target && loss, VQK_ERR_ARG);
     if (n <= 0) return VQK_OK;
     const dim3 grid(vqk_grid_1d(n, 256 * 8));
-    if (dtype == VQK_F32) hipLaunchKernelGGL(sse_kernel<float>, grid, dim3(256), 0, vqk_stream(stream), (const float*)recon, target, n, loss);
-    else if (dtype == VQK_BF16) hipLaunchKernelGGL(sse_kernel<bf16_raw>, grid, dim3(256), 0, vqk_stream(stream), (const bf16_raw*)recon, target, n, loss);
+    float* slots = scalar_sum_slots((int)grid.x);
+    if (dtype == VQK_F32) hipLaunchKernelGGL(sse_kernel<float>, grid, dim3(256), 0, vqk_stream(stream), (const float*)recon, target, n, loss, slots);
+    else if (dtype == VQK_BF16) hipLaunchKernelGGL(sse_kernel<bf16_raw>, grid, dim3(256), 0, vqk_stream(stream), (const bf16_raw*)recon, target, n, loss, slots);
     else return VQK_ERR_DTYPE;
+    if (slots) hipLaunchKernelGGL(scalar_sum_reduce_kernel, dim3(1), dim3(256), 0, vqk_stream(stream), (const float*)slots, (int)grid.x, loss);
     VQK_CHECK_LAUNCH();
     return VQK_OK;
 }
@@ -370,7 +401,10 @@ int vqk_axpby(int dtype, const void* x, const void* y2, void* y, float a, float 
 int vqk_pair_stats(const float* pred, const float* target, int64_t n, float* out5, void* stream) {
     VQK_REQUIRE(pred && target && out5, VQK_ERR_ARG);
     if (n <= 0) return VQK_OK;
-    hipLaunchKernelGGL(pair_stats_kernel, dim3(vqk_grid_1d(n, 256 * 8)), dim3(256), 0, vqk_stream(stream), pred, target, n, out5);
+    const int grid = vqk_grid_1d(n, 256 * 8);
+    float* slots = scalar_sum_slots(grid);
+    hipLaunchKernelGGL(pair_stats_kernel, dim3(grid), dim3(256), 0, vqk_stream(stream), pred, target, n, out5, slots);
+    if (slots) hipLaunchKernelGGL(scalar_sum_reduce_kernel, dim3(1), dim3(256), 0, vqk_stream(stream), (const float*)slots, grid, out5);
     VQK_CHECK_LAUNCH();
     return VQK_OK;
 }

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import _native
+from . import _native, ops
 
 
 def gaussian_window(kernel_size: int = 11, sigma: float = 1.5) -> torch.Tensor:
@@ -47,7 +47,7 @@ class ReconstructionMetrics:
         if p.shape != t.shape or p.dim() != 4 or not p.is_cuda:
             raise RuntimeError('vqk: metrics expect two CUDA tensors of the same (B, C, H, W) shape')
         b, c, h, w = p.shape
-        lib, st = _native.lib(), torch.cuda.current_stream().cuda_stream
+        lib, st = _native.lib(), ops._stream()         # (names this stream's workspace context: the ordered sum of pair_stats)
         inf = float('inf')
         batch = torch.tensor([0.0, inf, -inf, inf, -inf], dtype=torch.float32, device=p.device)
         _native.check(lib.vqk_pair_stats(p.data_ptr(), t.data_ptr(), p.numel(), batch.data_ptr(), st), 'pair_stats')
