@@ -553,8 +553,8 @@ int vqk_conv2d_wgrad_pooled_dy(int dtype, const void* x, const void* dy_pooled, 
                                int cout, float scale, const void* zeros, void* stream);
 /* Weight gradient of a nearest-x2 UPSAMPLE + 3x3 conv (vqvae/modules/autoencoder.py:102-105) in PHASE form (csrc/conv_wgmx.hip):
  * x [n, h, w, cin] is the LOW-resolution input, dy [n, 2h, 2w, cout] the gradient of the conv's output;
- * dw[Cout][3][3][Cin] += scale * the gradient, as four launches of a 2x2-window kernel (one per output phase: 4/9 of the
- * multiply-adds of the tap form vqk_conv2d_wgrad(..., ups = 1)).  bf16, h % 8 == 0, w % 16 == 0, cin % 64 == 0, cout % 64 == 0;
+ * dw[Cout][3][3][Cin] += scale * the gradient, from a 2x2-window kernel per output phase (4/9 of the multiply-adds of the tap
+ * form vqk_conv2d_wgrad(..., ups = 1)): the four phases as one launch, or one launch each with tuning slot UPS_MERGE = 0.  bf16, h % 8 == 0, w % 16 == 0, cin % 64 == 0, cout % 64 == 0;
  * VQK_ERR_SHAPE when not served (deterministic mode included: nothing launched, callers use the tap form). */
 int vqk_conv2d_wgrad_ups_phase(int dtype, const void* x, const void* dy, float* dw, int n, int h, int w, int cin, int cout,
                                float scale, const void* zeros, void* stream);
@@ -761,13 +761,33 @@ typedef struct vqk_wgrad_item {
 } vqk_wgrad_item;
 int vqk_conv3x3_wgrad_group(const vqk_wgrad_item* items, int n_items, const void* zeros, void* stream);
 int vqk_conv3x3_wgrad_group_plan(const vqk_wgrad_item* items, int n_items, int* splits, int* launches);
+/* The one-layer weight-gradient launcher's PLAN for a problem, without launching (no device needed): the kernel form the entry
+ * point of `op` would launch under the calling thread's variant, block cap and deterministic state and the current tuning slots
+ * -- a form id >= 0 -- or the negative status that call would return given valid, aligned pointers.  cin / cout: the conv's true
+ * channel counts.  op: 0 vqk_conv2d_wgrad / _general / _general_scaled (all arguments as vqk_conv2d_wgrad_general takes them, ups
+ * = its mode; vqk_conv2d_wgrad: stride 1, pad ksize / 2, h_out = h_in << ups); 1 vqk_conv2d_wgrad_pooled_dy, 2 _ups_phase,
+ * 3 _pooled_dy_phase ((h_in, w_in) = the entry point's (h, w)); 4 vqk_conv2d_wgrad_x3 (with ups); 5 vqk_conv2d_wgrad_x3_f32 (ups
+ * 0 / 1 / 2).  Ops 1-5 ignore ksize, stride, pad, h_out and w_out; ops 4 and 5 ignore dtype.
+ * Form ids: 0 matrix/auxiliary-wave kernel, 1 its pooled-dy form, 2 its upsample phase form, 3 its phase form with the roles
+ * swapped, 4 its pair-operand form; 5 8x16-patch kernel, 6 / 7 halo kernel with 8x16 / 8x8 patches; 8 / 9 fp32 thin kernel with 4
+ * input / 4 output channels; 10 / 11 general kernel fp32 / bf16, 12 double-buffered bf16 1x1; 13 split-product kernel, 14 / 15 its
+ * phase forms for ups 1 / 2.  details (may be NULL): five ints -- dW tiles (the grid's x; forms 8 / 9: blocks), split-K parts
+ * (per phase in the phase forms), patches per part (forms 10-12: pixels, 8 / 9: rows), number of kernel launches (4: one per
+ * phase, tuning slot UPS_MERGE = 0; 2: deterministic mode's partial sums went through the workspace and an ordered reduce
+ * follows), 1 when the form is memory-bound (name suffix " (HBM)").
+ * vqk_conv_wgrad_form_name: the kernel's name for the event statistics, "?" for an unknown id. */
+int vqk_conv_wgrad_plan(int op, int dtype, int n, int h_in, int w_in, int cin, int cout, int ksize, int stride, int pad, int ups,
+                        int h_out, int w_out, int* details);
+const char* vqk_conv_wgrad_form_name(int form, int dtype);
 /* The 3x3 weight gradient of the two EDGE convs (one 16-byte chunk of channels on one side: the padded 3-channel image /
  * reconstruction; vqvae/modules/autoencoder.py:114 and :170), bf16: (cin, cout) = (8, 128) or (128, 8), h*w % 128 == 0 and
  * (w % 128 == 0 or 128 % w == 0).
  * dw[Cout][3][3][Cin] += the gradient; split-K partials go through the caller's workspace `ws` (>=
  * vqk_conv2d_wgrad_edge_ws_bytes() bytes) and are summed in a fixed order: no atomics, run-to-run deterministic.
- * VQK_ERR_SHAPE when not served (nothing launched: callers use vqk_conv2d_wgrad). */
+ * VQK_ERR_SHAPE when not served (nothing launched: callers use vqk_conv2d_wgrad).
+ * vqk_conv2d_wgrad_edge_serves: 1 when the three entry points below take the problem, else 0 (no device needed). */
 int64_t vqk_conv2d_wgrad_edge_ws_bytes(void);
+int vqk_conv2d_wgrad_edge_serves(int dtype, int n, int h, int w, int cin, int cout);
 int vqk_conv2d_wgrad_edge(int dtype, const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes, int n, int h,
                           int w, int cin, int cout, const void* zeros, void* stream);
 /* vqk_conv2d_wgrad_edge with the TRUE channel count of the thin side (thin_true in 1..8; 3 for the image / reconstruction): dw is

@@ -1,7 +1,7 @@
 """Both sides of the conv launchers' shape guards against float64 torch.
 
-The launchers (csrc/conv.hip::launch_fprop, csrc/conv_wgrad.hip::wgrad_general, vqk_conv2d_wgrad_x3_f32) and, for the weight
-gradients, their Python mirrors in ops.py pick a kernel from the map shape: w % 32, w % 16, h % 8, the 64 KiB LDS bound of the edge-conv kernels,
+The launch plans (csrc/conv.hip::plan_fprop, csrc/conv_wgrad.hip::plan_wgrad) and, for the weight gradients, the routing
+between entry points in ops.py pick a kernel from the map shape: w % 32, w % 16, h % 8, the 64 KiB LDS bound of the edge-conv kernels,
 the 32-bit buffer offsets of the matrix/auxiliary-wave kernel.  Every case below sits just inside or just outside one of those
 guards, runs the product's autograd node (``ops.conv2d``: y, dx, dW) and compares with F.conv2d / its autograd in float64 on
 the same inputs (bf16 mode: on the bf16-rounded inputs).  Where the library chooses internally, the case also runs the general
@@ -190,16 +190,14 @@ BF16 = [(2, 128, 128, 8, 32, 'mx', 'mx', 'mx'), (2, 128, 128, 16, 16, 'mx', 'mx'
         (1, 128, 128, 200, 136, 'gen', 'gen', 'halo'), (1, 128, 128, 96, 256, 'mx', 'mx', 'mx'), (1, 128, 128, 256, 96, 'mx', 'mx', 'mx'),
         (1, 128, 128, 512, 512, 'mx', 'mx', 'mx')]
 _FNAME = {'mx': 'conv3x3_mx_kernel<bf16>', 'stream': 'conv3x3_stream_kernel<bf16>', 'gen': 'conv_fprop_kernel<bf16>'}
+_WNAME = {'mx': 'conv3x3_wgrad_mx_kernel<bf16>', 'halo': 'conv3x3_wgrad_halo_kernel<bf16>', 'gen': 'conv_wgrad_kernel<bf16>'}
 
 
 @pytest.mark.parametrize('n,cin,cout,h,w,fk,dk,wk', BF16)
 def test_bf16_conv3x3(n, cin, cout, h, w, fk, dk, wk):
     prod, gen, names = _run('bf16', n, cin, cout, h, w)
     assert names[0] == _FNAME[fk] and names[1] == _FNAME[dk], names  # forward, data gradient (ops' mirror of the launcher)
-    if wk == 'mx':
-        assert 'conv3x3_wgrad_mx_kernel<bf16>' in names, names
-    else:
-        assert 'conv_wgrad_kernel<bf16>' in names, names
+    assert [k for k in names if 'wgrad' in k] == [_WNAME[wk]], names  # weight gradient (the library's launch plan)
     # two fp32 sums rounded to bf16 agree on almost every element: only a large map tells the kernels apart
     if (fk, dk) != ('gen', 'gen') and prod[0].numel() >= 1 << 21:
         assert _differs(prod[0], gen[0]) or _differs(prod[1], gen[1]), 'specialised fprop kernel did not serve'
@@ -213,11 +211,14 @@ def test_bf16_wgrad_p16_kernel():
     _, _, rdw = _ref64(x, wt, None, dy, False)
     xd, dyd = x.to(BF).contiguous(memory_format=CL), dy.to(BF).contiguous(memory_format=CL)
     native.lib().vqk_set_tuning(b'WGMX', 0)
+    ops.KERNEL_EVENTS = []
     try:
         dw = ops.raw_conv_wgrad(xd, dyd, 3, False)
         torch.cuda.synchronize()
     finally:
         native.lib().vqk_set_tuning(b'WGMX', 1)
+        names, ops.KERNEL_EVENTS = [e[0] for e in ops.KERNEL_EVENTS], None
+    assert names == ['conv3x3_wgrad_p16_kernel<bf16>'], names
     _check_dw_bf16(dw, rdw, 'p16')
     _, _, gdw = _general('bf16', x, wt, dy, False)
     assert _differs(dw, gdw)

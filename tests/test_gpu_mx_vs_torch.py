@@ -112,6 +112,7 @@ def test_phase_form_upsample_fwd_and_dgrad_vs_torch():
     torch.cuda.synchronize()
     names = _kernels()
     assert names.count('conv3x3_mx_kernel<bf16>') == 2, names     # forward + data gradient, both in phase form
+    assert [k for k in names if 'wgrad' in k] == ['conv3x3_wgrad_mx_kernel<bf16>'], names      # (the weight gradient too)
     got, ref = y.detach().float().cpu(), want.detach()
     assert float((got - ref).norm() / ref.norm()) < 4e-3
     gx = xd.grad.float().cpu()
@@ -185,6 +186,7 @@ def test_conv1x1_on_mx_kernel_vs_torch(n, cin, cout, h, w):
     torch.cuda.synchronize()
     names = _kernels()
     assert names.count('conv1x1_mx_kernel<bf16> (HBM)') == 2, names  # forward + data gradient
+    assert [k for k in names if 'wgrad' in k] == ['conv_wgrad_db_kernel<bf16>'], names         # weight gradient: double-buffered 1x1
     _check(y.detach(), want.detach(), 1, '1x1 fprop')
     _check(xd.grad, x.grad, 1, '1x1 dgrad')
     gw = wd.grad.float().cpu()

@@ -76,15 +76,21 @@ def test_thin_weight_gradients(n, c, h, w):
     # conv_in: x thin, dy wide -> dW [c][3][3][4]
     for x, dy, co, ci in ((thin, wide, c, 4), (wide, thin, 4, c)):
         pre = torch.randn(co, 3, 3, ci, device=DEV, generator=g).permute(0, 3, 1, 2)
-        dw = ops.raw_conv_wgrad(x, dy, 3, False, out=pre.clone(memory_format=torch.preserve_format))
-        wd = torch.zeros(co, ci, 3, 3, device=DEV, dtype=torch.float64, requires_grad=True)
-        (F.conv2d(x.double(), wd, None, padding=1) * dy.double()).sum().backward()
-        ref = wd.grad + pre.double()
-        native.lib().vqk_conv_set_variant(0)
+        ops.KERNEL_EVENTS = []
         try:
-            dw0 = ops.raw_conv_wgrad(x, dy, 3, False, out=pre.clone(memory_format=torch.preserve_format))
+            dw = ops.raw_conv_wgrad(x, dy, 3, False, out=pre.clone(memory_format=torch.preserve_format))
+            wd = torch.zeros(co, ci, 3, 3, device=DEV, dtype=torch.float64, requires_grad=True)
+            (F.conv2d(x.double(), wd, None, padding=1) * dy.double()).sum().backward()
+            ref = wd.grad + pre.double()
+            native.lib().vqk_conv_set_variant(0)
+            try:
+                dw0 = ops.raw_conv_wgrad(x, dy, 3, False, out=pre.clone(memory_format=torch.preserve_format))
+            finally:
+                native.lib().vqk_conv_set_variant(-1)
+            torch.cuda.synchronize()
         finally:
-            native.lib().vqk_conv_set_variant(-1)
-        torch.cuda.synchronize()
+            events, ops.KERNEL_EVENTS = ops.KERNEL_EVENTS, None
+        # the thin kernel is memory-bound (no FLOPs in the statistics); the hook takes the general fp32 kernel
+        assert [(e[0], e[1] > 0) for e in events] == [('conv3x3_wgrad_thin_f32_kernel (HBM)', False), ('conv_wgrad_kernel<f32>', True)]
         assert _rel(dw, ref) < 1e-5, (co, ci)
         assert _rel(dw0, ref) < 1e-5

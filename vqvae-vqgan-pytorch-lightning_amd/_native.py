@@ -130,6 +130,8 @@ _PROTOS = {
     'vqk_conv2d_wgrad': [I, P, P, P, I, I, I, I, I, I, I, P, P],
     'vqk_conv3x3_wgrad_group': [P, I, P, P],
     'vqk_conv3x3_wgrad_group_plan': [P, I, P, P],
+    'vqk_conv_wgrad_plan': [I, I, I, I, I, I, I, I, I, I, I, I, I, P],
+    'vqk_conv2d_wgrad_edge_serves': [I, I, I, I, I, I],
     'vqk_conv2d_wgrad_pooled_dy': [I, P, P, P, I, I, I, I, I, F, P, P],
     'vqk_conv2d_wgrad_ups_phase': [I, P, P, P, I, I, I, I, I, F, P, P],
     'vqk_split_pair_f32': [P, P, L, I, P],
@@ -195,7 +197,7 @@ _PROTOS = {
     'vqk_arena_stats': [P, L, P, P, I, I, F, P, L, P, P, P],
 }
 _SPECIAL = {'vqk_set_tuning': (I, [c_char_p, I]), 'vqk_reset_tuning': (I, []), 'vqk_tuning_count': (I, []),
-            'vqk_tuning_name': (c_char_p, [I]), 'vqk_conv_fprop_form_name': (c_char_p, [I, I]),
+            'vqk_tuning_name': (c_char_p, [I]), 'vqk_conv_fprop_form_name': (c_char_p, [I, I]), 'vqk_conv_wgrad_form_name': (c_char_p, [I, I]),
             'vqk_conv_packed_elems': (c_int64, [I, I, I, I]), 'vqk_calib_mfma_flops': (c_int64, [I, I]), 'vqk_conv2d_wgrad_edge_ws_bytes': (c_int64, []), 'vqk_vq_filter_ws_bytes': (c_int64, [I, I]), 'vqk_fsq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_lfq_ws_bytes': (c_int64, [L, I, I, I]), 'vqk_bsq_ws_bytes': (c_int64, [L, I, I, I]), 'vqk_rvq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_cos_ws_bytes': (c_int64, [I, I]), 'vqk_cos_backward_ws_bytes': (c_int64, [L, I]), 'vqk_gvq_backward_ws_bytes': (c_int64, [L, I, I]), 'vqk_simvq_backward_ws_bytes': (c_int64, [L, I]), 'vqk_ibq_forward_ws_bytes': (c_int64, [L]), 'vqk_ibq_backward_ws_bytes': (c_int64, [L, I]), 'vqk_kmeans_seed_ws_bytes': (c_int64, [L]), 'vqk_spnorm_ws_bytes': (c_int64, [I, I, I, I, I, I]), 'vqk_conv4x4_wgrad_ws_bytes': (c_int64, [I, I, I, I, I, I, I]), 'vqk_bn_ws_bytes': (c_int64, [L, I]), 'vqk_egress_canvas_bytes': (c_int64, [I, I, I, I, I]), 'vqk_arena_stats_ws_bytes': (c_int64, [L, I]), 'vqk_adamw_bias_table': (c_int64, [F, F, P, L]), 'vqk_status_str': (c_char_p, [I]), 'vqk_version': (I, []), 'vqk_arch': (c_char_p, [])}
 EXPORTS = sorted(list(_PROTOS) + list(_SPECIAL))
 

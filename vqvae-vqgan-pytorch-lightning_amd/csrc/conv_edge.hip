@@ -344,6 +344,14 @@ extern "C" {
 
 int64_t vqk_conv2d_wgrad_edge_ws_bytes(void) { return (int64_t)256 * EDGE_OUT * 4; }
 
+int vqk_conv2d_wgrad_edge_serves(int dtype, int n, int h, int w, int cin, int cout) {
+    if (dtype != VQK_BF16 || n <= 0 || h <= 0 || w <= 0) return 0;
+    const bool first = cin == 8 && cout == EDGE_CW, last = cout == 8 && cin == EDGE_CW;
+    // a 128-pixel patch lies inside one image, and inside one row or on whole rows (the kernel decodes a slot's pixel once)
+    return (first || last) && ((int64_t)h * w) % EDGE_PIX == 0 && (w % EDGE_PIX == 0 || EDGE_PIX % w == 0) &&
+           (int64_t)n * h * w < 0x7fffffffLL;
+}
+
 int vqk_conv2d_wgrad_edge(int dtype, const void* x, const void* dy, float* dw, void* ws, int64_t ws_bytes, int n, int h,
                           int w, int cin, int cout, const void* zeros, void* stream) {
     return vqk_conv2d_wgrad_edge_true(dtype, x, dy, dw, ws, ws_bytes, n, h, w, cin, cout, 8, zeros, stream);
@@ -361,13 +369,9 @@ int vqk_conv2d_wgrad_edge_bias(int dtype, const void* x, const void* dy, float* 
     VQK_REQUIRE(thin_true >= 1 && thin_true <= 8, VQK_ERR_ARG);
     VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy) && vqk_aligned16(ws) && vqk_aligned16(zeros), VQK_ERR_ALIGN);
     VQK_REQUIRE(dtype == VQK_BF16, VQK_ERR_DTYPE);
-    VQK_REQUIRE(n > 0 && h > 0 && w > 0, VQK_ERR_SHAPE);
-    const bool first = cin == 8 && cout == EDGE_CW, last = cout == 8 && cin == EDGE_CW;
-    const int64_t m = (int64_t)n * h * w;
-    // a 128-pixel patch lies inside one image, and inside one row or on whole rows (the kernel decodes a slot's pixel once)
-    VQK_REQUIRE((first || last) && ((int64_t)h * w) % EDGE_PIX == 0 && (w % EDGE_PIX == 0 || EDGE_PIX % w == 0) && m < 0x7fffffffLL,
-                VQK_ERR_SHAPE);
-    const int total = (int)(m / EDGE_PIX);
+    VQK_REQUIRE(vqk_conv2d_wgrad_edge_serves(dtype, n, h, w, cin, cout) == 1, VQK_ERR_SHAPE);
+    const bool first = cin == 8;
+    const int total = (int)(((int64_t)n * h * w) / EDGE_PIX);
     int blocks = total < 256 ? total : 256;
     VQK_REQUIRE(ws_bytes >= (int64_t)blocks * EDGE_OUT * 4, VQK_ERR_ARG);
     hipStream_t st = vqk_stream(stream);

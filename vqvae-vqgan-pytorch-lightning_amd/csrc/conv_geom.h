@@ -50,8 +50,7 @@ struct ConvGeom {
                     // forward-type phase launch compute  nearest-x2(dy) * flip(W)^T  = the data gradient of a conv FOLLOWED BY a
                     // 2x2 average pool from the pooled gradient (vqk_conv2d_pooled_dgrad_phase): phase (a, b) of the mirrored
                     // kernel is phase (1-a, 1-b) of the unmirrored one with its 2x2 window mirrored
-    int dy_pool;    // weight-gradient mx kernel: dy is given at HALF resolution (the gradient of a fused 2x2 average pool: every
-                    // pooled pixel stands for its 2x2 block), dW is scaled by acc_scale
+    int dy_pool;    // weight-gradient mx kernel: the operand mode, one of the WgradDyPool values below
     int act;        // matrix/auxiliary-wave kernel: epilogue activation (0 none, 2 relu, 3 leaky relu 0.2), with acc_scale / out_gain
     // matrix/auxiliary-wave kernel: DYNAMIC TILE QUEUE (vqk_set_tile_queue + tuning slot TILE_QUEUE).  tq = nullptr: the static
     // share (tile j of block b = b + j * grid).  Otherwise tq[0..7] are the per-XCD counters and tq[8] the census of finished
@@ -111,6 +110,26 @@ enum ConvVariant : int {
     CONV_VARIANT_NO_MX = 5,          // never the matrix/auxiliary-wave kernel (nor its 1x1, phase and stride-2 forms)
     CONV_VARIANT_MX = 6,             // that kernel whenever the shape is eligible, below MX_MIN_TILES too
 };
+// the values of ConvGeom::dy_pool, read by the weight-gradient matrix/auxiliary-wave kernel (conv_wgmx.hip)
+enum WgradDyPool : int {
+    WGRAD_DY_PLAIN = 0,              // dy at the resolution of the conv's output
+    WGRAD_DY_POOLED = 1,             // dy at HALF resolution (the gradient of a fused 2x2 average pool: every pooled pixel stands for
+                                     // its 2x2 block), dW is scaled by acc_scale
+    WGRAD_DY_PHASE0 = 2,             // 2..5: ONE output phase (a, b) of an upsample conv in phase form, value 2 + 2a + b: x is the
+                                     // low-resolution input, dy at twice its resolution is gathered at stride 2
+    WGRAD_DY_PHASES = 6,             // the four phases merged into one launch (phase = a dimension of the grid)
+    WGRAD_DY_PHASES_SWAPPED = 7,     // ... with the operands' roles swapped: the conv FOLLOWED by a 2x2 average pool, from the pooled
+                                     // gradient ("x" of the kernel = dy_pooled, its phase-gathered "dy" = the conv's input)
+};
+// what a weight-gradient entry point asks of the launch plan (conv_wgrad.hip::plan_wgrad); part of the C-ABI (vqk_conv_wgrad_plan)
+enum WgradOp : int {
+    WGRAD_OP_PLAIN = 0,              // vqk_conv2d_wgrad / _general / _general_scaled
+    WGRAD_OP_POOLED_DY = 1,          // vqk_conv2d_wgrad_pooled_dy
+    WGRAD_OP_UPS_PHASE = 2,          // vqk_conv2d_wgrad_ups_phase
+    WGRAD_OP_POOLED_DY_PHASE = 3,    // vqk_conv2d_wgrad_pooled_dy_phase
+    WGRAD_OP_FOLD = 4,               // vqk_conv2d_wgrad_x3: (hi | lo) pair operands (ConvGeom::fold)
+    WGRAD_OP_X3 = 5,                 // vqk_conv2d_wgrad_x3_f32: the split-product kernel straight from the fp32 tensors
+};
 namespace vqkd {
 int& conv_force_variant();
 int& conv_wgrad_blocks();
@@ -119,8 +138,9 @@ int& conv_wgrad_blocks();
 bool conv3x3_x3_serves(const ConvGeom& g);   // the shapes the launcher takes (the rest: VQK_ERR_SHAPE)
 int launch_conv3x3_x3(const void* x, const void* w, const float* bias, const void* res, void* y, const void* zeros,
                       const ConvGeom& g, int act, int blocks_cap, hipStream_t st);
-// ... and its weight gradient straight from the fp32 tensors (no pair tensors): fp32 atomics into dw
-int launch_conv3x3_wgrad_x3(const void* x, const void* dy, float* dw, const ConvGeom& g, int blocks_cap, hipStream_t st);
+// ... and its weight gradient straight from the fp32 tensors (no pair tensors): fp32 atomics into dw; grid = tiles x splits blocks
+// (x 4 phases where g.ntap == 4), `pps` 8x8-pixel patches per split
+int launch_conv3x3_wgrad_x3(const void* x, const void* dy, float* dw, const ConvGeom& g, int tiles, int splits, int pps, hipStream_t st);
 
 // exact-fp32 kernels of the two edge convs (conv_thin_f32.hip): one side of the GEMM is the 4-channel (padded 3-channel) tensor
 int launch_conv3x3_thin_out_f32(const float* x, const float* w, const float* bias, const float* res, float* y, int n, int h, int wd,

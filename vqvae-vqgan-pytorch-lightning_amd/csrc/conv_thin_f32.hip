@@ -305,7 +305,7 @@ static inline size_t thin_wgrad_lds(int R, int w) {
 }
 
 // output rows per block of the weight-gradient kernel: the largest R in {8, 4, 2, 1} that divides h and whose R + 2 staged thin
-// rows fit in 64 KiB of LDS (8 rows up to w = 407, 1 row up to w = 1363); 0 when no R fits -- wgrad_general then takes the
+// rows fit in 64 KiB of LDS (8 rows up to w = 407, 1 row up to w = 1363); 0 when no R fits -- plan_wgrad then takes the
 // general fp32 kernel.  The dispatch (conv_wgrad.hip) and the launcher below both ask this, so they cannot disagree.
 int thin_wgrad_rows(int h, int w) {
     for (int R = thin_rows_per_block(h); R >= 1; R >>= 1)

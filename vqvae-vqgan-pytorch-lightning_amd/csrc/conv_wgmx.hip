@@ -20,7 +20,7 @@
 // window of low-resolution shifts occurs, so  dW[ky][kx] = sum over the four phases of G_ab[r(a,ky)][s(b,kx)],
 // G_ab[r][s] = sum_ij dy[2i+a][2j+b] x[i+r][j+s] -- sixteen low-resolution tap GEMMs over a quarter of the pixels each instead of
 // nine full-resolution ones: 4/9 of the multiply-adds, like the phase form of the forward / data gradient (conv_mx.hip).  One
-// launch per phase (g.dy_pool = 2 + 2a + b): x is the LOW-resolution input with the ordinary halo, the dy patch is gathered at
+// launch per phase (g.dy_pool = WGRAD_DY_PHASE0 + 2a + b): x is the LOW-resolution input with the ordinary halo, the dy patch is gathered at
 // stride 2 from the full-resolution gradient by the LDS-DMA source addresses, four accumulators per wave, and the final atomic
 // pass adds G[ty][tx] to every tap (ky, kx) it stands for (1, 2 or 4 of them).
 // ------------------------------------------------------------------------------------------------
@@ -219,7 +219,7 @@ __device__ __forceinline__ void wgrad_mx_body(const bf16_raw* __restrict__ x, co
 #pragma unroll
     for (int sl = 0; sl < NDY; ++sl) {
         const int q = xw + 4 * sl, half = q >> 3, prow = q & 7;
-        // dy_pool 1: dy at HALF resolution (every pooled pixel stands for its 2x2 block); >= 2 (NT = 4): dy at TWICE the resolution
+        // dy_pool WGRAD_DY_POOLED: dy at HALF resolution (every pooled pixel stands for its 2x2 block); >= 2 (NT = 4): dy at TWICE the resolution
         // of the patch grid, one phase of it gathered at stride 2
         dyoff[sl] = g.dy_pool == 1 ? (unsigned)(((((prow >> 1) * (g.w >> 1) + (lrow >> 1)) * g.cout) + co0m + half * 32 + lch) * 2)
                   : g.dy_pool >= 2 ? (unsigned)(((((2 * prow) * (2 * g.w) + 2 * lrow) * g.cout) + co0m + half * 32 + lch) * 2)
@@ -320,10 +320,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_mx_kernel(const bf16_raw
     const int co0 = tco * 64, ci0 = tci * 64;                    // dW tile (true channels)
     const int co0m = co0 + (cls == 2 ? cout_t : 0), ci0m = ci0 + (cls == 1 ? cin_t : 0);      // operand channels in memory
     const int total_patches = g.n * (g.h >> 3) * (g.w >> 4);
-    // NT = 4: g.dy_pool = 2 + phase (one phase per launch) or 6 (ALL FOUR phases in one launch: phase = by & 3, split = by >> 2 --
+    // NT = 4 (values: conv_geom.h, WgradDyPool): g.dy_pool = WGRAD_DY_PHASE0 + phase (one phase per launch) or WGRAD_DY_PHASES (ALL FOUR phases in one launch: phase = by & 3, split = by >> 2 --
     // a block still owns one phase, i.e. four accumulators, but the launch fills the chip with a quarter of the splits per phase:
     // per-block prologue and atomic pass are amortised over 4x the patches of the one-phase-per-launch form)
-    // g.dy_pool = 7: as 6 with the operands' ROLES SWAPPED -- the weight gradient of a conv followed by a 2x2 average pool from the
+    // g.dy_pool = WGRAD_DY_PHASES_SWAPPED: the same with the operands' ROLES SWAPPED -- the weight gradient of a conv followed by a 2x2 average pool from the
     // POOLED gradient: dW[ky][kx] = sum_YX dyp[Y>>1][X>>1] x[Y+ky-1][X+kx-1] re-indexed over the phases (a', b') of the FULL-resolution
     // x: G'[r'][s'] = sum_ij x[2i+a'][2j+b'] dyp[i+r'][j+s'] over the same 2x2 windows.  The phase-gathered operand ("dy" of this
     // kernel) is x, the windowed low-resolution operand ("x" of this kernel) is the pooled gradient; the tile comes out transposed
@@ -384,8 +384,8 @@ namespace vqkd {
 int launch_conv3x3_wgrad_mx(const void* x, const void* dy, float* dw, const void* zeros, const ConvGeom& g, int tiles,
                             int splits, int pps, hipStream_t st, float* part) {
     if (g.fold && (g.dy_pool || part)) return VQK_ERR_ARG;        // split-product operands: plain 3x3 form, atomics only
-    if (g.dy_pool >= 2) {                                         // one output phase of an upsample conv: the 2x2-window form
-        if (g.dy_pool > 7 || part || (g.dy_pool >= 6 && (splits & 3))) return VQK_ERR_ARG;
+    if (g.dy_pool >= WGRAD_DY_PHASE0) {                           // the 2x2-window form: one output phase of an upsample conv, or all four
+        if (g.dy_pool > WGRAD_DY_PHASES_SWAPPED || part || (g.dy_pool >= WGRAD_DY_PHASES && (splits & 3))) return VQK_ERR_ARG;
         static const hipError_t attr4 = hipFuncSetAttribute((const void*)conv3x3_wgrad_mx_kernel<4>,
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, VQK_WGMX_NST * 40960);
         if (attr4 != hipSuccess) return VQK_ERR_LAUNCH;

@@ -667,169 +667,426 @@ inline int make_geom(ConvGeom& g, int dtype, int n, int h_in, int w_in, int cin,
     return vqkd::conv_make_geom(g, dtype, n, h_in, w_in, cin, cout, ksize, ups);
 }
 
-}  // namespace
+// ---- the weight-gradient dispatch: plan_wgrad decides and launches nothing, launch_wgrad launches what it decided ----
+// The kernel forms.  The ids are part of the C-ABI (vqk_conv_wgrad_plan returns them): append, never renumber.
+enum WgradForm : int {
+    WGF_MX = 0,              // conv_wgmx.hip: matrix/auxiliary-wave kernel, plain 3x3 (tap form behind a nearest-x2 upsample too)
+    WGF_MX_POOLED_DY,        // ... dy at half resolution (WGRAD_DY_POOLED)
+    WGF_MX_UPS_PHASE,        // ... upsample conv in phase form: one merged launch, or four (tuning slot UPS_MERGE = 0)
+    WGF_MX_POOLED_DY_PHASE,  // ... phase form with the operands' roles swapped (WGRAD_DY_PHASES_SWAPPED)
+    WGF_MX_FOLD,             // ... (hi | lo) pair operands of the split-product mode, three tile classes (ConvGeom::fold)
+    WGF_P16,                 // conv3x3_wgrad_p16_kernel: 8x16 patches, whole 64-channel tiles
+    WGF_HALO16,              // conv3x3_wgrad_halo_kernel<true>: 8x16 patches
+    WGF_HALO8,               // conv3x3_wgrad_halo_kernel<false>: 8x8 patches
+    WGF_THIN_F32_CIN4,       // conv_thin_f32.hip: fp32, 4 input channels (memory-bound)
+    WGF_THIN_F32_COUT4,      // conv_thin_f32.hip: fp32, 4 output channels (memory-bound)
+    WGF_GENERAL_F32,         // conv_wgrad_kernel<float>
+    WGF_GENERAL_BF16,        // conv_wgrad_kernel<bf16>: 3x3 (strided, explicitly padded, shapes no patch kernel takes)
+    WGF_GENERAL_DB,          // conv_wgrad_db_kernel: bf16 1x1, double-buffered
+    WGF_X3,                  // conv_x3.hip: split-product kernel from the fp32 tensors, tap form
+    WGF_X3_UPS_PHASE,        // ... phase form of an upsample conv (ups = 1)
+    WGF_X3_POOLED_PHASE,     // ... phase form of a conv followed by a 2x2 average pool, from the pooled gradient (ups = 2)
+    WGF_COUNT
+};
 
-extern "C" {
+// What an entry point hands to the plan: the arguments of vqk_conv2d_wgrad_general with the conv's TRUE channel counts.  The
+// pooled / phase ops: (h_in, w_in) = their entry point's (h, w), plain 3x3; WGRAD_OP_X3: mode = its `ups` (0, 1, 2)
+struct WgradProblem {
+    int op;                  // WgradOp
+    int dtype, n, h_in, w_in, cin, cout, ksize, stride, pad, mode, h_out, w_out;
+    float scale;             // dW += scale * (x^T dy)
+};
+inline WgradProblem plain3x3(int op, int dtype, int n, int h, int w, int cin, int cout, int ups, float scale) {
+    return {op, dtype, n, h, w, cin, cout, 3, 1, 1, ups, ups == 1 ? 2 * h : h, ups == 1 ? 2 * w : w, scale};
+}
 
-static int wgrad_general(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin, int cout,
-                         int ksize, int stride, int pad, int mode, int h_out, int w_out, const void* zeros, void* stream,
-                         int dy_pool = 0, float dy_scale = 1.0f, int fold = 0) {
-    VQK_REQUIRE(x && dy && dw && zeros, VQK_ERR_ARG);
-    VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy) && vqk_aligned16(zeros), VQK_ERR_ALIGN);
-    VQK_REQUIRE(mode >= 0 && mode <= 1 && (stride == 1 || stride == 2) && pad >= 0, VQK_ERR_ARG);
-    ConvGeom g;
-    const int rc = make_geom(g, dtype, n, h_in, w_in, cin, cout, ksize, mode);
-    if (rc) return rc;
-    const int epc = dtype == VQK_F32 ? 4 : 8;
-    VQK_REQUIRE(cout % epc == 0, VQK_ERR_SHAPE);
-    g.acc_scale = dy_scale;                                      // dW += dy_scale * (x^T dy): every kernel below scales its partial sums
-    const bool plain = stride == 1 && pad == (ksize >> 1) && h_out == g.h && w_out == g.w;
-    if (!plain) {
-        g.stride = stride; g.pad = pad;
-        VQK_REQUIRE(h_out > 0 && w_out > 0, VQK_ERR_SHAPE);
-        g.h = h_out; g.w = w_out;
-        const int64_t m = (int64_t)n * h_out * w_out;
-        VQK_REQUIRE(m < 0x7fffff00, VQK_ERR_SHAPE);
-        g.m = (int)m;
+struct WgradPlan {
+    int status;     // VQK_OK, or what the entry point returns instead of launching
+    int form;       // WgradForm
+    int tiles;      // dW tiles = grid x (the thin fp32 forms: blocks)
+    int splits;     // split-K parts (1: unsplit); the phase forms carry this many per phase
+    int pps;        // pixel patches (general kernels: pixels; thin fp32 forms: rows) per part
+    int launches;   // kernel launches: 4 for the per-phase loop, 2 with the ordered reduce
+    int ordered;    // deterministic mode's workspace is used: the parts' partial sums are stored there and added in order
+};
+struct WgradSplit { int splits, pps; };
+
+// The shapes the matrix/auxiliary-wave kernel takes (whole 8x16 patches, whole 64-channel tiles of the conv's true channels) ...
+inline bool mx_wgrad_shape_ok(int h, int w, int cin, int cout) {
+    return (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0;
+}
+// ... and the state it is allowed in.  Every op: the WGMX slot on, no test hook, and neither A/B slot of the halo kernels set
+// (WGRAD_BLOCKS sizes their grid, WGRAD_NO_PW16 takes their 8x16 patches away).  Deterministic mode: the ordered workspace exists
+// for the NT = 9 kernel of ONE layer, so the plain and pooled-dy ops keep the kernel; the phase forms, the pair operands and the
+// grouped launch add with atomics only and refuse (their callers fall back to the plain op).  The swapped roles of
+// WGRAD_OP_POOLED_DY_PHASE exist in the merged launch only (UPS_MERGE); the upsample conv's phase form also runs a phase per launch.
+inline bool mx_wgrad_enabled(int op, bool grouped = false) {
+    if (!VQK_TUNE("WGMX", 1) || g_general_only || VQK_TUNE("WGRAD_BLOCKS", 0) != 0 || VQK_TUNE("WGRAD_NO_PW16", 0) != 0) return false;
+    if (g_det && (grouped || (op != WGRAD_OP_PLAIN && op != WGRAD_OP_POOLED_DY))) return false;
+    return op != WGRAD_OP_POOLED_DY_PHASE || VQK_TUNE("UPS_MERGE", 1) != 0;
+}
+
+// split-K of the halo / p16 kernels over pixel patches.  Cost model fitted on MI355X (tools/convbench.py sweeps): MFMA time falls
+// with the number of resident blocks (up to 2 per CU) while every split adds one fp32 atomic pass over dW (~1.1 TB/s):
+// t(s) = F / (R * min(1, tiles*s/512)) + s * |dW| / B  =>  s* = sqrt(0.16 * pixels / tiles) below the block cap.
+WgradSplit split_halo(int m, int tiles, int total_patches, bool pw16) {
+    const int target = VQK_TUNE("WGRAD_BLOCKS", 0);
+    const int cap = g_wgrad_blocks > 0 ? g_wgrad_blocks : 512;
+    int splits;
+    if (target > 0) splits = (target + tiles - 1) / tiles;
+    else {
+        splits = (int)(sqrt(0.16 * (double)m / tiles) + 0.5);
+        if (splits > (cap + tiles - 1) / tiles) splits = (cap + tiles - 1) / tiles;
     }
-    if (fold) {
-        // (hi | lo) pair operands of the split-product mode: only the matrix/auxiliary-wave kernel has the folded tile classes
-        VQK_REQUIRE(plain && dtype == VQK_BF16 && ksize == 3 && (g.h % 8) == 0 && (g.w % 16) == 0 && (cin % 128) == 0 && (cout % 128) == 0
-                    && !dy_pool && !g_det && !g_general_only && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
-                    && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
+    const int minp = pw16 ? 2 : 4;                                              // >= 256 pixels per block
+    if (splits > (total_patches + minp - 1) / minp) splits = (total_patches + minp - 1) / minp;
+    if (splits < 1 || g_det) splits = 1;                         // deterministic: one block per dW tile, no cross-block sums
+    const int pps = (total_patches + splits - 1) / splits;
+    return {(total_patches + pps - 1) / pps, pps};
+}
+
+// split-K of the matrix/auxiliary-wave form: ONE 512-thread block per CU, so half as many resident blocks as the cost model
+// above assumes: s* = sqrt(0.08 * pixels / tiles) under half the block cap.  nph = 4: all four phases of an upsample conv in one
+// launch, 4 x the blocks.  ordered (deterministic mode): the partial tiles go to the workspace and are summed in split order
+WgradSplit split_mx(int m, int tiles, int total_patches, int nph, int& ordered) {
+    const int cap = g_wgrad_blocks > 0 ? g_wgrad_blocks : 512;
+    const double coef = VQK_TUNE("WGMX_COEF_E4", 800) * 1e-4;          // (knob in units of 1e-4)
+    const int comm = VQK_TUNE("COMM_CUS", 0);               // CUs left to a running collective (conv_mx.hip)
+    const int capm = (cap / 2 - comm) / nph > tiles ? (cap / 2 - comm) / nph : tiles;
+    int sm = (int)(sqrt(coef * (double)m / tiles) + 0.5);
+    if (sm > (capm + tiles - 1) / tiles) sm = (capm + tiles - 1) / tiles;
+    if (sm > (total_patches + 3) / 4) sm = (total_patches + 3) / 4;          // >= 4 patches per block
+    if (g_det) {                                             // no more partial tiles than the workspace holds
+        const int64_t per_split = (int64_t)tiles * 64 * 9 * 64 * 4;
+        const int fit = (int)(g_det_ws_bytes / per_split);
+        if (sm > fit) sm = fit;
     }
-    if (plain && dtype == VQK_BF16 && ksize == 3 && (g.h % 8) == 0 && (g.w % 8) == 0 && !g_general_only) {
-        const int tiles = fold ? 3 * (cout / 128) * (cin / 128) : ((cout + 63) / 64) * ((cin + 63) / 64);
-        const bool no_pw16 = VQK_TUNE("WGRAD_NO_PW16", 0) != 0;
-        const bool pw16 = (g.w % 16) == 0 && !no_pw16;
-        const int total_patches = g.n * (g.h / 8) * (g.w / (pw16 ? 16 : 8));
-        // split-K over pixel patches.  Cost model fitted on MI355X (tools/convbench.py sweeps): MFMA time falls with the
-        // number of resident blocks (up to 2 per CU) while every split adds one fp32 atomic pass over dW (~1.1 TB/s):
-        // t(s) = F / (R * min(1, tiles*s/512)) + s * |dW| / B  =>  s* = sqrt(0.16 * pixels / tiles) below the block cap.
-        const int target = VQK_TUNE("WGRAD_BLOCKS", 0);
-        const int cap = g_wgrad_blocks > 0 ? g_wgrad_blocks : 512;
-        int splits;
-        if (target > 0) splits = (target + tiles - 1) / tiles;
-        else {
-            splits = (int)(sqrt(0.16 * (double)g.m / tiles) + 0.5);
-            if (splits > (cap + tiles - 1) / tiles) splits = (cap + tiles - 1) / tiles;
-        }
-        const int minp = pw16 ? 2 : 4;                                              // >= 256 pixels per block
-        if (splits > (total_patches + minp - 1) / minp) splits = (total_patches + minp - 1) / minp;
-        if (splits < 1 || g_det) splits = 1;                     // deterministic: one block per dW tile, no cross-block sums
-        const int pps = (total_patches + splits - 1) / splits;
-        splits = (total_patches + pps - 1) / pps;
-        const dim3 grid((unsigned)tiles, (unsigned)splits);
-        const bool no_p16k = VQK_TUNE("WGRAD_NO_P16K", 0) != 0;
-        const int wgmx = VQK_TUNE("WGMX", 1);
-        if (pw16 && (cin % 64) == 0 && (cout % 64) == 0 && wgmx && target == 0) {
-            // matrix/auxiliary-wave form: ONE 512-thread block per CU, so half as many resident blocks as the cost model
-            // above assumes: s* = sqrt(0.08 * pixels / tiles) under half the block cap
-            const double coef = VQK_TUNE("WGMX_COEF_E4", 800) * 1e-4;          // (knob in units of 1e-4)
-            const int comm = VQK_TUNE("COMM_CUS", 0);               // CUs left to a running collective (conv_mx.hip)
-            const int nph = dy_pool >= 6 ? 4 : 1;                   // all four phases of an upsample conv in one launch: 4 x the blocks
-            const int capm = (cap / 2 - comm) / nph > tiles ? (cap / 2 - comm) / nph : tiles;
-            int sm = (int)(sqrt(coef * (double)g.m / tiles) + 0.5);
-            if (sm > (capm + tiles - 1) / tiles) sm = (capm + tiles - 1) / tiles;
-            if (sm > (total_patches + 3) / 4) sm = (total_patches + 3) / 4;          // >= 4 patches per block
-            float* part = nullptr;
-            if (g_det) {                                         // partial tiles in the workspace, summed in split order
-                const int64_t per_split = (int64_t)tiles * 64 * 9 * 64 * 4;
-                const int fit = (int)(g_det_ws_bytes / per_split);
-                if (sm > fit) sm = fit;
-                part = sm >= 2 ? g_det_ws : nullptr;             // a single split owns every element: its atomics are plain adds
-            }
-            if (sm < 1) sm = 1;
-            const int ppm = (total_patches + sm - 1) / sm;
-            sm = (total_patches + ppm - 1) / ppm;
-            if (sm < 2) part = nullptr;
-            ConvGeom gm = g;
-            gm.dy_pool = dy_pool; gm.acc_scale = dy_scale; gm.fold = fold;
-            return vqkd::launch_conv3x3_wgrad_mx(x, dy, dw, zeros, gm, tiles, sm * nph, ppm, vqk_stream(stream), part);
-        }
-        if (dy_pool || fold) return VQK_ERR_SHAPE;              // half-resolution dy / pair operands exist on the matrix/auxiliary-wave kernel only
-        if (pw16 && (cin % 64) == 0 && (cout % 64) == 0 && !no_p16k) {
-            static const hipError_t attr = hipFuncSetAttribute((const void*)conv3x3_wgrad_p16_kernel,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 40960);
-            (void)attr;
-            hipLaunchKernelGGL(conv3x3_wgrad_p16_kernel, grid, dim3(256), 2 * 40960, vqk_stream(stream),
-                               (const bf16_raw*)x, (const bf16_raw*)dy, dw, (const char*)zeros, g, pps);
-        } else if (pw16) {
-            static const hipError_t attr = hipFuncSetAttribute((const void*)conv3x3_wgrad_halo_kernel<true>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 40960);
-            (void)attr;
-            hipLaunchKernelGGL(conv3x3_wgrad_halo_kernel<true>, grid, dim3(256), 2 * 40960, vqk_stream(stream),
-                               (const bf16_raw*)x, (const bf16_raw*)dy, dw, (const char*)zeros, g, pps);
-        } else {
-            hipLaunchKernelGGL(conv3x3_wgrad_halo_kernel<false>, grid, dim3(256), 2 * 22528, vqk_stream(stream),
-                               (const bf16_raw*)x, (const bf16_raw*)dy, dw, (const char*)zeros, g, pps);
-        }
-        VQK_CHECK_LAUNCH();
-        return VQK_OK;
-    }
-    if (plain && dtype == VQK_F32 && ksize == 3 && mode == 0 && !g_det && !dy_pool && !g_general_only && (g.w % 4) == 0 &&
-        vqkd::thin_wgrad_rows(g.h, g.w) > 0) {
-        // the edge convs' weight gradients in the fp32 modes (conv_thin_f32.hip); maps too wide for one staged row in LDS take the
-        // general kernel below
-        if (cin == 4 && (cout == 64 || cout == 128 || cout == 256))
-            return vqkd::launch_conv3x3_wgrad_thin_f32(0, (const float*)dy, (const float*)x, dw, n, g.h, g.w, cout, dy_scale, vqk_stream(stream));
-        if (cout == 4 && (cin == 64 || cin == 128 || cin == 256))
-            return vqkd::launch_conv3x3_wgrad_thin_f32(1, (const float*)x, (const float*)dy, dw, n, g.h, g.w, cin, dy_scale, vqk_stream(stream));
-    }
-    const int kp = dtype == VQK_F32 ? 32 : 64;
-    const int tiles = ((cout + 127) / 128) * ((cin + 127) / 128) * ksize * ksize;
-    // split the pixel range so that ~2048 blocks are in flight, each with >= 4 K-steps (fp32); the double-buffered bf16
-    // kernel keeps two 64-KiB blocks per CU busy with ~512 blocks and a quarter of the atomic passes over dW (each block
-    // ends with one: at 2048 blocks the 1x1 shortcut's 128 x 256 gradient cost 134 MB of atomics per launch)
-    // (measured, tools/wgrad_gen_bench.py: 1x1 128->256 @128^2 167 -> 67 us; the strided 3x3 gathers are faster on the
-    // single-stage kernel with ~2048 blocks -- 421 vs 302 us at 128->256 @257^2 stride 2 -- and keep it)
+    if (sm < 1) sm = 1;
+    const int ppm = (total_patches + sm - 1) / sm;
+    sm = (total_patches + ppm - 1) / ppm;
+    ordered = g_det && sm >= 2;                              // a single split owns every element: its atomics are plain adds
+    return {sm, ppm};
+}
+
+// split-K of the general kernels over pixels, in steps of kp: split the pixel range so that ~2048 blocks are in flight, each
+// with >= 4 K-steps (fp32); the double-buffered bf16 kernel keeps two 64-KiB blocks per CU busy with ~512 blocks and a quarter of
+// the atomic passes over dW (each block ends with one: at 2048 blocks the 1x1 shortcut's 128 x 256 gradient cost 134 MB of
+// atomics per launch) (measured, tools/wgrad_gen_bench.py: 1x1 128->256 @128^2 167 -> 67 us; the strided 3x3 gathers are faster
+// on the single-stage kernel with ~2048 blocks -- 421 vs 302 us at 128->256 @257^2 stride 2 -- and keep it)
+WgradSplit split_general(int m, int tiles, int kp, bool db, int64_t dw_elems) {
     const int wg_target = VQK_TUNE("WGRAD_GEN_BLOCKS", 512);
-    const bool db = dtype == VQK_BF16 && ksize == 1;
     const int target_blocks = db ? wg_target : 2048;
     int splits = (target_blocks + tiles - 1) / tiles;
-    const int max_splits = (g.m + 4 * kp - 1) / (4 * kp);
+    const int max_splits = (m + 4 * kp - 1) / (4 * kp);
     if (splits > max_splits) splits = max_splits;
-    const int64_t dw_elems = (int64_t)cout * ksize * ksize * cin;
     if (g_det) {                                                 // deterministic: private copies of dW per split + ordered reduce
         const int64_t fit = g_det_ws ? g_det_ws_bytes / (dw_elems * 4) : 0;
         if (splits > fit) splits = (int)fit;
     }
     if (splits < 1) splits = 1;
-    int pps = (g.m + splits - 1) / splits;
+    int pps = (m + splits - 1) / splits;
     pps = ((pps + kp - 1) / kp) * kp;
-    splits = (g.m + pps - 1) / pps;
-    const dim3 grid((unsigned)(((cout + 127) / 128) * ((cin + 127) / 128)), (unsigned)(ksize * ksize), (unsigned)splits);
-    float* dst = dw;
-    int64_t sstride = 0;
-    const bool det_split = g_det && splits > 1;
-    if (det_split) {
-        dst = g_det_ws; sstride = dw_elems;
-        if (hipMemsetAsync(g_det_ws, 0, (size_t)splits * dw_elems * 4, vqk_stream(stream)) != hipSuccess) return VQK_ERR_LAUNCH;
+    return {(m + pps - 1) / pps, pps};
+}
+
+// split-K of the split-product kernel over 8x8-pixel patches: the cost model of the bf16 kernels (split_halo) with a third of
+// their atomic passes per multiply-add -- s* = sqrt(c * pixels / tiles) under the block cap (two blocks per CU)
+WgradSplit split_x3(int m, int tiles, int total_patches, int phases) {
+    int cap = g_wgrad_blocks > 0 ? g_wgrad_blocks : 512;
+    if (phases == 4) cap = cap * VQK_TUNE("X3_WGRAD_PHASE_CAP_PCT", 150) / 100;      // 166 VGPRs: a third block fits a CU (step 70.39 -> 69.89 ms)
+    const double coef = (phases == 4 ? VQK_TUNE("X3_WGRAD_PHASE_COEF_E4", 3200) : VQK_TUNE("X3_WGRAD_COEF_E4", 3200)) * 1e-4;
+    // (phase forms: the four phases are four times the blocks -- a quarter of the splits each, the same number of atomic passes)
+    int splits = (int)(sqrt(coef * (double)m * phases / tiles) / phases + 0.5);
+    if (splits > (cap + tiles * phases - 1) / (tiles * phases)) splits = (cap + tiles * phases - 1) / (tiles * phases);
+    if (splits > (total_patches + 3) / 4) splits = (total_patches + 3) / 4;          // >= 256 pixels per block
+    if (splits < 1) splits = 1;
+    const int pps = (total_patches + splits - 1) / splits;
+    return {(total_patches + pps - 1) / pps, pps};
+}
+
+// What an op's entry point tests before it looks at a pointer: the op's shape rule and the state of the kernel it exists on
+int wgrad_op_check(const WgradProblem& q) {
+    if (q.op == WGRAD_OP_PLAIN || q.op == WGRAD_OP_X3) return VQK_OK;
+    if (q.op == WGRAD_OP_FOLD) {                                 // (its state is tested behind the geometry, with the map's shape)
+        VQK_REQUIRE(q.mode == 0 || q.mode == 1, VQK_ERR_ARG);
+        VQK_REQUIRE((q.cin % 64) == 0 && (q.cout % 64) == 0, VQK_ERR_SHAPE);
+        return VQK_OK;
     }
-    if (dtype == VQK_F32)
-        hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), 32768, vqk_stream(stream), (const float*)x, (const float*)dy, dst, (const char*)zeros, g, pps, sstride);
-    else if (db) {
-        static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_db_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        if (attr != hipSuccess) return VQK_ERR_LAUNCH;
-        hipLaunchKernelGGL(conv_wgrad_db_kernel, grid, dim3(256), 65536, vqk_stream(stream), (const bf16_raw*)x, (const bf16_raw*)dy, dst, (const char*)zeros, g, pps, sstride);
+    VQK_REQUIRE(q.op == WGRAD_OP_POOLED_DY || q.op == WGRAD_OP_UPS_PHASE || q.op == WGRAD_OP_POOLED_DY_PHASE, VQK_ERR_ARG);
+    VQK_REQUIRE(q.dtype == VQK_BF16 && mx_wgrad_shape_ok(q.h_in, q.w_in, q.cin, q.cout) && mx_wgrad_enabled(q.op), VQK_ERR_SHAPE);
+    return VQK_OK;
+}
+
+// The split-product kernel straight from the fp32 tensors (vqk_conv2d_wgrad_x3_f32): atomics only, deterministic mode keeps the
+// exact-fp32 kernel
+WgradPlan plan_wgrad_x3(const WgradProblem& q, ConvGeom& g) {
+    WgradPlan p = {VQK_OK, WGF_X3, 0, 1, 0, 1, 0};
+    auto refuse = [&](int status) { p.status = status; return p; };
+    const int ups = q.mode;
+    if (ups != 0 && ups != 1 && ups != 2) return refuse(VQK_ERR_ARG);
+    if (g_det || g_general_only) return refuse(VQK_ERR_SHAPE);
+    const bool phase = ups == 2 || (ups == 1 && VQK_TUNE("X3_WGRAD_PHASE", 1) && (q.h_in % 8) == 0 && (q.w_in % 8) == 0);
+    if (phase) {
+        // the 2x2-resampling convs in phase form (4/9 of the MFMAs): patches over the LOW-resolution grid.  ups = 1: x [n][h_in][w_in] is
+        // that grid, dy [n][2 h_in][2 w_in]; ups = 2: dy = the pooled gradient [n][h_in / 2][w_in / 2] of a conv over x [n][h_in][w_in]
+        if (ups == 2 && ((q.h_in % 16) != 0 || (q.w_in % 16) != 0)) return refuse(VQK_ERR_SHAPE);
+        const int rc = make_geom(g, VQK_F32, q.n, ups == 2 ? q.h_in / 2 : q.h_in, ups == 2 ? q.w_in / 2 : q.w_in, q.cin, q.cout, 3, 0);
+        if (rc) return refuse(rc);
+        g.ntap = 4; g.phase_mode = ups == 2 ? 2 : 1;
     } else {
-        hipLaunchKernelGGL(conv_wgrad_kernel<bf16_raw>, grid, dim3(256), 32768, vqk_stream(stream), (const bf16_raw*)x, (const bf16_raw*)dy, dst, (const char*)zeros, g, pps, sstride);
+        const int rc = make_geom(g, VQK_F32, q.n, q.h_in, q.w_in, q.cin, q.cout, 3, ups);
+        if (rc) return refuse(rc);
     }
-    if (det_split)
-        hipLaunchKernelGGL(wgrad_split_reduce_kernel, dim3((unsigned)((dw_elems + 255) / 256)), dim3(256), 0, vqk_stream(stream),
-                           (const float*)g_det_ws, dw_elems, splits, dw);
+    g.acc_scale = q.scale;
+    if ((g.cin & 63) || (g.cout & 63) || (g.h & 7) || (g.w & 7)) return refuse(VQK_ERR_SHAPE);
+    p.form = !phase ? WGF_X3 : ups == 1 ? WGF_X3_UPS_PHASE : WGF_X3_POOLED_PHASE;
+    p.tiles = (g.cout >> 6) * (g.cin >> 6);
+    const WgradSplit s = split_x3(g.m, p.tiles, g.n * (g.h >> 3) * (g.w >> 3), phase ? 4 : 1);
+    p.splits = s.splits; p.pps = s.pps;
+    return p;
+}
+
+// Fills the kernel's geometry `g` and names the form, the grid and the split.  Reads the tuning slots and the calling thread's
+// block cap, variant hook and deterministic state; touches no device.
+WgradPlan plan_wgrad(const WgradProblem& q, ConvGeom& g) {
+    if (q.op == WGRAD_OP_X3) return plan_wgrad_x3(q, g);
+    WgradPlan p = {VQK_OK, WGF_GENERAL_F32, 0, 1, 0, 1, 0};
+    auto refuse = [&](int status) { p.status = status; return p; };
+    auto take = [&](int form, int tiles, WgradSplit s) { p.form = form; p.tiles = tiles; p.splits = s.splits; p.pps = s.pps; return p; };
+    const int rco = wgrad_op_check(q);
+    if (rco) return refuse(rco);
+    if (q.mode < 0 || q.mode > 1 || (q.stride != 1 && q.stride != 2) || q.pad < 0) return refuse(VQK_ERR_ARG);
+    // the kernel's channel counts: the pair operands' pixel pitches; with the roles swapped its "x" operand is dy_pooled
+    const bool fold = q.op == WGRAD_OP_FOLD, swapped = q.op == WGRAD_OP_POOLED_DY_PHASE;
+    const int cin = fold ? 2 * q.cin : swapped ? q.cout : q.cin, cout = fold ? 2 * q.cout : swapped ? q.cin : q.cout;
+    const int dtype = q.dtype, ksize = q.ksize;
+    const int rc = make_geom(g, dtype, q.n, q.h_in, q.w_in, cin, cout, ksize, q.mode);
+    if (rc) return refuse(rc);
+    if (cout % (dtype == VQK_F32 ? 4 : 8)) return refuse(VQK_ERR_SHAPE);
+    g.acc_scale = q.scale;                                       // dW += scale * (x^T dy): every kernel below scales its partial sums
+    const bool plain = q.stride == 1 && q.pad == (ksize >> 1) && q.h_out == g.h && q.w_out == g.w;
+    if (!plain) {
+        g.stride = q.stride; g.pad = q.pad;
+        if (q.h_out <= 0 || q.w_out <= 0) return refuse(VQK_ERR_SHAPE);
+        g.h = q.h_out; g.w = q.w_out;
+        const int64_t m = (int64_t)q.n * q.h_out * q.w_out;
+        if (m >= 0x7fffff00) return refuse(VQK_ERR_SHAPE);
+        g.m = (int)m;
+    }
+    const bool bf3 = plain && dtype == VQK_BF16 && ksize == 3;
+    if (bf3 && mx_wgrad_shape_ok(g.h, g.w, q.cin, q.cout) && mx_wgrad_enabled(q.op)) {
+        static const int forms[] = {WGF_MX, WGF_MX_POOLED_DY, WGF_MX_UPS_PHASE, WGF_MX_POOLED_DY_PHASE, WGF_MX_FOLD};
+        static const int dy_pools[] = {WGRAD_DY_PLAIN, WGRAD_DY_POOLED, WGRAD_DY_PHASES, WGRAD_DY_PHASES_SWAPPED, WGRAD_DY_PLAIN};
+        const bool per_phase = q.op == WGRAD_OP_UPS_PHASE && !VQK_TUNE("UPS_MERGE", 1);   // four launches, g.dy_pool = WGRAD_DY_PHASE0 + phase
+        g.dy_pool = per_phase ? (int)WGRAD_DY_PHASE0 : dy_pools[q.op];
+        g.fold = fold;
+        const int tiles = fold ? 3 * (cout / 128) * (cin / 128) : (cout / 64) * (cin / 64);
+        const WgradSplit s = split_mx(g.m, tiles, g.n * (g.h / 8) * (g.w / 16), g.dy_pool >= WGRAD_DY_PHASES ? 4 : 1, p.ordered);
+        p.launches = per_phase ? 4 : p.ordered ? 2 : 1;
+        return take(forms[q.op], tiles, s);
+    }
+    if (q.op != WGRAD_OP_PLAIN) return refuse(VQK_ERR_SHAPE);    // half-resolution dy, phases and pair operands exist on that kernel only
+    if (bf3 && (g.h % 8) == 0 && (g.w % 8) == 0 && !g_general_only) {
+        const bool pw16 = (g.w % 16) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0;
+        const int tiles = ((cout + 63) / 64) * ((cin + 63) / 64);
+        const WgradSplit s = split_halo(g.m, tiles, g.n * (g.h / 8) * (g.w / (pw16 ? 16 : 8)), pw16);
+        if (pw16 && (cin % 64) == 0 && (cout % 64) == 0 && VQK_TUNE("WGRAD_NO_P16K", 0) == 0) return take(WGF_P16, tiles, s);
+        return take(pw16 ? WGF_HALO16 : WGF_HALO8, tiles, s);
+    }
+    if (plain && dtype == VQK_F32 && ksize == 3 && q.mode == 0 && !g_det && !g_general_only && (g.w % 4) == 0) {
+        // the edge convs' weight gradients in the fp32 modes (conv_thin_f32.hip); maps too wide for one staged row in LDS take the
+        // general kernel below
+        const int rows = vqkd::thin_wgrad_rows(g.h, g.w);
+        auto wide = [](int c) { return c == 64 || c == 128 || c == 256; };
+        if (rows > 0 && cin == 4 && wide(cout)) return take(WGF_THIN_F32_CIN4, g.n * (g.h / rows), {1, rows});
+        if (rows > 0 && cout == 4 && wide(cin)) return take(WGF_THIN_F32_COUT4, g.n * (g.h / rows), {1, rows});
+    }
+    const bool db = dtype == VQK_BF16 && ksize == 1;
+    const int tiles = ((cout + 127) / 128) * ((cin + 127) / 128) * ksize * ksize;
+    const WgradSplit s = split_general(g.m, tiles, dtype == VQK_F32 ? 32 : 64, db, (int64_t)cout * ksize * ksize * cin);
+    p.ordered = g_det && s.splits > 1;
+    p.launches = p.ordered ? 2 : 1;
+    return take(dtype == VQK_F32 ? WGF_GENERAL_F32 : db ? WGF_GENERAL_DB : WGF_GENERAL_BF16, tiles, s);
+}
+
+// one helper per kernel template; it holds the kernel's dynamic-LDS attribute where the form needs more than 64 KiB.
+// The patch kernels (p16, halo): grid = dW tiles x splits
+template <auto KERNEL, int LDS>
+void launch_patch(const WgradPlan& p, const ConvGeom& g, const void* x, const void* dy, float* dw, const void* zeros, hipStream_t st) {
+    static const hipError_t attr = LDS > 65536 ? hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)
+                                               : hipSuccess;
+    (void)attr;
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)p.tiles, (unsigned)p.splits), dim3(256), LDS, st, (const bf16_raw*)x, (const bf16_raw*)dy, dw,
+                       (const char*)zeros, g, p.pps);
+}
+// the general kernels: grid = (cout x cin tiles, taps, splits); dst / sstride: dW itself, or the splits' private copies
+template <typename T>
+void launch_general(const WgradPlan& p, const ConvGeom& g, const void* x, const void* dy, float* dst, int64_t sstride, const void* zeros,
+                    hipStream_t st) {
+    const int taps = g.ks * g.ks;
+    hipLaunchKernelGGL(conv_wgrad_kernel<T>, dim3((unsigned)(p.tiles / taps), (unsigned)taps, (unsigned)p.splits), dim3(256), 32768, st,
+                       (const T*)x, (const T*)dy, dst, (const char*)zeros, g, p.pps, sstride);
+}
+int launch_general_db(const WgradPlan& p, const ConvGeom& g, const void* x, const void* dy, float* dst, int64_t sstride, const void* zeros,
+                      hipStream_t st) {
+    static const hipError_t attr = hipFuncSetAttribute((const void*)conv_wgrad_db_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    if (attr != hipSuccess) return VQK_ERR_LAUNCH;
+    hipLaunchKernelGGL(conv_wgrad_db_kernel, dim3((unsigned)p.tiles, 1, (unsigned)p.splits), dim3(256), 65536, st, (const bf16_raw*)x,
+                       (const bf16_raw*)dy, dst, (const char*)zeros, g, p.pps, sstride);
+    return VQK_OK;
+}
+
+// x, dy: the conv's input and the gradient of its output, as the entry point received them
+int launch_wgrad(const WgradPlan& p, const ConvGeom& g, const void* x, const void* dy, float* dw, const void* zeros, hipStream_t st) {
+    if (p.status != VQK_OK) return p.status;
+    switch (p.form) {
+    case WGF_MX:
+    case WGF_MX_POOLED_DY:
+    case WGF_MX_FOLD:
+        return vqkd::launch_conv3x3_wgrad_mx(x, dy, dw, zeros, g, p.tiles, p.splits, p.pps, st, p.ordered ? g_det_ws : nullptr);
+    case WGF_MX_POOLED_DY_PHASE:                                 // the kernel's windowed "x" operand is dy_pooled, its gathered "dy" is x
+        return vqkd::launch_conv3x3_wgrad_mx(dy, x, dw, zeros, g, p.tiles, 4 * p.splits, p.pps, st);
+    case WGF_MX_UPS_PHASE: {
+        if (p.launches == 1) return vqkd::launch_conv3x3_wgrad_mx(x, dy, dw, zeros, g, p.tiles, 4 * p.splits, p.pps, st);
+        ConvGeom gp = g;
+        for (int ph = 0; ph < p.launches; ++ph) {                // one launch per output phase (a, b) = (ph >> 1, ph & 1)
+            gp.dy_pool = WGRAD_DY_PHASE0 + ph;
+            const int rc = vqkd::launch_conv3x3_wgrad_mx(x, dy, dw, zeros, gp, p.tiles, p.splits, p.pps, st);
+            if (rc) return rc;
+        }
+        return VQK_OK;
+    }
+    case WGF_P16: launch_patch<conv3x3_wgrad_p16_kernel, 2 * 40960>(p, g, x, dy, dw, zeros, st); break;
+    case WGF_HALO16: launch_patch<conv3x3_wgrad_halo_kernel<true>, 2 * 40960>(p, g, x, dy, dw, zeros, st); break;
+    case WGF_HALO8: launch_patch<conv3x3_wgrad_halo_kernel<false>, 2 * 22528>(p, g, x, dy, dw, zeros, st); break;
+    case WGF_THIN_F32_CIN4:
+        return vqkd::launch_conv3x3_wgrad_thin_f32(0, (const float*)dy, (const float*)x, dw, g.n, g.h, g.w, g.cout, g.acc_scale, st);
+    case WGF_THIN_F32_COUT4:
+        return vqkd::launch_conv3x3_wgrad_thin_f32(1, (const float*)x, (const float*)dy, dw, g.n, g.h, g.w, g.cin, g.acc_scale, st);
+    case WGF_GENERAL_F32:
+    case WGF_GENERAL_BF16:
+    case WGF_GENERAL_DB: {
+        const int64_t dw_elems = (int64_t)g.cout * g.ks * g.ks * g.cin;
+        float* dst = p.ordered ? g_det_ws : dw;                  // deterministic: private copies of dW per split + ordered reduce
+        const int64_t sstride = p.ordered ? dw_elems : 0;
+        if (p.ordered && hipMemsetAsync(dst, 0, (size_t)p.splits * dw_elems * 4, st) != hipSuccess) return VQK_ERR_LAUNCH;
+        if (p.form == WGF_GENERAL_F32) launch_general<float>(p, g, x, dy, dst, sstride, zeros, st);
+        else if (p.form == WGF_GENERAL_BF16) launch_general<bf16_raw>(p, g, x, dy, dst, sstride, zeros, st);
+        else if (launch_general_db(p, g, x, dy, dst, sstride, zeros, st)) return VQK_ERR_LAUNCH;
+        if (p.ordered)
+            hipLaunchKernelGGL(wgrad_split_reduce_kernel, dim3((unsigned)((dw_elems + 255) / 256)), dim3(256), 0, st, (const float*)dst,
+                               dw_elems, p.splits, dw);
+        break;
+    }
+    case WGF_X3:
+    case WGF_X3_UPS_PHASE:
+    case WGF_X3_POOLED_PHASE:
+        return vqkd::launch_conv3x3_wgrad_x3(x, dy, dw, g, p.tiles, p.splits, p.pps, st);
+    default: return VQK_ERR_ARG;
+    }
     VQK_CHECK_LAUNCH();
     return VQK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// the one-layer entry points: the op's own refusals, the pointers, then the plan and what it names
+static int wgrad_run(const WgradProblem& q, const void* x, const void* dy, float* dw, const void* zeros, void* stream) {
+    const int rc = wgrad_op_check(q);
+    if (rc) return rc;
+    VQK_REQUIRE(x && dy && dw && zeros, VQK_ERR_ARG);
+    VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy) && vqk_aligned16(zeros), VQK_ERR_ALIGN);
+    ConvGeom g;
+    const WgradPlan p = plan_wgrad(q, g);
+    return launch_wgrad(p, g, x, dy, dw, zeros, vqk_stream(stream));
 }
 
 int vqk_conv2d_wgrad(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin, int cout,
                      int ksize, int ups, const void* zeros, void* stream) {
     VQK_REQUIRE(ups == 0 || ups == 1, VQK_ERR_ARG);
-    return wgrad_general(dtype, x, dy, dw, n, h_in, w_in, cin, cout, ksize, 1, ksize >> 1, ups, h_in << ups, w_in << ups,
-                         zeros, stream);
+    return wgrad_run({WGRAD_OP_PLAIN, dtype, n, h_in, w_in, cin, cout, ksize, 1, ksize >> 1, ups, h_in << ups, w_in << ups, 1.0f}, x, dy,
+                     dw, zeros, stream);
+}
+
+int vqk_conv2d_wgrad_general(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin,
+                             int cout, int ksize, int stride, int pad, int mode, int h_out, int w_out, const void* zeros,
+                             void* stream) {
+    return wgrad_run({WGRAD_OP_PLAIN, dtype, n, h_in, w_in, cin, cout, ksize, stride, pad, mode, h_out, w_out, 1.0f}, x, dy, dw, zeros,
+                     stream);
+}
+
+int vqk_conv2d_wgrad_general_scaled(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin,
+                                    int cout, int ksize, int stride, int pad, int mode, int h_out, int w_out, float scale,
+                                    const void* zeros, void* stream) {
+    return wgrad_run({WGRAD_OP_PLAIN, dtype, n, h_in, w_in, cin, cout, ksize, stride, pad, mode, h_out, w_out, scale}, x, dy, dw, zeros,
+                     stream);
+}
+
+int vqk_conv2d_wgrad_pooled_dy(int dtype, const void* x, const void* dy_pooled, float* dw, int n, int h, int w, int cin,
+                               int cout, float scale, const void* zeros, void* stream) {
+    return wgrad_run(plain3x3(WGRAD_OP_POOLED_DY, dtype, n, h, w, cin, cout, 0, scale), x, dy_pooled, dw, zeros, stream);
+}
+
+int vqk_conv2d_wgrad_ups_phase(int dtype, const void* x, const void* dy, float* dw, int n, int h, int w, int cin, int cout,
+                                float scale, const void* zeros, void* stream) {
+    return wgrad_run(plain3x3(WGRAD_OP_UPS_PHASE, dtype, n, h, w, cin, cout, 0, scale), x, dy, dw, zeros, stream);
+}
+
+int vqk_conv2d_wgrad_pooled_dy_phase(int dtype, const void* x, const void* dy_pooled, float* dw, int n, int h, int w, int cin,
+                                     int cout, float scale, const void* zeros, void* stream) {
+    // x [n, 2h, 2w, cin] (the conv's input), dy_pooled [n, h, w, cout]; dw[Cout][3][3][Cin] += scale * wgrad(x, unpool(dy_pooled));
+    // h, w: the POOLED grid
+    return wgrad_run(plain3x3(WGRAD_OP_POOLED_DY_PHASE, dtype, n, h, w, cin, cout, 0, scale), x, dy_pooled, dw, zeros, stream);
+}
+
+int vqk_conv2d_wgrad_x3(const void* x_pair, const void* dy_pair, float* dw, int n, int h_in, int w_in, int cin, int cout, int ups,
+                        float scale, const void* zeros, void* stream) {
+    // x_pair [n, h_in, w_in, 2 cin], dy_pair [n, h, w, 2 cout] bf16 (vqk_split_pair_f32); dw fp32 [cout][3][3][cin] +=
+    return wgrad_run(plain3x3(WGRAD_OP_FOLD, VQK_BF16, n, h_in, w_in, cin, cout, ups, scale), x_pair, dy_pair, dw, zeros, stream);
+}
+
+int vqk_conv2d_wgrad_x3_f32(const float* x, const float* dy, float* dw, int n, int h_in, int w_in, int cin, int cout, int ups,
+                            float scale, void* stream) {
+    // split-product weight gradient straight from the fp32 tensors (csrc/conv_x3.hip: conv3x3_wgrad_x3_kernel)
+    VQK_REQUIRE(x && dy && dw, VQK_ERR_ARG);
+    VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy), VQK_ERR_ALIGN);
+    ConvGeom g;
+    const WgradPlan p = plan_wgrad({WGRAD_OP_X3, VQK_F32, n, h_in, w_in, cin, cout, 3, 1, 1, ups, 0, 0, scale}, g);
+    return launch_wgrad(p, g, x, dy, dw, nullptr, vqk_stream(stream));
+}
+
+int vqk_conv_wgrad_plan(int op, int dtype, int n, int h_in, int w_in, int cin, int cout, int ksize, int stride, int pad, int ups,
+                        int h_out, int w_out, int* details) {
+    VQK_REQUIRE(op >= WGRAD_OP_PLAIN && op <= WGRAD_OP_X3, VQK_ERR_ARG);
+    ConvGeom g;
+    WgradProblem q = {op, dtype, n, h_in, w_in, cin, cout, ksize, stride, pad, ups, h_out, w_out, 1.0f};
+    if (op == WGRAD_OP_X3) q.dtype = VQK_F32;                    // (the tensors' dtype is the entry point's own)
+    else if (op != WGRAD_OP_PLAIN) q = plain3x3(op, op == WGRAD_OP_FOLD ? (int)VQK_BF16 : dtype, n, h_in, w_in, cin, cout, op == WGRAD_OP_FOLD ? ups : 0, 1.0f);
+    const WgradPlan p = plan_wgrad(q, g);
+    if (p.status != VQK_OK) return p.status;
+    if (details) {
+        details[0] = p.tiles; details[1] = p.splits; details[2] = p.pps; details[3] = p.launches;
+        details[4] = p.form == WGF_THIN_F32_CIN4 || p.form == WGF_THIN_F32_COUT4;
+    }
+    return p.form;
+}
+
+const char* vqk_conv_wgrad_form_name(int form, int dtype) {
+    static const char* const names[WGF_COUNT] = {
+        "conv3x3_wgrad_mx_kernel<bf16>", "conv3x3_wgrad_mx_kernel<bf16>", "conv3x3_wgrad_mx_kernel<bf16>", "conv3x3_wgrad_mx_kernel<bf16>",
+        "conv3x3_wgrad_mx_kernel<f32 as 3 x bf16>", "conv3x3_wgrad_p16_kernel<bf16>", "conv3x3_wgrad_halo_kernel<bf16>",
+        "conv3x3_wgrad_halo_kernel<bf16>", "conv3x3_wgrad_thin_f32_kernel (HBM)", "conv3x3_wgrad_thin_f32_kernel (HBM)",
+        "conv_wgrad_kernel<f32>", "conv_wgrad_kernel<bf16>", "conv_wgrad_db_kernel<bf16>", "conv3x3_wgrad_x3_kernel<f32 as 3 x bf16>",
+        "conv3x3_wgrad_x3_kernel<f32 as 3 x bf16>", "conv3x3_wgrad_x3_kernel<f32 as 3 x bf16>",
+    };
+    if (form < 0 || form >= WGF_COUNT || (dtype != VQK_F32 && dtype != VQK_BF16)) return "?";
+    return names[form];                                          // (every form exists for one dtype)
 }
 
 // ---------------------------------------------------------------- grouped 3x3 weight gradients (include/vqk.h)
+
 // Partition of one launch of <= 16 layers.  Unit of work: one 8x16-pixel patch of one 64 x 64 x 9 dW tile (72 MFMAs per M wave,
 // ~1.8 us at the 0.55 of peak the kernel sustains).  W = sum tiles_i * patches_i; one 120-KiB block per CU, so the even share of
 // the 256 CUs is A = W / 256 patches.  A block of layer i runs patches_i / splits_i patches; blocks start longest first, so the
@@ -861,13 +1118,12 @@ static int wgrad_group_plan(const vqk_wgrad_item* it, int n, int* splits, int* p
 static int wgrad_group_check(const vqk_wgrad_item* items, int n_items) {
     VQK_REQUIRE(items && n_items >= 1, VQK_ERR_ARG);
     // the ordered-workspace path of deterministic mode belongs to the one-layer launch; so do the test hook and the A/B slots
-    VQK_REQUIRE(!g_det && !g_general_only && VQK_TUNE("WGMX", 1) && VQK_TUNE("WGRAD_BLOCKS", 0) == 0
-                && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
+    VQK_REQUIRE(mx_wgrad_enabled(WGRAD_OP_PLAIN, true), VQK_ERR_SHAPE);
     for (int i = 0; i < n_items; ++i) {
         const vqk_wgrad_item& q = items[i];
         VQK_REQUIRE(q.x && q.dy && q.dw, VQK_ERR_ARG);
-        VQK_REQUIRE(q.dtype == VQK_BF16 && q.ksize == 3 && q.ups == 0 && q.n >= 1 && q.h >= 8 && q.w >= 16 && (q.h % 8) == 0
-                    && (q.w % 16) == 0 && q.cin >= 64 && q.cout >= 64 && (q.cin % 64) == 0 && (q.cout % 64) == 0, VQK_ERR_SHAPE);
+        VQK_REQUIRE(q.dtype == VQK_BF16 && q.ksize == 3 && q.ups == 0 && q.n >= 1 && q.h >= 8 && q.w >= 16 && q.cin >= 64 && q.cout >= 64
+                    && mx_wgrad_shape_ok(q.h, q.w, q.cin, q.cout), VQK_ERR_SHAPE);
         VQK_REQUIRE((int64_t)q.n * q.h * q.w < 0x7fffff00 && (int64_t)q.n * q.h * q.w * (q.cin > q.cout ? q.cin : q.cout) < (1ll << 31),
                     VQK_ERR_SHAPE);                              // 32-bit byte offsets inside a patch, as in the one-layer launch
         VQK_REQUIRE(vqk_aligned16(q.x) && vqk_aligned16(q.dy) && vqk_aligned16(q.dw), VQK_ERR_ALIGN);
@@ -924,87 +1180,6 @@ int vqk_conv3x3_wgrad_group(const vqk_wgrad_item* items, int n_items, const void
         if (rl) return rl;
     }
     return VQK_OK;
-}
-
-int vqk_conv2d_wgrad_x3_f32(const float* x, const float* dy, float* dw, int n, int h_in, int w_in, int cin, int cout, int ups,
-                            float scale, void* stream) {
-    // split-product weight gradient straight from the fp32 tensors (csrc/conv_x3.hip: conv3x3_wgrad_x3_kernel)
-    VQK_REQUIRE(x && dy && dw, VQK_ERR_ARG);
-    VQK_REQUIRE(vqk_aligned16(x) && vqk_aligned16(dy), VQK_ERR_ALIGN);
-    VQK_REQUIRE(ups == 0 || ups == 1 || ups == 2, VQK_ERR_ARG);
-    VQK_REQUIRE(!g_det && !g_general_only, VQK_ERR_SHAPE);      // atomics only: deterministic mode keeps the exact-fp32 kernel
-    ConvGeom g;
-    if (ups == 2 || (ups == 1 && VQK_TUNE("X3_WGRAD_PHASE", 1) && (h_in % 8) == 0 && (w_in % 8) == 0)) {
-        // the 2x2-resampling convs in phase form (4/9 of the MFMAs): patches over the LOW-resolution grid.  ups = 1: x [n][h_in][w_in] is
-        // that grid, dy [n][2 h_in][2 w_in]; ups = 2: dy = the pooled gradient [n][h_in / 2][w_in / 2] of a conv over x [n][h_in][w_in]
-        VQK_REQUIRE(ups == 1 || ((h_in % 16) == 0 && (w_in % 16) == 0), VQK_ERR_SHAPE);
-        const int hl = ups == 2 ? h_in / 2 : h_in, wl = ups == 2 ? w_in / 2 : w_in;
-        const int rcp = make_geom(g, VQK_F32, n, hl, wl, cin, cout, 3, 0);
-        if (rcp) return rcp;
-        g.ntap = 4; g.phase_mode = ups == 2 ? 2 : 1;
-        g.acc_scale = scale;
-        return vqkd::launch_conv3x3_wgrad_x3(x, dy, dw, g, g_wgrad_blocks, vqk_stream(stream));
-    }
-    const int rc = make_geom(g, VQK_F32, n, h_in, w_in, cin, cout, 3, ups);
-    if (rc) return rc;
-    g.acc_scale = scale;
-    return vqkd::launch_conv3x3_wgrad_x3(x, dy, dw, g, g_wgrad_blocks, vqk_stream(stream));
-}
-
-int vqk_conv2d_wgrad_x3(const void* x_pair, const void* dy_pair, float* dw, int n, int h_in, int w_in, int cin, int cout, int ups,
-                        float scale, const void* zeros, void* stream) {
-    // x_pair [n, h_in, w_in, 2 cin], dy_pair [n, h, w, 2 cout] bf16 (vqk_split_pair_f32); dw fp32 [cout][3][3][cin] +=
-    VQK_REQUIRE(ups == 0 || ups == 1, VQK_ERR_ARG);
-    VQK_REQUIRE((cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
-    return wgrad_general(VQK_BF16, x_pair, dy_pair, dw, n, h_in, w_in, 2 * cin, 2 * cout, 3, 1, 1, ups, h_in << ups, w_in << ups,
-                         zeros, stream, 0, scale, 1);
-}
-
-int vqk_conv2d_wgrad_pooled_dy(int dtype, const void* x, const void* dy_pooled, float* dw, int n, int h, int w, int cin,
-                               int cout, float scale, const void* zeros, void* stream) {
-    VQK_REQUIRE(dtype == VQK_BF16 && (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
-    const int wgmx = VQK_TUNE("WGMX", 1);
-    VQK_REQUIRE(wgmx && !g_general_only && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0, VQK_ERR_SHAPE);
-    return wgrad_general(dtype, x, dy_pooled, dw, n, h, w, cin, cout, 3, 1, 1, 0, h, w, zeros, stream, 1, scale);
-}
-
-int vqk_conv2d_wgrad_ups_phase(int dtype, const void* x, const void* dy, float* dw, int n, int h, int w, int cin, int cout,
-                                float scale, const void* zeros, void* stream) {
-    VQK_REQUIRE(dtype == VQK_BF16 && (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
-    const int wgmx = VQK_TUNE("WGMX", 1);
-    VQK_REQUIRE(wgmx && !g_general_only && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0 && !g_det,
-                VQK_ERR_SHAPE);
-    if (VQK_TUNE("UPS_MERGE", 1))                                // the four output phases as ONE launch (phase = a dimension of the grid)
-        return wgrad_general(dtype, x, dy, dw, n, h, w, cin, cout, 3, 1, 1, 0, h, w, zeros, stream, 6, scale);
-    for (int ph = 0; ph < 4; ++ph) {                             // one launch per output phase (a, b) = (ph >> 1, ph & 1)
-        const int rc = wgrad_general(dtype, x, dy, dw, n, h, w, cin, cout, 3, 1, 1, 0, h, w, zeros, stream, 2 + ph, scale);
-        if (rc) return rc;
-    }
-    return VQK_OK;
-}
-
-int vqk_conv2d_wgrad_pooled_dy_phase(int dtype, const void* x, const void* dy_pooled, float* dw, int n, int h, int w, int cin,
-                                     int cout, float scale, const void* zeros, void* stream) {
-    // x [n, 2h, 2w, cin] (the conv's input), dy_pooled [n, h, w, cout]; dw[Cout][3][3][Cin] += scale * wgrad(x, unpool(dy_pooled)).
-    // The phase-form kernel with the operands' roles swapped (conv_wgmx.hip, dy_pool = 7): its "x" operand is dy_pooled (cout
-    // channels), its phase-gathered "dy" operand is x (cin channels); h, w: the POOLED grid.
-    VQK_REQUIRE(dtype == VQK_BF16 && (h % 8) == 0 && (w % 16) == 0 && (cin % 64) == 0 && (cout % 64) == 0, VQK_ERR_SHAPE);
-    const int wgmx = VQK_TUNE("WGMX", 1);
-    VQK_REQUIRE(wgmx && !g_general_only && VQK_TUNE("WGRAD_BLOCKS", 0) == 0 && VQK_TUNE("WGRAD_NO_PW16", 0) == 0 && !g_det &&
-                VQK_TUNE("UPS_MERGE", 1) != 0, VQK_ERR_SHAPE);
-    return wgrad_general(dtype, dy_pooled, x, dw, n, h, w, cout, cin, 3, 1, 1, 0, h, w, zeros, stream, 7, scale);
-}
-
-int vqk_conv2d_wgrad_general(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin,
-                             int cout, int ksize, int stride, int pad, int mode, int h_out, int w_out, const void* zeros,
-                             void* stream) {
-    return wgrad_general(dtype, x, dy, dw, n, h_in, w_in, cin, cout, ksize, stride, pad, mode, h_out, w_out, zeros, stream);
-}
-
-int vqk_conv2d_wgrad_general_scaled(int dtype, const void* x, const void* dy, float* dw, int n, int h_in, int w_in, int cin,
-                                    int cout, int ksize, int stride, int pad, int mode, int h_out, int w_out, float scale,
-                                    const void* zeros, void* stream) {
-    return wgrad_general(dtype, x, dy, dw, n, h_in, w_in, cin, cout, ksize, stride, pad, mode, h_out, w_out, zeros, stream, 0, scale);
 }
 
 }  // extern "C"

@@ -642,25 +642,13 @@ int launch_conv3x3_x3(const void* x, const void* w, const float* bias, const voi
 
 namespace vqkd {
 // x fp32 [n][h_in][w_in][cin], dy fp32 [n][h][w][cout], dw fp32 [cout][3][3][cin] +=; cin % 64 == 0, cout % 64 == 0, h % 8 == 0, w % 8 == 0.
-// g.ntap == 4 (g.phase_mode 1 | 2): the phase forms -- g.h x g.w is the LOW-resolution grid, see the kernel
-int launch_conv3x3_wgrad_x3(const void* x, const void* dy, float* dw, const ConvGeom& g, int blocks_cap, hipStream_t st) {
+// g.ntap == 4 (g.phase_mode 1 | 2): the phase forms -- g.h x g.w is the LOW-resolution grid, see the kernel.  tiles, splits and pps
+// come from the launch plan (conv_wgrad.hip::plan_wgrad), as for launch_conv3x3_wgrad_mx
+int launch_conv3x3_wgrad_x3(const void* x, const void* dy, float* dw, const ConvGeom& g, int tiles, int splits, int pps, hipStream_t st) {
     if ((g.cin & 63) || (g.cout & 63) || (g.h & 7) || (g.w & 7) || g.ks != 3) return VQK_ERR_SHAPE;
     const int phases = g.ntap == 4 ? 4 : 1;
     if (phases == 4 && (g.ups || (g.phase_mode != 1 && g.phase_mode != 2))) return VQK_ERR_SHAPE;
-    const int tiles = (g.cout >> 6) * (g.cin >> 6);
-    const int total_patches = g.n * (g.h >> 3) * (g.w >> 3);
-    // split-K over pixel patches: the cost model of the bf16 kernels (conv.hip::wgrad_general) with a third of their atomic passes
-    // per multiply-add -- s* = sqrt(c * pixels / tiles) under the block cap (two blocks per CU)
-    int cap = blocks_cap > 0 ? blocks_cap : 512;
-    if (phases == 4) cap = cap * VQK_TUNE("X3_WGRAD_PHASE_CAP_PCT", 150) / 100;      // 166 VGPRs: a third block fits a CU (step 70.39 -> 69.89 ms)
-    const double coef = (phases == 4 ? VQK_TUNE("X3_WGRAD_PHASE_COEF_E4", 3200) : VQK_TUNE("X3_WGRAD_COEF_E4", 3200)) * 1e-4;
-    // (phase forms: the four phases are four times the blocks -- a quarter of the splits each, the same number of atomic passes)
-    int splits = (int)(sqrt(coef * (double)g.m * phases / tiles) / phases + 0.5);
-    if (splits > (cap + tiles * phases - 1) / (tiles * phases)) splits = (cap + tiles * phases - 1) / (tiles * phases);
-    if (splits > (total_patches + 3) / 4) splits = (total_patches + 3) / 4;          // >= 256 pixels per block
-    if (splits < 1) splits = 1;
-    const int pps = (total_patches + splits - 1) / splits;
-    splits = (total_patches + pps - 1) / pps;
+    if (tiles != (g.cout >> 6) * (g.cin >> 6) || splits < 1 || pps < 1) return VQK_ERR_ARG;
     constexpr int lds = 2 * 22784;
     if (phases == 4)
         hipLaunchKernelGGL(conv3x3_wgrad_x3_kernel<4>, dim3((unsigned)tiles, (unsigned)(splits * 4)), dim3(256), lds, st, (const float*)x,

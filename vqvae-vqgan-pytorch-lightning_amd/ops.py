@@ -254,11 +254,41 @@ def _fprop_event(x, out_dtype, cout: int, ksize: int, ups, act: int, wlayout: in
     return name, (0.0 if details[4] else flops)
 
 
+_WG_PLAIN, _WG_POOLED_DY, _WG_UPS_PHASE, _WG_POOLED_DY_PHASE, _WG_FOLD, _WG_X3 = range(6)     # ops of vqk_conv_wgrad_plan (include/vqk.h)
+
+
+def _wgrad_event(op: int, x, cout: int, h: int, w: int, ksize: int, ups: int, flops: float, shape_tag: str = ''):
+    """(label, FLOPs, executed FLOPs, launches, bytes) of a one-layer weight gradient for the event statistics, from the library's own launch
+    plan (vqk_conv_wgrad_plan; op, h, w, ups as that op's entry point takes them).  None: the plan refuses, the entry point launches nothing."""
+    details, (n, cin) = (ctypes.c_int * 5)(), x.shape[:2]
+    form = _native.lib().vqk_conv_wgrad_plan(op, dcode(x.dtype), n, h, w, cin, cout, ksize, 1, ksize >> 1, ups, h << (ups == 1),
+                                             w << (ups == 1), details)
+    if form < 0:
+        return None
+    name = _native.lib().vqk_conv_wgrad_form_name(form, dcode(x.dtype)).decode()
+    if _EVENT_SHAPES:                                            # tooling (tools/per_shape.py): one line per layer shape
+        name += f' {cin}->{cout}@{shape_tag}' + (' phase' if form in (2, 3, 14) else '')      # (the phase forms chosen inside the library)
+    # memory-bound (a plain conv): the bytes of x and dy, no FLOPs; phase forms (2, 3, 14, 15) execute 4/9, split-product forms (4, 13, 14, 15) x 3
+    scale = 0.0 if details[4] else (4.0 / 9.0 if form in (2, 3, 14, 15) else 1.0) * (3.0 if form in (4, 13, 14, 15) else 1.0)
+    return name, flops if scale else 0.0, flops * scale, details[3], 0.0 if scale else x.element_size() * (x.numel() + n * cout * h * w)
+
+
+def _run_wgrad(what: str, launch, *event, must: bool = False) -> bool:
+    """a weight-gradient entry point, timed under ``_wgrad_event(*event)`` while events are recorded; False: VQK_ERR_SHAPE, nothing launched"""
+    ev = _wgrad_event(*event) if KERNEL_EVENTS is not None else None
+    st = launch() if ev is None else _timed(ev[0], ev[1], launch, ev[4], ev[3], ev[2])
+    _native.check(0 if st == _native.ERR_SHAPE and not must else st, what)
+    return st == 0
+
+
+def _whole_tiles(cin: int, cout: int, h: int, w: int, ph: int = 8, pw: int = 16) -> bool:     # 64-channel dW tiles over ph x pw patches
+    return cin % 64 == 0 and cout % 64 == 0 and h % ph == 0 and w % pw == 0
+
+
 def _thin_out_bf16(dtype, out_dtype, cin, cout, ksize, ups, h, w) -> bool:
     """the decoder's last conv: 8 output channels on 16x16x32 MFMAs (vqk_conv2d_thin_out, csrc/conv_edge.hip; plain weights)"""
     return (_THIN_OUT and ksize == 3 and not ups and dtype == torch.bfloat16 and out_dtype in (None, torch.bfloat16)
             and cin == 128 and cout == 8 and h % 8 == 0 and w % 32 == 0)
-
 
 
 def weight_layout(dtype, n, h_in, w_in, cin, cout, ksize, ups, out_dtype=None, x3=None) -> int:
@@ -888,8 +918,8 @@ def _edge_ws(device) -> torch.Tensor:
 def edge_wgrad_served(x, dy, ksize: int, ups: bool) -> bool:
     """the K = 72 weight-gradient kernel of the two edge convs (padded 3-channel image / reconstruction) serves this problem"""
     n, cin, h, w = x.shape
-    return (_EDGE_WGRAD and x.dtype == torch.bfloat16 and ksize == 3 and not ups and (cin, dy.shape[1]) in ((8, 128), (128, 8))
-            and (h * w) % 128 == 0 and (w % 128 == 0 or 128 % w == 0))
+    return (_EDGE_WGRAD and ksize == 3 and not ups and min(cin, dy.shape[1]) == 8        # (asked for the thin convs only)
+            and _native.lib().vqk_conv2d_wgrad_edge_serves(dcode(x.dtype), n, h, w, cin, dy.shape[1]) == 1)
 
 
 def raw_split_pair(t) -> torch.Tensor:
@@ -932,49 +962,30 @@ def raw_conv_wgrad(x, dy, ksize: int, ups: bool, out=None, thin_true: int = 8, x
         return dw
     if thin_true != 8:
         raise RuntimeError('vqk: an unpadded weight-gradient target needs the edge-conv kernel')
-    if (x3 and not X3_WGRAD_FOLD and x.dtype == torch.float32 and dy.dtype == torch.float32 and ksize == 3 and cin % 64 == 0
-            and cout % 64 == 0 and dy.shape[3] % 8 == 0 and dy.shape[2] % 8 == 0 and not DETERMINISTIC):
-        # split-product mode: both fp32 operands split in registers on their way into LDS, three products per staged fragment pair
-        # (csrc/conv_x3.hip: conv3x3_wgrad_x3_kernel)
-        phase = bool(ups) and X3_WGRAD_PHASE and h % 8 == 0 and w % 8 == 0      # (the library's own rule: include/vqk.h)
-        st = _timed('conv3x3_wgrad_x3_kernel<f32 as 3 x bf16>' + (f' {cin}->{cout}@{dy.shape[2]}x{dy.shape[3]} k3{" phase" if phase else ""}' if _EVENT_SHAPES else ''), flops,
-                    lambda: _native.lib().vqk_conv2d_wgrad_x3_f32(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), n, h, w, cin, cout, int(ups),
-                                                                  1.0, _stream()), exec_flops=3.0 * flops * (4.0 / 9.0 if phase else 1.0))
-        if st != _native.ERR_SHAPE:
-            _native.check(st, 'conv2d_wgrad_x3_f32')
-            return dw
-    if (x3 and x.dtype == torch.float32 and dy.dtype == torch.float32 and ksize == 3 and cin % 64 == 0 and cout % 64 == 0
-            and dy.shape[3] % 16 == 0 and dy.shape[2] % 8 == 0 and not DETERMINISTIC and _WGMX_ON):
-        # split-product mode: both operands as (hi | lo) bf16 pair tensors, three tile classes of one launch of the bf16
-        # matrix/auxiliary-wave weight-gradient kernel folded onto dW (csrc/conv_wgmx.hip, ConvGeom::fold)
+    tag = f'{dy.shape[2]}x{dy.shape[3]} k{ksize}' if _EVENT_SHAPES else ''
+    lib, ptrs, dims = _native.lib(), (x.data_ptr(), dy.data_ptr(), dw.data_ptr()), (n, h, w, cin, cout)
+    x3 = x3 and x.dtype == torch.float32 and dy.dtype == torch.float32 and ksize == 3 and not DETERMINISTIC
+    # split-product mode: both fp32 operands split in registers on their way into LDS (csrc/conv_x3.hip: conv3x3_wgrad_x3_kernel)
+    if (x3 and not X3_WGRAD_FOLD and _whole_tiles(cin, cout, dy.shape[2], dy.shape[3], 8, 8)
+            and _run_wgrad('conv2d_wgrad_x3_f32', lambda: lib.vqk_conv2d_wgrad_x3_f32(*ptrs, *dims, int(ups), 1.0, _stream()),
+                           _WG_X3, x, cout, h, w, 3, int(ups), flops, tag)):
+        return dw
+    if x3 and _WGMX_ON and _whole_tiles(cin, cout, dy.shape[2], dy.shape[3]):
+        # ... or as (hi | lo) bf16 pair tensors: three tile classes of one matrix/auxiliary-wave launch folded onto dW (conv_wgmx.hip, ConvGeom::fold)
         xp, dyp = raw_split_pair(x), raw_split_pair(dy)
-        st = _timed('conv3x3_wgrad_mx_kernel<f32 as 3 x bf16>' + (f' {cin}->{cout}@{dy.shape[2]}x{dy.shape[3]} k3' if _EVENT_SHAPES else ''), flops,
-                    lambda: _native.lib().vqk_conv2d_wgrad_x3(xp.data_ptr(), dyp.data_ptr(), dw.data_ptr(), n, h, w, cin, cout, int(ups),
-                                                              1.0, zero_page(x.device).data_ptr(), _stream()), exec_flops=3.0 * flops)
-        if st != _native.ERR_SHAPE:
-            _native.check(st, 'conv2d_wgrad_x3')
+        if _run_wgrad('conv2d_wgrad_x3', lambda: lib.vqk_conv2d_wgrad_x3(xp.data_ptr(), dyp.data_ptr(), ptrs[2], *dims, int(ups), 1.0,
+                                                                         zero_page(x.device).data_ptr(), _stream()),
+                      _WG_FOLD, x, cout, h, w, 3, int(ups), flops, tag):
             return dw
-    if (ups and UPS_PHASE_WGRAD and _WGMX_ON and x.dtype == torch.bfloat16 and ksize == 3 and cin % 64 == 0 and cout % 64 == 0
-            and w % 16 == 0 and h % 8 == 0 and not DETERMINISTIC):
-        # the upsample conv's weight gradient in phase form: four 2x2-window launches on the LOW-resolution input, 4/9 of the
-        # multiply-adds (csrc/conv_wgmx.hip, NT = 4)
-        st = _timed('conv3x3_wgrad_mx_kernel<bf16>' + (f' {cin}->{cout}@{dy.shape[2]}x{dy.shape[3]} k{ksize} phase' if _EVENT_SHAPES else ''), flops,
-                    lambda: _native.lib().vqk_conv2d_wgrad_ups_phase(dcode(x.dtype), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), n, h, w,
-                                                                     cin, cout, 1.0, zero_page(x.device).data_ptr(), _stream()),
-                    launches=4, exec_flops=flops * 4.0 / 9.0)
-        if st != _native.ERR_SHAPE:
-            _native.check(st, 'conv2d_wgrad_ups_phase')
-            return dw
-    mxw = (_WGMX_ON and x.dtype == torch.bfloat16 and ksize == 3 and cin % 64 == 0 and cout % 64 == 0
-           and dy.shape[3] % 16 == 0 and dy.shape[2] % 8 == 0)
-    kname = 'conv3x3_wgrad_mx_kernel<bf16>' if mxw else f'conv_wgrad_kernel<{"f32" if x.dtype == torch.float32 else "bf16"}>'
-    if _EVENT_SHAPES:
-        kname += f' {cin}->{cout}@{dy.shape[2]}x{dy.shape[3]} k{ksize}'
-    st = _timed(kname, flops,
-                lambda: _native.lib().vqk_conv2d_wgrad(dcode(x.dtype), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), n, h,
-                                                       w, cin, cout, ksize, int(ups),
-                                                       zero_page(x.device).data_ptr(), _stream()))
-    _native.check(st, 'conv2d_wgrad')
+    # the upsample conv in phase form: 2x2-window launches on the LOW-resolution input, 4/9 of the multiply-adds (conv_wgmx.hip, NT = 4)
+    if (ups and UPS_PHASE_WGRAD and _WGMX_ON and x.dtype == torch.bfloat16 and ksize == 3 and _whole_tiles(cin, cout, h, w)
+            and not DETERMINISTIC
+            and _run_wgrad('conv2d_wgrad_ups_phase', lambda: lib.vqk_conv2d_wgrad_ups_phase(dcode(x.dtype), *ptrs, *dims, 1.0,
+                                                                                            zero_page(x.device).data_ptr(), _stream()),
+                           _WG_UPS_PHASE, x, cout, h, w, 3, 0, flops, tag)):
+        return dw
+    _run_wgrad('conv2d_wgrad', lambda: lib.vqk_conv2d_wgrad(dcode(x.dtype), *ptrs, *dims, ksize, int(ups), zero_page(x.device).data_ptr(),
+                                                            _stream()), _WG_PLAIN, x, cout, h, w, ksize, int(ups), flops, tag, must=True)
     return dw
 
 
@@ -987,17 +998,13 @@ def raw_conv_wgrad_pooled_x3(x, dy_pooled, scale: float, out) -> bool:
     False: not served, nothing launched."""
     n, cin, h, w = x.shape
     cout = dy_pooled.shape[1]
-    if (not X3_WGRAD_PHASE or x.dtype != torch.float32 or dy_pooled.dtype != torch.float32 or cin % 64 or cout % 64 or h % 16 or w % 16
+    if (not X3_WGRAD_PHASE or x.dtype != torch.float32 or dy_pooled.dtype != torch.float32 or not _whole_tiles(cin, cout, h, w, 16, 16)
             or DETERMINISTIC or tuple(dy_pooled.shape[2:]) != (h // 2, w // 2)):
         return False
     flops = 2.0 * n * h * w * cout * cin * 9
-    st = _timed('conv3x3_wgrad_x3_kernel<f32 as 3 x bf16>' + (f' {cin}->{cout}@{h}x{w} k3 pooled-dy phase' if _EVENT_SHAPES else ''), flops,
-                lambda: _native.lib().vqk_conv2d_wgrad_x3_f32(x.data_ptr(), dy_pooled.data_ptr(), out.data_ptr(), n, h, w, cin, cout, 2,
-                                                              float(scale), _stream()), exec_flops=3.0 * flops * 4.0 / 9.0)
-    if st == _native.ERR_SHAPE:
-        return False
-    _native.check(st, 'conv2d_wgrad_x3_f32')
-    return True
+    return _run_wgrad('conv2d_wgrad_x3_f32', lambda: _native.lib().vqk_conv2d_wgrad_x3_f32(x.data_ptr(), dy_pooled.data_ptr(), out.data_ptr(),
+                                                                                           n, h, w, cin, cout, 2, float(scale), _stream()),
+                      _WG_X3, x, cout, h, w, 3, 2, flops, f'{h}x{w} k3 pooled-dy phase' if _EVENT_SHAPES else '')
 
 
 def raw_conv_wgrad_pooled_dy(x, dy_pooled, scale: float, out) -> bool:
@@ -1005,27 +1012,19 @@ def raw_conv_wgrad_pooled_dy(x, dy_pooled, scale: float, out) -> bool:
     kernel does not serve the problem (nothing launched)."""
     n, cin, h, w = x.shape
     cout = dy_pooled.shape[1]
-    if not (_WGMX_ON and x.dtype == torch.bfloat16 and cin % 64 == 0 and cout % 64 == 0 and w % 16 == 0 and h % 8 == 0):
+    if not (_WGMX_ON and x.dtype == torch.bfloat16 and _whole_tiles(cin, cout, h, w)):
         return False
     flops = 2.0 * n * h * w * cout * cin * 9
-    if POOLED_WGRAD_PHASE and not DETERMINISTIC and (h // 2) % 8 == 0 and (w // 2) % 16 == 0:
-        # phase form (operands' roles swapped, csrc/conv_wgmx.hip): 4/9 of the multiply-adds
-        st = _timed('conv3x3_wgrad_mx_kernel<bf16>' + (f' {cin}->{cout}@{h}x{w} pooled-dy phase' if _EVENT_SHAPES else ''), flops,
-                    lambda: _native.lib().vqk_conv2d_wgrad_pooled_dy_phase(dcode(x.dtype), x.data_ptr(), dy_pooled.data_ptr(), out.data_ptr(),
-                                                                           n, h // 2, w // 2, cin, cout, float(scale),
-                                                                           zero_page(x.device).data_ptr(), _stream()),
-                    exec_flops=flops * 4.0 / 9.0)
-        if st != _native.ERR_SHAPE:
-            _native.check(st, 'conv2d_wgrad_pooled_dy_phase')
-            return True
-    st = _timed('conv3x3_wgrad_mx_kernel<bf16>' + (f' {cin}->{cout}@{h}x{w} pooled-dy' if _EVENT_SHAPES else ''), flops,
-                lambda: _native.lib().vqk_conv2d_wgrad_pooled_dy(dcode(x.dtype), x.data_ptr(), dy_pooled.data_ptr(), out.data_ptr(),
-                                                                 n, h, w, cin, cout, float(scale),
-                                                                 zero_page(x.device).data_ptr(), _stream()))
-    if st == _native.ERR_SHAPE:
-        return False
-    _native.check(st, 'conv2d_wgrad_pooled_dy')
-    return True
+    tag = f'{h}x{w} pooled-dy' if _EVENT_SHAPES else ''
+    lib, head = _native.lib(), (dcode(x.dtype), x.data_ptr(), dy_pooled.data_ptr(), out.data_ptr(), n)
+    # phase form (operands' roles swapped, csrc/conv_wgmx.hip): 4/9 of the multiply-adds
+    if (POOLED_WGRAD_PHASE and not DETERMINISTIC and _whole_tiles(cin, cout, h, w, 16, 32)
+            and _run_wgrad('conv2d_wgrad_pooled_dy_phase', lambda: lib.vqk_conv2d_wgrad_pooled_dy_phase(
+                *head, h // 2, w // 2, cin, cout, float(scale), zero_page(x.device).data_ptr(), _stream()),
+                _WG_POOLED_DY_PHASE, x, cout, h // 2, w // 2, 3, 0, flops, tag)):
+        return True
+    return _run_wgrad('conv2d_wgrad_pooled_dy', lambda: lib.vqk_conv2d_wgrad_pooled_dy(
+        *head, h, w, cin, cout, float(scale), zero_page(x.device).data_ptr(), _stream()), _WG_POOLED_DY, x, cout, h, w, 3, 0, flops, tag)
 
 
 def raw_colsum(x2d_rows: int, c: int, x, out=None, lead: int | None = None, scale: float = 1.0) -> torch.Tensor:
@@ -1930,8 +1929,8 @@ def wgrad_group_deferrable(x, dy, target, x3: bool = False, ksize: int = 3, ups:
     64-channel tiles, a map of at most WGRAD_GROUP_MAX_HW pixels, not in deterministic / split-product mode"""
     n, cin, h, w = x.shape
     return (WGRAD_GROUP_MAX_HW > 0 and target is not None and not x3 and not DETERMINISTIC and _WGMX_ON and ksize == 3 and not ups
-            and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and h * w <= WGRAD_GROUP_MAX_HW and h % 8 == 0
-            and w % 16 == 0 and cin % 64 == 0 and dy.shape[1] % 64 == 0 and tuple(dy.shape[2:]) == (h, w))
+            and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and h * w <= WGRAD_GROUP_MAX_HW
+            and _whole_tiles(cin, dy.shape[1], h, w) and tuple(dy.shape[2:]) == (h, w))
 
 
 def defer_wgrad(x, dy, target) -> None:
